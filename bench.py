@@ -7,11 +7,16 @@ sharded, one process per GPU; the only exchange of a pass is ONE all-gather of t
 A "step" = one pass of the hot path over the batch: Philox + Box-Muller + SDE sub-steps, cashflows / regression exposure,
 CVA reduction (+ the collective).  The LSM pre-simulation (131,072 paths per GPU) runs once before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--paths P] [--scaling weak|strong]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--paths P] [--scaling weak|strong] [--dump-outputs DIR]
 
 `value` is the figure of --scaling (default weak: P paths PER GPU, the per-GPU work is fixed as N grows).  The metric is quoted on
 1 M paths IN TOTAL, so the same line also carries `strong`: the same K steps timed on 1,048,576 paths split over the N GPUs
 (131,072 per GPU at N = 8), and `sustained`: a second timed region of >= 1 s of passes (K steps of 1 ms are 20 ms of work).
+
+--dump-outputs DIR: after the run, rank 0 writes the results of the LAST step of the K timed steps as a caller of the pass
+receives them (SimulationResults.results): one float64 array [evaluations][value, mc_error] per netting set and metric,
+DIR/<netting set>_<metric>.npy (here DIR/irs_cva_cp.npy, shape [1][2]).  Seeds and inputs are fixed, so two builds run with the same
+arguments can be compared array for array.
 
 --gpus N > 1 without a torch.distributed environment: this process starts N ranks itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>`) BEFORE
@@ -22,6 +27,7 @@ import hashlib
 import json
 import math
 import os
+import re
 import socket
 import subprocess
 import sys
@@ -99,6 +105,21 @@ def cpu_baseline(target_seconds=12.0):
     return obj, (n, n_pre, cva)
 
 
+def dump_outputs(sc, res, out_dir):
+    """write the nested metric results `res` of one pass of controller `sc` as DIR/<netting set>_<metric>.npy (float64
+    [evaluations][value, mc_error]), named as run_simulation() names them; returns the file names"""
+    import numpy as np
+    packed = sc._package(res, [], [])
+    os.makedirs(out_dir, exist_ok=True)
+    files = []
+    for ns_i, ns_name in enumerate(packed.netting_set_names):
+        for m_i, m_name in enumerate(packed.metric_names):
+            fn = re.sub(r"[^\w.-]+", "_", f"{ns_name}_{m_name}").strip("_") + ".npy"
+            np.save(os.path.join(out_dir, fn), np.asarray(packed.results[ns_i][m_i], dtype=np.float64).reshape(-1, 2))
+            files.append(fn)
+    return files
+
+
 def launch_ranks(args, argv):
     """parent of an N-GPU run: never touches the GPU; starts the ranks, relays rank 0's JSON line, returns their exit code"""
     with socket.socket() as s:
@@ -131,7 +152,11 @@ def main():
     ap.add_argument("--clock-warmup", type=float, default=1.0, help="seconds of untimed passes before the W warm-up steps (power state)")
     ap.add_argument("--plan", default="auto", choices=["auto", "semi", "fused", "unfused"],
                     help="main-pass execution plan: fused = one launch; semi = K1 + one book/metric kernel; unfused = K1,K2,K4")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<netting set>_<metric>.npy (float64 [evaluations][value, mc_error])")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -375,6 +400,8 @@ def main():
         }
         if counters_note:
             out["counters_note"] = counters_note
+        if args.dump_outputs:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dump_outputs(sc, res, args.dump_outputs)}
         if not args.no_cpu_baseline and world == 1:
             cb, (n_s, n_pre_s, cva_cpu) = cpu_baseline()
             out["cpu_baseline"] = cb

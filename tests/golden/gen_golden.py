@@ -287,12 +287,7 @@ def gen_steps():
         out[f"he2_qe_{tag}"] = npf(res)
         out[f"he2_qe_{tag}_u"] = rec.uniforms[0]
 
-    # ModelConfig Cholesky factors (model_config.py:101-142, model.py:50-73)
-    for rho in (-0.95, 0.0, 0.5, 0.99999):
-        mc = ModelConfig([VasicekModel(0.0, 0.03, 0.05, 0.1, 0.01, asset_id="irs"),
-                          CIRPPModel(0.0, "cp", HAZARDS, 0.1, 0.01, 0.02, 1e-4)],
-                         inter_asset_correlation_matrix=np.array([rho]))
-        out[f"mc_chol_{rho}"] = npf(mc.get_cholesky(SimulationScheme.EULER, None))
+    out.update(mc_chol_factors())
     models = [BlackScholesModel(0.0, 100.0, 0.0, 0.4, asset_id=f"a{i}") for i in range(4)]
     mc = ModelConfig(models, inter_asset_correlation_matrix=np.array([[0.5]] * 6))
     out["mc4_chol_euler"] = npf(mc.get_cholesky(SimulationScheme.EULER, None))
@@ -601,6 +596,31 @@ def case_s2f_european():
     return [NettingSet(name=prod.get_name(), products=[prod])], model, RiskMetrics([PVMetric()])
 
 
+def mc_chol_factors():
+    """ModelConfig Cholesky factors of the Vasicek + CIR++ pair (model_config.py:101-142, model.py:50-73)"""
+    out = {}
+    for rho in (-0.95, 0.0, 0.5, 0.99999):
+        mc = ModelConfig([VasicekModel(0.0, 0.03, 0.05, 0.1, 0.01, asset_id="irs"),
+                          CIRPPModel(0.0, "cp", HAZARDS, 0.1, 0.01, 0.02, 1e-4)],
+                         inter_asset_correlation_matrix=np.array([rho]))
+        out[f"mc_chol_{rho}"] = npf(mc.get_cholesky(SimulationScheme.EULER, None))
+    return out
+
+
+def gen_mc_chol_nofma():
+    """the same factors from LAPACK code without FMA.  torch.linalg.cholesky's last bits depend on the code path MKL picks for
+    the host CPU: its FMA paths give the factors in steps.npz, the others differ (1 ulp at rho = -0.95, ~1e3 ulps at
+    rho = 0.99999, where 1 - rho^2 cancels), and some CPUs get no FMA path at all.  Run with MKL_CBWR=COMPATIBLE:
+        MKL_CBWR=COMPATIBLE python tests/golden/gen_golden.py only mc_chol_nofma"""
+    if os.environ.get("MKL_CBWR") != "COMPATIBLE":
+        print("mc_chol_nofma: skipped (needs MKL_CBWR=COMPATIBLE)")
+        return
+    out = mc_chol_factors()
+    path = os.path.join(OUT, "mc_chol_nofma.npz")
+    np.savez_compressed(path, **out)
+    print("mc_chol_nofma: wrote", path)
+
+
 def gen_netting_interp():
     """NettingSet collateral profile WITHOUT exact delayed indices (netting_set.py:76-107, 151-157): 'linear' and 'previous'
     interpolation of the netted exposure at t - MPoR, with and without a threshold"""
@@ -640,6 +660,7 @@ NEW_CASES = {
     "american_put_aad": lambda: (run_controller_case("american_put_aad", case_american, 2048, 1024, 1, SimulationScheme.ANALYTICAL, differentiate=True),
                                  slim_to_gradients("american_put_aad")),
     "netting_interp": gen_netting_interp,
+    "mc_chol_nofma": gen_mc_chol_nofma,
 }
 
 

@@ -115,3 +115,23 @@ def test_entry_points_plan_on_one_host_thread_and_restore_the_pool(oracle, monke
     assert torch.get_num_threads() == before
     sc.run_simulation()
     assert seen == [1] and torch.get_num_threads() == before
+
+
+def test_compat_aliases_serve_the_reference_import_paths():
+    """mcx.compat.install() puts the mcx modules under the reference's top-level import paths, so scripts that put the reference's
+    src/ on sys.path (`from controller.controller import SimulationController`) run against mcx unmodified"""
+    import importlib
+    import sys
+    import mcx.compat
+    saved = dict(sys.modules)
+    try:
+        mcx.compat.install()
+        for name in mcx.compat._MODULES:
+            assert sys.modules[name] is importlib.import_module(f"mcx.{name}"), name
+        from controller.controller import SimulationController as Aliased
+        from products.netting_set import NettingSet as AliasedNS
+        assert Aliased is SimulationController and AliasedNS is NettingSet
+    finally:
+        for k in list(sys.modules):
+            if k not in saved:
+                del sys.modules[k]
