@@ -79,9 +79,34 @@ struct FastDateHot {
 static_assert(sizeof(FastDateHot) == 144 && offsetof(FastDate, ni_c0) == sizeof(FastDateHot), "FastDateHot must mirror the head of FastDate");
 struct LeanTerm { double w, c0, c1; int32_t reg, pad; };     // w exp(c0 + c1 reg[reg]), read through scalar loads
 
+// The CVA-only date of a Vasicek + CIR++ (Euler) book, for the cva-date instantiation of kf_lean (kf_lean.hip lean_date_cva).
+// FastDateCva is what mcx_fused_create builds: the ten doubles of the date (the FastDate fields of the same names) and the offsets
+// of its regression rows in the book's coefficient table (-1: absent).  The coefficients change between runs (LSM), so the kernel
+// prologue gathers them and stages every date as one 128-byte FastDateCvaLds in LDS.  The state registers are the signature's
+// canonical layout (FDC_X_REG ...), so neither record carries any.
+struct alignas(16) FastDateCva {
+    double m_s1, m_n1, m_c0, m_b;    // S(0,t) / numeraire = m_b exp(m_c0 + m_n1 reg[FDC_NI_REG] + m_s1 reg[FDC_S_REG])
+    double c_c1, c_c0, c_a, c_b;     // S(t,t+) cond = c_a + c_b exp(c_c0 + c_c1 reg[FDC_C_REG])
+    double x_d, x_a;                 // x = x_a + x_d reg[FDC_X_REG]
+    int32_t coeff_off0, coeff_off1, pad[2];
+};
+// An absent row is a row of zeros: it adds +0.0 to the exposure, which leaves it unchanged for a finite state (the sum starts
+// at 0.0 + first row, so it is never -0.0).  A date with no effect on the CVA (no metric op, no cash consumer) is an all-zero
+// record: its increment is fma(0, 0, cva) = cva.
+struct alignas(16) FastDateCvaLds {
+    double m_s1, m_n1, m_c0, m_b, c_c1, c_c0, c_a, c_b, x_d, x_a;
+    double row0[3], row1[3];
+};
+#define FDC_HEAD 10                  // doubles of FastDateCva copied as they are, in this order
+static_assert(sizeof(FastDateCva) == 96 && offsetof(FastDateCva, coeff_off0) == FDC_HEAD * sizeof(double), "FastDateCva layout");
+static_assert(sizeof(FastDateCvaLds) == 128 && offsetof(FastDateCvaLds, row0) == FDC_HEAD * sizeof(double), "FastDateCvaLds layout");
+// canonical registers of SIG_VAS_CIR_E: Vasicek (r, log B) in slot 0, CIR++ (lambda, integral of lambda) in slot 1
+enum { FDC_X_REG = 0, FDC_NI_REG = 1, FDC_C_REG = 2, FDC_S_REG = 3 };
+
 struct FusedArgs {
     K1Args k1;
     const FastDate* __restrict__ fast;        // [n_dates]
+    const FastDateCva* __restrict__ cva_dates;    // [n_dates] or nullptr: the book runs the cva-date kernel (kf_lean.hip)
     const LeanTerm* __restrict__ lterms;      // exponential terms of the exercise values (FastDate::ex_term_off)
     const double* __restrict__ vcoef;         // coefficients of the exercise-value polynomials (FastDate::ex_p_off), one spare block at the end
     const unsigned char* __restrict__ prog;   // per-date program chunks (header | events | terms | metric ops)
@@ -170,5 +195,6 @@ __device__ __forceinline__ double f_regsel(int r, const double (&reg)[NREG])    
 
 // kf_lean.hip: launches the straight-line one-launch kernel for a book whose every date has a FastDate record; returns the
 // grid size (= number of per-block partial records written to a.partials), or -1 when (slots, z) has no instantiation;
-// simulate = false: the date programs run on the paths tensor a.k1.paths (the evaluation pass of mcx_fused_eval_paths)
+// simulate = false: the date programs run on the paths tensor a.k1.paths (the evaluation pass of mcx_fused_eval_paths);
+// a.cva_dates != nullptr (simulating, no injected draws, no path / cashflow / exposure output): the cva-date kernel
 int mcx_launch_kf_lean(const FusedArgs& a, const mcx_sim_desc& sd, int n_cu, bool inject, bool simulate, hipStream_t s);

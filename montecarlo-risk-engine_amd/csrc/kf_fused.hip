@@ -406,6 +406,7 @@ struct mcx_fused {
     int32_t* d_date_row;
     int chunk_cap, npf;
     int lean;                  // every date has a FastDate record kf_lean.hip can run (valid != 0)
+    FastDateCva* d_cva;        // [n_dates] when every date runs in the cva-date kernel of kf_lean.hip, else nullptr
     LeanTerm* d_lterms;
     double* d_vcoef;           // this object's copy of the exercise-value polynomial coefficients (the book may rebuild its own)
     int32_t rec_pv[MCX_FUSED_MAX_NS], rec_cva[MCX_FUSED_MAX_NS];
@@ -456,7 +457,7 @@ extern "C" void mcx_fused_destroy(mcx_fused* f)
 {
     if (!f) return;
     fused_timing_off(f);
-    hipFree(f->d_lterms); hipFree(f->d_vcoef); hipFree(f->d_prog); hipFree(f->d_fast); hipFree(f->d_date_off); hipFree(f->d_date_row); hipFree(f->d_partials); hipFree(f->d_out);
+    hipFree(f->d_lterms); hipFree(f->d_vcoef); hipFree(f->d_cva); hipFree(f->d_prog); hipFree(f->d_fast); hipFree(f->d_date_off); hipFree(f->d_date_row); hipFree(f->d_partials); hipFree(f->d_out);
     delete f;
 }
 
@@ -739,6 +740,26 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
     for (int q = 0; q < sd.n_slots; ++q)
         if (sd.slots[q].kind == MCX_MODEL_CIRPP && !(sd.init_state[sd.slots[q].state_off] > 0.0)) lean = false;
     f->lean = lean ? 1 : 0;
+    // the cva-date kernel of kf_lean.hip: a Vasicek + CIR++ (Euler) CVA book without a PV record whose every date either is the merged
+    // CVA increment of lean_date (regression exposure of n_basis = 3, no threshold, no EPE / ENE record, no exercise, a conditional
+    // survival that depends on the state) on the signature's canonical registers, or has no effect on the CVA
+    std::vector<FastDateCva> cva_dates(T);
+    bool cva_only = lean && mcx_sim_signature(sd) == SIG_VAS_CIR_E && f->rec_pv[0] < 0 && f->rec_cva[0] >= 0 && book->n_basis == 3;
+    for (int t = 0; t < T && cva_only; ++t) {
+        const FastDate& fd = fast[t];
+        FastDateCva& c = cva_dates[t];
+        memset(&c, 0, sizeof(c));
+        c.coeff_off0 = c.coeff_off1 = -1;
+        if ((fd.flags & (64 | 128 | 256)) == 64) {
+            cva_only = fd.c_b != 0.0 && fd.s_reg == FDC_S_REG && fd.ni_reg == FDC_NI_REG && fd.c_reg == FDC_C_REG && fd.x_reg == FDC_X_REG;
+            c.m_s1 = fd.m_s1; c.m_n1 = fd.m_n1; c.m_c0 = fd.m_c0; c.m_b = fd.m_b;
+            c.c_c1 = fd.c_c1; c.c_c0 = fd.c_c0; c.c_a = fd.c_a; c.c_b = fd.c_b;
+            c.x_d = fd.x_d; c.x_a = fd.x_a;
+            if (fd.flags & 2) { c.coeff_off0 = fd.coeff_off0; c.coeff_off1 = fd.coeff_off1; }
+        } else if (fd.flags & (32 | 128 | 256)) {
+            cva_only = false;          // a threshold, an EPE / ENE record or an exercise: the general program
+        }
+    }
     if ((size_t)4 * f->chunk_cap + sizeof(double) * 9 * (size_t)n_rec > 60 * 1024) {
         delete f;
         MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: a date's event program (%d B) exceeds the per-wave LDS slot budget", max_chunk);
@@ -758,6 +779,7 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
     f->partial_bytes = sizeof(double) * 4 * (size_t)n_rec * 2048;
     hipError_t e = up((void**)&f->d_prog, prog.data(), prog.size());
     if (e == hipSuccess) e = up((void**)&f->d_fast, fast.data(), sizeof(FastDate) * fast.size());
+    if (e == hipSuccess && cva_only) e = up((void**)&f->d_cva, cva_dates.data(), sizeof(FastDateCva) * cva_dates.size());
     if (e == hipSuccess) e = up((void**)&f->d_lterms, lterms.data(), sizeof(LeanTerm) * lterms.size());
     if (e == hipSuccess) e = up((void**)&f->d_vcoef, vcoef.data(), sizeof(double) * vcoef.size());
     if (e == hipSuccess) e = up((void**)&f->d_date_off, date_off.data(), sizeof(int32_t) * date_off.size());
@@ -792,6 +814,8 @@ static int fused_run_impl(mcx_handle* h, const mcx_fused* f, bool simulate, uint
     FusedArgs a;
     memset(&a, 0, sizeof(a));
     mcx_fill_k1_args(f->sim, seed, path_offset, n_paths, ld > 0 ? ld : n_paths, d_paths, d_inject_z, d_inject_u, &a.k1);
+    // the cva-date kernel computes the CVA records alone: no stored paths, cashflows or exposures
+    a.cva_dates = (simulate && !d_inject_z && !d_paths && !d_cfs && !d_expo) ? f->d_cva : nullptr;
     a.prog = f->d_prog; a.fast = f->d_fast; a.lterms = f->d_lterms; a.vcoef = f->d_vcoef; a.date_off = f->d_date_off; a.chunk_cap = f->chunk_cap;
     a.date_row = f->d_date_row; a.coeffs = f->book->d_coeffs; a.cfs = d_cfs; a.expo = d_expo; a.partials = f->d_partials;
     a.ld_out = ld_out; a.n_dates = f->n_dates; a.n_basis = f->book->n_basis; a.n_ns = f->n_ns; a.n_rec = f->n_rec;

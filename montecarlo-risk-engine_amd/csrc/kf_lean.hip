@@ -334,15 +334,48 @@ __device__ __forceinline__ void lean_date(int t, const int64_t (&i)[PPL], const 
     }
 }
 
+// The CVA-only date of the cva-date instantiation (DK = 1): a Vasicek + CIR++ book whose every date is the merged CVA block
+// above or has no effect (FastDateCva, kf_common.h).  The record comes from LDS (staged once per block by the kernel
+// prologue) as uniform-address wide reads, so no SGPR is held across the sub-step runs and nothing waits on a chain of scalar
+// loads; no flag is decoded; the state registers are compile-time indices (no M0-relative moves); the four exponentials of
+// the lane go out as one round of table reads.  Same arithmetic, in the same order, as the merged CVA block of lean_date.
+template <int NSLOT, int PPL>
+__device__ __forceinline__ void lean_date_cva(const FastDateCvaLds* __restrict__ rp, const double (&reg)[PPL][2 * NSLOT], double (&cva)[PPL],
+                                              const double* __restrict__ etab)
+{
+    const mcx_expq_coef ec = mcx_expq_load(mcx_region_zero());
+    const FastDateCvaLds r = *rp;
+    double xe[2 * PPL], ev[2 * PPL];
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) {
+        xe[2 * q] = fma(r.m_s1, reg[q][FDC_S_REG], fma(r.m_n1, reg[q][FDC_NI_REG], r.m_c0));
+        xe[2 * q + 1] = fma(r.c_c1, reg[q][FDC_C_REG], r.c_c0);
+    }
+    mcx_exp_tab_n<2 * PPL>(xe, ev, etab, ec);
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) {
+        const double x = fma(r.x_d, reg[q][FDC_X_REG], r.x_a);
+        double p = 0.0;
+        p += fma(fma(r.row0[2], x, r.row0[1]), x, r.row0[0]);
+        p += fma(fma(r.row1[2], x, r.row1[1]), x, r.row1[0]);
+        const double w = r.m_b * ev[2 * q];
+        const double cs = fma(r.c_b, ev[2 * q + 1], r.c_a);
+        cva[q] = fma(fmax(p, 0.0), w * (1.0 - cs), cva[q]);
+    }
+}
+
 #define MCX_LEAN_WAVES 4
 // SIMULATE = false: the same date programs on a paths tensor produced earlier by K1 (k1.paths is then the INPUT
 // [date][state][path]): one streaming pass, the next date's state columns in flight while this date's program runs
 // (Measured and dropped: drawing the normals of 2-5 sub-steps AHEAD as independent staged chains, for small path counts — the draws
 // depend on the counter (path, step) only.  No gain at one or two waves per SIMD: what a thin launch waits for is scalar work, see
 // launch_lean.)
-template <int NSLOT, int NZ, bool INJECT, int SIG, int PPL, bool SIMULATE>
+// DK (date kind) = 1: every date through lean_date_cva from the FastDateCvaLds records that follow the record area in the
+// dynamic LDS (launch_lean_shape: a.cva_dates != nullptr)
+template <int NSLOT, int NZ, bool INJECT, int SIG, int PPL, bool SIMULATE, int DK = 0>
 __global__ __launch_bounds__(MCX_BLOCK, MCX_LEAN_WAVES) void kf_lean(const FusedArgs)      // read through kargs_region(), never by name
 {
+    static_assert(DK == 0 || (SIG == SIG_VAS_CIR_E && SIMULATE && !INJECT), "the cva-date kernel simulates the Vasicek + CIR++ signature");
     constexpr int NREG = 2 * NSLOT;
     constexpr int TILE = MCX_BLOCK * PPL;
     extern __shared__ double lds[];
@@ -350,6 +383,24 @@ __global__ __launch_bounds__(MCX_BLOCK, MCX_LEAN_WAVES) void kf_lean(const Fused
     const int n_rec = a0.n_rec;
     const int64_t n = a0.k1.n;
     for (int q = threadIdx.x; q < 9 * n_rec; q += MCX_BLOCK) lds[q] = 0.0;
+    FastDateCvaLds* const dlds = (FastDateCvaLds*)(lds + ((9 * n_rec + 1) & ~1));      // (DK = 1) 16-byte aligned
+    if constexpr (DK == 1) {
+        // every date's record, its regression rows gathered from the coefficient table of this run
+        const FastDateCva* __restrict__ dc = a0.cva_dates;
+        const double* __restrict__ cf = a0.coeffs;
+        const int n_dates = a0.n_dates;
+        for (int q = threadIdx.x; q < 16 * n_dates; q += MCX_BLOCK) {
+            const int t = q >> 4, e = q & 15;
+            double v;
+            if (e < FDC_HEAD) {
+                v = ((const double*)(dc + t))[e];
+            } else {
+                const int off = e < FDC_HEAD + 3 ? dc[t].coeff_off0 : dc[t].coeff_off1;
+                v = off >= 0 ? cf[off + (e - FDC_HEAD) % 3] : 0.0;
+            }
+            ((double*)dlds)[q] = v;
+        }
+    }
     // 1024-entry Box-Muller tables (32 KiB of LDS) where the sub-steps dominate and four blocks per CU still fit: the two-factor
     // rates / credit signature; 128 entries elsewhere (books with hundreds of per-date records need the LDS for those)
     constexpr int BMB = SIG == SIG_VAS_CIR_E ? 10 : 7;
@@ -439,7 +490,10 @@ __global__ __launch_bounds__(MCX_BLOCK, MCX_LEAN_WAVES) void kf_lean(const Fused
                     ++step;
                 }
             }
-            if (st >= 0) lean_date<NSLOT, SIG, PPL, true>(st, i, live, first_tile, lds, reg, cfs, cva, est, etab);
+            if (st >= 0) {
+                if constexpr (DK == 1) lean_date_cva<NSLOT, PPL>(dlds + st, reg, cva, etab);
+                else lean_date<NSLOT, SIG, PPL, true>(st, i, live, first_tile, lds, reg, cfs, cva, est, etab);
+            }
         }
         } else {
             auto load_row = [&](int t, double (&dst)[PPL][NREG]) {
@@ -503,16 +557,17 @@ int launch_lean_shape(const FusedArgs& a, int n_cu, bool inject, bool simulate, 
 {
     const int64_t tiles = (a.k1.n + MCX_BLOCK * PPL - 1) / (MCX_BLOCK * PPL);
     const size_t lds = sizeof(double) * (size_t)((9 * a.n_rec + 1) & ~1);
+    const size_t lds_cva = lds + sizeof(FastDateCvaLds) * (size_t)a.n_dates;
     // blocks that are really co-resident: __launch_bounds__(256, 4) guarantees the registers of 4 blocks per CU, but a book with
     // hundreds of records (one per metric date) adds dynamic LDS to the 34 KiB of tables and may leave room for 3 only; a grid
     // sized for 4 would then run its last quarter as a tail at a third of the occupancy
-    auto residency = [&](auto kernel) {
+    auto residency = [&](auto kernel, size_t bytes) {
         thread_local std::map<std::pair<const void*, size_t>, int> cache;      // (the query costs microseconds: once per kernel and size)
-        const auto key = std::make_pair((const void*)kernel, lds);
+        const auto key = std::make_pair((const void*)kernel, bytes);
         auto it = cache.find(key);
         if (it == cache.end()) {
             int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, MCX_BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, MCX_BLOCK, bytes) != hipSuccess || per_cu < 1) per_cu = 1;
             it = cache.emplace(key, per_cu < MCX_LEAN_WAVES ? per_cu : MCX_LEAN_WAVES).first;
         }
         return (int64_t)it->second * n_cu;
@@ -525,15 +580,25 @@ int launch_lean_shape(const FusedArgs& a, int n_cu, bool inject, bool simulate, 
     int grid;
     if (!simulate) {
         auto kern = kf_lean<NSLOT, NZ, false, SIG, PPL, false>;
-        grid = sized(residency(kern));
+        grid = sized(residency(kern, lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(MCX_BLOCK), lds, s, a);
     } else if (inject) {
         auto kern = kf_lean<NSLOT, NZ, true, SIG, PPL, true>;
-        grid = sized(residency(kern));
+        grid = sized(residency(kern, lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(MCX_BLOCK), lds, s, a);
     } else {
         auto kern = kf_lean<NSLOT, NZ, false, SIG, PPL, true>;
-        grid = sized(residency(kern));
+        const int64_t resident = residency(kern, lds);
+        if constexpr (SIG == SIG_VAS_CIR_E) {
+            // the cva-date kernel, unless its date records in LDS (128 B per date) cost a block per CU
+            auto kern_cva = kf_lean<NSLOT, NZ, false, SIG, PPL, true, 1>;
+            if (a.cva_dates && residency(kern_cva, lds_cva) >= resident) {
+                grid = sized(resident);
+                hipLaunchKernelGGL(kern_cva, dim3(grid), dim3(MCX_BLOCK), lds_cva, s, a);
+                return grid;
+            }
+        }
+        grid = sized(resident);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(MCX_BLOCK), lds, s, a);
     }
     return grid;

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Static VALU instruction mix of the sub-step loop of the bench kernel (kf_lean<2,2,false,SIG_VAS_CIR_E,2>): compiles
+"""Static VALU instruction mix of the sub-step loop of the bench kernel (kf_lean<2,2,false,SIG_VAS_CIR_E,2,true,1>, the cva-date
+instantiation): compiles
 csrc/kf_lean.hip to gfx950 assembly and counts the instruction classes between the innermost loop header that contains the
 Philox multiplies and its back-branch.  Output (JSON on stdout): per PATH and sub-step (the loop body handles 2 paths per lane).
 The loop holds one rarely taken side block per path (the guarded root of a uniform that rounds to 1, mcx_device.h pair_from_words);
@@ -25,7 +26,7 @@ def main():
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=on", "-DMCX_LEAN_ONE_SIG",
                                "--cuda-device-only", "-S", "kf_lean.hip", "-o", out], cwd=CS, stderr=subprocess.DEVNULL)
         text = open(out).read()
-    m = re.search(r"^(_ZN\S*kf_leanILi2ELi2ELb0ELi1ELi2ELb1E[^\s:]*):[^\n]*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S | re.M)
+    m = re.search(r"^(_ZN\S*kf_leanILi2ELi2ELb0ELi1ELi2ELb1ELi1E[^\s:]*):[^\n]*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S | re.M)
     lines = m.group(2).split("\n")
     # innermost loop with v_mad_u64_u32: label .LBBx_y ... s_cbranch* .LBBx_y
     best = None
