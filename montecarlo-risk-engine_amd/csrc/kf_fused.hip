@@ -20,13 +20,13 @@
 namespace {
 
 // straight-line evaluation of a FastDate (see the struct); returns false when the date must be interpreted
-template <int NSLOT, int SIG, int NNS, bool STORE, bool ALL_FAST>
+template <int NSLOT, int SIG, int NNS, bool STORE>
 __device__ __forceinline__ bool kf_fast_date(const FusedArgs& a, int t, int64_t i, bool live, bool first_tile, double* __restrict__ lds,
                                              const double (&reg)[2 * NSLOT], double (&cfs)[NNS], double (&cva)[NNS])
 {
     constexpr int NREG = 2 * NSLOT;
     if (NNS != 1) return false;
-    if (!ALL_FAST && ldk(&a.fast[t].valid) != 1) return false;
+    if (ldk(&a.fast[t].valid) != 1) return false;
     const FastDate* __restrict__ fp = a.fast + t;                // every field is a scalar load at its point of use
 #define FD(x) ldk(&fp->x)
     const K1Args& k = a.k1;
@@ -66,8 +66,8 @@ __device__ __forceinline__ bool kf_fast_date(const FusedArgs& a, int t, int64_t 
         const double u = dev_thr(e, FD(thr));
         if (flags & 8) {
             const int rp = FD(rec_profile);
-            f_record(fmax(u, 0.0), live, rp, a.n_rec, first_tile, lds);
-            f_record(fmin(u, 0.0), live, rp + 1, a.n_rec, first_tile, lds);
+            lean_record<1>({fmax(u, 0.0)}, {live}, rp, a.n_rec, first_tile, lds);
+            lean_record<1>({fmin(u, 0.0)}, {live}, rp + 1, a.n_rec, first_tile, lds);
         }
         if (flags & 4) {
             const double sp = FD(s_b) * mcx_exp(fma(FD(s_c1), f_regsel<NREG>(FD(s_reg), reg), FD(s_c0)));
@@ -185,8 +185,8 @@ __device__ __forceinline__ void kf_on_date(const FusedArgs& a, int t, int64_t i,
         for (int w = 1; w < NNS; ++w) e = (mo.ns == w) ? e_ns[w] : e;
         const double u = dev_thr(e, mo.threshold);
         if (mo.rec_profile >= 0) {
-            f_record(fmax(u, 0.0), live, mo.rec_profile, n_rec, first_tile, lds);
-            f_record(fmin(u, 0.0), live, mo.rec_profile + 1, n_rec, first_tile, lds);
+            lean_record<1>({fmax(u, 0.0)}, {live}, mo.rec_profile, n_rec, first_tile, lds);
+            lean_record<1>({fmin(u, 0.0)}, {live}, mo.rec_profile + 1, n_rec, first_tile, lds);
         }
         if (mo.has_cva) {
             const double sp = f_atom<NREG>(mo.surv, reg);
@@ -203,7 +203,8 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // NNS = compile-time bound on netting sets (1 or MCX_FUSED_MAX_NS), NST = bound on exercise products (0 -> none).
 // NPF = 1 KiB pieces of the NEXT date's program chunk each wave prefetches into VGPRs (one coalesced global_load_dwordx4
 // per piece, issued before the sub-steps that lead to that date, written to the wave's LDS slot just before use: the HBM/L2
-// latency hides under ~5 sub-steps of RNG + SDE work).  NPF = 0: chunks larger than 2 KiB are copied at use.
+// latency hides under ~5 sub-steps of RNG + SDE work).  NPF = 0: chunks larger than 2 KiB are copied at use, or no date is
+// interpreted.
 // SIMULATE = false: the same event/metric program runs on a paths tensor produced earlier by K1 (`k.paths` is then the
 // INPUT [date][state][path]): one pass over the paths replaces K2 + K4 and writes no exposure matrix unless asked to.
 template <int NSLOT, int NZ, bool INJECT, int SIG, int NNS, int NST, int NPF, bool SIMULATE>
@@ -212,7 +213,6 @@ __device__ __forceinline__ void kf_body(const FusedArgs& a)
     constexpr int NREG = 2 * NSLOT;
     constexpr int NSTA = NST > 0 ? NST : 1;
     constexpr int NPFA = NPF > 0 ? NPF : 1;
-    constexpr bool FAST_ONLY = NPF < 0;          // every date has a FastDate record: no interpreter, no program slots
     extern __shared__ double lds[];
     const K1Args& k = a.k1;
     const int n_rec = a.n_rec;
@@ -266,17 +266,13 @@ __device__ __forceinline__ void kf_body(const FusedArgs& a)
 
         auto on_date = [&](int t, auto store) {
             constexpr bool ST = decltype(store)::value;
-            if (FAST_ONLY) {
-                kf_fast_date<NSLOT, SIG, NNS, ST, true>(a, t, i, live, first_tile, lds, reg, cfs, cva);
-            } else {
-                const bool fast = kf_fast_date<NSLOT, SIG, NNS, ST, false>(a, t, i, live, first_tile, lds, reg, cfs, cva);
-                if (!fast) stage(t);
-                prefetch(t + 1);
-                if (!fast) kf_on_date<NSLOT, SIG, NNS, NSTA, ST>(a, t, i, live, first_tile, lds, slot, reg, cfs, cva, est);
-            }
+            const bool fast = kf_fast_date<NSLOT, SIG, NNS, ST>(a, t, i, live, first_tile, lds, reg, cfs, cva);
+            if (!fast) stage(t);
+            prefetch(t + 1);
+            if (!fast) kf_on_date<NSLOT, SIG, NNS, NSTA, ST>(a, t, i, live, first_tile, lds, slot, reg, cfs, cva, est);
         };
         int next_t = 0;                                    // timeline dates are visited in increasing order, each once
-        if (!FAST_ONLY) prefetch(0);
+        prefetch(0);
         if (SIMULATE) {
             for (int t = 0; t < k.n_initial_store; ++t) {
                 on_date(t, std::integral_constant<bool, true>());
@@ -329,8 +325,8 @@ __device__ __forceinline__ void kf_body(const FusedArgs& a)
 #pragma unroll
             for (int q = 1; q < NNS; ++q) { cv = (w == q) ? cfs[q] : cv; cc = (w == q) ? cva[q] : cc; }
             if (a.cfs && live) a.cfs[(int64_t)w * a.ld_out + i] = cv;
-            if (a.rec_pv[w] >= 0) f_record(cv, live, a.rec_pv[w], n_rec, first_tile, lds);
-            if (a.rec_cva[w] >= 0) f_record(cc * a.lgd[w], live, a.rec_cva[w], n_rec, first_tile, lds);
+            if (a.rec_pv[w] >= 0) lean_record<1>({cv}, {live}, a.rec_pv[w], n_rec, first_tile, lds);
+            if (a.rec_cva[w] >= 0) lean_record<1>({cc * a.lgd[w]}, {live}, a.rec_cva[w], n_rec, first_tile, lds);
         }
     }
     __syncthreads();
@@ -730,11 +726,11 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
     date_off[T] = (int32_t)prog.size();
     if (bs_exposure) { delete f; MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: analytic Black-Scholes exposures are evaluated by the book kernel (K2)"); }
     // LDS budget: 4 wave slots + the record area must fit comfortably (several blocks per CU)
-    bool all_fast = d->n_netting_sets == 1 && n_stateful == 0, lean = d->n_netting_sets == 1 && n_stateful <= 1;
-    for (int t = 0; t < T; ++t) { all_fast = all_fast && fast[t].valid == 1; lean = lean && fast[t].valid != 0; }
-    f->npf = max_chunk <= 1024 ? 1 : (max_chunk <= 2048 ? 2 : 0);
+    bool lean = d->n_netting_sets == 1 && n_stateful <= 1;
+    for (int t = 0; t < T; ++t) lean = lean && fast[t].valid != 0;
+    // no interpreted date at all: no program slots (NPF = 0, chunk_cap = 0)
+    f->npf = max_chunk == 0 ? 0 : (max_chunk <= 1024 ? 1 : (max_chunk <= 2048 ? 2 : 0));
     f->chunk_cap = f->npf > 0 ? f->npf * 1024 : ((max_chunk + 255) & ~255);
-    if (all_fast) { f->npf = -1; f->chunk_cap = 0; }      // no interpreted date at all: the straight-line instantiations
     // the straight-line kernel skips the zero test under the CIR++ diffusion root: it needs a positive initial intensity (the
     // reference asserts y0 > 0, cirpp.py:40; the state is floored at 1e-12 after every step); other starts run the interpreter
     for (int q = 0; q < sd.n_slots; ++q)

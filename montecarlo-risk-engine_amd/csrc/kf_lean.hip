@@ -28,314 +28,8 @@
 
 namespace {
 
-#define FD(x) ldk(&fp->x)
-
-// the kernel arguments as seen from one code region: the kernarg segment (explicit arguments start at offset 0) behind a
-// region zero
-typedef const MCX_KONST FusedArgs KArgs;
-__device__ __forceinline__ KArgs& kargs_region(int z)
-{
-    return *(KArgs*)((const MCX_KONST char*)__builtin_amdgcn_kernarg_segment_ptr() + z);
-}
-
-// polynomial in the raw explanatory variable with wave-uniform coefficients (scalar loads); K == 3 is the default
-// PolyomialRegression(degree=2) of the reference (controller.py:35)
-template <int PPL>
-__device__ __forceinline__ void lean_poly_add(const double* __restrict__ c, int K, const double (&x)[PPL], double (&p)[PPL])
-{
-    if (K == 3) {
-        const double c0 = ldk(c), c1 = ldk(c + 1), c2 = ldk(c + 2);
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) p[q] += fma(fma(c2, x[q], c1), x[q], c0);
-    } else {
-        double v[PPL];
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) v[q] = 0.0;
-#pragma unroll 1
-        for (int k = K - 1; k >= 0; --k) {
-            const double ck = ldk(c + k);
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) v[q] = fma(v[q], x[q], ck);
-        }
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) p[q] += v[q];
-    }
-}
-
-// LDS record area: shift[n_rec] | acc[4 waves][n_rec][2]   (layout of f_record, kf_common.h)
-template <int PPL>
-__device__ __forceinline__ void lean_record(const double (&v)[PPL], const bool (&live)[PPL], int rec, int n_rec, bool first_tile,
-                                            double* __restrict__ lds)
-{
-    if (first_tile) {                      // block-uniform: the first path the block sees fixes the record's shift
-        __syncthreads();
-        if (threadIdx.x == 0) lds[rec] = v[0];
-        __syncthreads();
-    }
-    const double c = lds[rec];
-    double d1 = 0.0, d2 = 0.0;
-#pragma unroll
-    for (int q = 0; q < PPL; ++q) {
-        const double d = live[q] ? v[q] - c : 0.0;
-        d1 += d;
-        d2 = fma(d, d, d2);
-    }
-    const double s1 = wave_sum(d1), s2 = wave_sum(d2);
-    if ((threadIdx.x & 63) == 0) {
-        double* acc = lds + n_rec + ((threadIdx.x >> 6) * n_rec + rec) * 2;
-        acc[0] += s1;
-        acc[1] += s2;
-    }
-}
-
-template <int NSLOT, int SIG, int PPL, bool STORE>
-__device__ __forceinline__ void lean_date(int t, const int64_t (&i)[PPL], const bool (&live)[PPL], bool first_tile,
-                                          double* __restrict__ lds, const double (&reg)[PPL][2 * NSLOT], double (&cfs)[PPL], double (&cva)[PPL],
-                                          int (&est)[PPL], const double* __restrict__ etab)
-{
-    // (state registers are indexed by wave-uniform record fields: M0-relative VGPR reads; mcx_fused_create binds an absent
-    // reference to register 0 with a zero coefficient, so no range test is needed)
-    const int zd = mcx_region_zero();                  // arguments, date record and exp coefficients: live in this block only
-    KArgs& a = kargs_region(zd);
-    const FastDate* __restrict__ fp = a.fast + t;
-    const auto& k = a.k1;
-    const mcx_expq_coef ec = mcx_expq_load(zd);       // exponentials: table of 2^(j/128) in LDS + degree-5 remainder
-    // The CVA-only date (the config-3 shape: regression exposure, merged discount x survival factor, conditional default
-    // probability — nothing stored, no cashflow consumer) in TWO rounds of scalar loads instead of one per branch of the general
-    // program below: (1) the head of the record + the arguments, (2) the coefficient rows; and one round of LDS reads for its
-    // two exponentials.  The waits of ~12 dependent scalar loads per date were a third of a wave's cycles at one or two waves
-    // per SIMD.  Same arithmetic as the general path.
-    // (the simulating kernel with two paths per lane at four waves per SIMD: measured slower — 52 SGPR spills around the date — than
-    //  the general program below; the streaming kernel has no generator state to keep and is bound by the scalar unit, which the
-    //  four SIMDs of a CU share: ~500 scalar instructions per date and wave of the general program cap it at ~4.3 TB/s)
-    if ((PPL == 1 || !STORE) && !(STORE && k.paths)) {
-        const FastDateHot hot = ldk_struct((const FastDateHot*)fp);
-        const bool pure_cva = (hot.flags & (64 | 128 | 256 | 2)) == (64 | 2) && !((hot.flags & 1) && (a.cfs != nullptr || a.rec_pv[0] >= 0)) &&
-                              a.expo == nullptr && a.n_basis == 3 && hot.c_b != 0.0;
-        if (pure_cva) {
-            const double* __restrict__ cf = a.coeffs;
-            double c0[3] = {0.0, 0.0, 0.0}, c1[3] = {0.0, 0.0, 0.0};
-            if (hot.coeff_off0 >= 0) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) c0[j] = ldk(cf + hot.coeff_off0 + j);
-            }
-            if (hot.coeff_off1 >= 0) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) c1[j] = ldk(cf + hot.coeff_off1 + j);
-            }
-            double xe[2 * PPL], ev[2 * PPL], p[PPL];
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) {
-                xe[2 * q] = fma(hot.m_s1, reg[q][hot.s_reg], fma(hot.m_n1, reg[q][hot.ni_reg], hot.m_c0));
-                xe[2 * q + 1] = fma(hot.c_c1, reg[q][hot.c_reg], hot.c_c0);
-            }
-            mcx_exp_tab_n<2 * PPL>(xe, ev, etab, ec);
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) {
-                const double x = fma(hot.x_d, reg[q][hot.x_reg], hot.x_a);
-                p[q] = 0.0;
-                if (hot.coeff_off0 >= 0) p[q] += fma(fma(c0[2], x, c0[1]), x, c0[0]);
-                if (hot.coeff_off1 >= 0) p[q] += fma(fma(c1[2], x, c1[1]), x, c1[0]);
-                const double w = hot.m_b * ev[2 * q];
-                const double cs = fma(hot.c_b, ev[2 * q + 1], hot.c_a);
-                cva[q] = fma(fmax(p[q], 0.0), w * (1.0 - cs), cva[q]);
-            }
-            return;
-        }
-    }
-    if (STORE && k.paths) {
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) if (live[q]) sim_store_state<NSLOT, SIG>(k, t, i[q], reg[q]);
-    }
-    const int flags = FD(flags);
-    // cashflows feed the PV record / the cashflow output only; a CVA / exposure-profile run skips them
-    const bool want_cash = (flags & 1) && (a.cfs != nullptr || a.rec_pv[0] >= 0);
-    // CVA-only date without threshold: relu(p / N) S (1 - Sc) = relu(p) (S / N) (1 - Sc), one exponential for S / N
-    const bool merged = (flags & 64) && !(flags & 128) && !want_cash && a.expo == nullptr;
-    double inv[PPL];
-    if (!merged) {
-        if (flags & 16) {
-            const double c = FD(ni_c0);
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) inv[q] = c;
-        } else {
-            const double c0 = FD(ni_c0), c1 = FD(ni_c1);
-            const int r = FD(ni_reg);
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) inv[q] = mcx_exp_tab(fma(c1, reg[q][r], c0), etab, ec);
-        }
-    }
-    if (want_cash) {
-        const double k0 = FD(k0), k1 = FD(k1);
-        const int lr = FD(lin_reg), n_exp = FD(n_exp);
-        double val[PPL];
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) val[q] = fma(k1, reg[q][lr], k0);
-#pragma unroll 1
-        for (int j = 0; j < n_exp; ++j) {
-            const double w = FD(t_w[j]), c0 = FD(t_c0[j]), c1 = FD(t_c1[j]);
-            const int r = FD(t_reg[j]);
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) val[q] = fma(w, mcx_exp_tab(fma(c1, reg[q][r], c0), etab, ec), val[q]);
-        }
-        if (flags & 512) {                                 // plain option payoff (european_option.py:45-68)
-            const double strike = FD(op_strike), sign = FD(op_sign);
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) val[q] = fmax(sign * (val[q] - strike), 0.0);
-        }
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) cfs[q] = fma(val[q], inv[q], cfs[q]);
-    }
-    if (flags & 128) {
-        // exercise event of the two-state product (bermudan_option.py:93-131): exercise iff the immediate value exceeds the
-        // regression continuation value and a right is left; the (up to ~64) exponential terms of the immediate value come
-        // through scalar loads, one 32-byte record per term, and serve both paths of the lane
-        const double strike = FD(ex_strike), sign = FD(ex_sign);
-        double val[PPL];
-        // the whole value as ONE verified polynomial of the state variable (mcx_vpoly.hip: ~20 multiply-adds for both paths of the
-        // lane instead of ~15 VALU per term and path); a wave that holds a path outside the verified range runs the terms
-        bool collapsed = false;
-        if (flags & 1024) {
-            const double lo = FD(ex_p_lo), hi = FD(ex_p_hi);
-            const int pr = FD(ex_p_reg);
-            bool in = true;
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) in = in && reg[q][pr] >= lo && reg[q][pr] <= hi;
-            if (__all(in)) {
-                const double ms = FD(ex_p_ms), ih = FD(ex_p_ih);
-                const int nb = FD(ex_p_blk);
-                const VPolyBlk* __restrict__ blk = (const VPolyBlk*)(a.vcoef + FD(ex_p_off));
-                double tt[PPL];
-#pragma unroll
-                for (int q = 0; q < PPL; ++q) { tt[q] = fma(reg[q][pr], ih, ms); val[q] = 0.0; }
-                VPolyBlk c = ldk_struct(blk);
-#pragma unroll 1
-                for (int kb = 0; kb < nb; ++kb) {
-                    const VPolyBlk nx = ldk_struct(blk + kb + 1);
-#pragma unroll
-                    for (int j = 0; j < MCX_VPOLY_BLK; ++j)
-#pragma unroll
-                        for (int q = 0; q < PPL; ++q) val[q] = fma(val[q], tt[q], c.c[j]);
-                    c = nx;
-                }
-                collapsed = true;
-            }
-        }
-        if (!collapsed) {
-            const double k0 = FD(ex_k0), k1 = FD(ex_k1);
-            const int lr = FD(ex_lin_reg), n_t = FD(ex_n);
-            const LeanTerm* __restrict__ lt = a.lterms + FD(ex_term_off);
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) val[q] = fma(k1, reg[q][lr], k0);
-            // the next term's record is in flight while this term's two exponentials run (the table has one spare entry at its end)
-            LeanTerm tm = ldk_struct(lt);
-#pragma unroll 1
-            for (int j = 0; j < n_t; ++j) {
-                const LeanTerm nx = ldk_struct(lt + j + 1);
-#pragma unroll
-                for (int q = 0; q < PPL; ++q) val[q] = fma(tm.w, mcx_exp_tab(fma(tm.c1, reg[q][tm.reg], tm.c0), etab, ec), val[q]);
-                tm = nx;
-            }
-        }
-        const double xa = FD(ex_x_a), xd = FD(ex_x_d);
-        const int xr = FD(ex_x_reg), co = FD(ex_coeff_off);
-        double x[PPL], cont[PPL];
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) { x[q] = fma(xd, reg[q][xr], xa); cont[q] = 0.0; }
-        if (co >= 0) lean_poly_add<PPL>(a.coeffs + co + a.n_basis, a.n_basis, x, cont);      // row of state 1 (a right is left)
-        const bool want_ex_cash = a.cfs != nullptr || a.rec_pv[0] >= 0;
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) {
-            const double imm = fmax(sign * (val[q] - strike), 0.0);
-            const bool ex = (imm > cont[q]) && (est[q] > 0);
-            if (want_ex_cash) cfs[q] = ex ? fma(imm, inv[q], cfs[q]) : cfs[q];
-            est[q] = ex ? est[q] - 1 : est[q];
-        }
-    }
-    double p[PPL];
-#pragma unroll
-    for (int q = 0; q < PPL; ++q) p[q] = 0.0;
-    if (flags & 2) {
-        const double xa = FD(x_a), xd = FD(x_d);
-        const int xr = FD(x_reg), off0 = FD(coeff_off0), off1 = FD(coeff_off1);
-        double x[PPL];
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) x[q] = fma(xd, reg[q][xr], xa);
-        if (flags & 256) {
-            // exposure of the exercise product: the coefficient row of the lane's state (product.py:150-184)
-            double p0[PPL], p1[PPL];
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) { p0[q] = 0.0; p1[q] = 0.0; }
-            lean_poly_add<PPL>(a.coeffs + off0, a.n_basis, x, p0);
-            lean_poly_add<PPL>(a.coeffs + off0 + a.n_basis, a.n_basis, x, p1);
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) p[q] = est[q] > 0 ? p1[q] : p0[q];
-        } else {
-            if (off0 >= 0) lean_poly_add<PPL>(a.coeffs + off0, a.n_basis, x, p);
-            if (off1 >= 0) lean_poly_add<PPL>(a.coeffs + off1, a.n_basis, x, p);
-        }
-    }
-    // survival probability over the next interval, conditional on the credit state (cva_metric.py:66-89)
-    auto cond_surv = [&](double (&cs)[PPL]) {
-        const double ca = FD(c_a), cb = FD(c_b);
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) cs[q] = ca;
-        if (cb != 0.0) {
-            const double cc0 = FD(c_c0), cc1 = FD(c_c1);
-            const int cr = FD(c_reg);
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) cs[q] = fma(cb, mcx_exp_tab(fma(cc1, reg[q][cr], cc0), etab, ec), ca);
-        }
-    };
-    if (merged) {
-        const double mb = FD(m_b), mc0 = FD(m_c0), mn1 = FD(m_n1), ms1 = FD(m_s1);
-        const int nr = FD(ni_reg), sr = FD(s_reg);
-        double w[PPL], cs[PPL];
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) w[q] = mb * mcx_exp_tab(fma(ms1, reg[q][sr], fma(mn1, reg[q][nr], mc0)), etab, ec);
-        cond_surv(cs);
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) cva[q] = fma(fmax(p[q], 0.0), w[q] * (1.0 - cs[q]), cva[q]);
-        return;
-    }
-    double e[PPL];
-#pragma unroll
-    for (int q = 0; q < PPL; ++q) e[q] = p[q] * inv[q];
-    if (a.expo) {
-        const int row = ldk(a.date_row + t);
-        if (row >= 0) {
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) if (live[q]) a.expo[(int64_t)row * a.ld_out + i[q]] = e[q];
-        }
-    }
-    if (flags & 32) {
-        const double thr = FD(thr);
-        double u[PPL];
-#pragma unroll
-        for (int q = 0; q < PPL; ++q) u[q] = dev_thr(e[q], thr);
-        if (flags & 8) {
-            const int rp = FD(rec_profile);
-            double up[PPL], un[PPL];
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) { up[q] = fmax(u[q], 0.0); un[q] = fmin(u[q], 0.0); }
-            lean_record<PPL>(up, live, rp, a.n_rec, first_tile, lds);
-            lean_record<PPL>(un, live, rp + 1, a.n_rec, first_tile, lds);
-        }
-        if (flags & 4) {
-            const double sb = FD(s_b), sc0 = FD(s_c0), sc1 = FD(s_c1);
-            const int sr = FD(s_reg);
-            double sp[PPL], cs[PPL];
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) sp[q] = sb * mcx_exp_tab(fma(sc1, reg[q][sr], sc0), etab, ec);
-            cond_surv(cs);
-#pragma unroll
-            for (int q = 0; q < PPL; ++q) cva[q] = fma(fmax(u[q], 0.0), sp[q] * (1.0 - cs[q]), cva[q]);
-        }
-    }
-}
-
 // The CVA-only date of the cva-date instantiation (DK = 1): a Vasicek + CIR++ book whose every date is the merged CVA block
-// above or has no effect (FastDateCva, kf_common.h).  The record comes from LDS (staged once per block by the kernel
+// of lean_date (kf_common.h) or has no effect (FastDateCva, kf_common.h).  The record comes from LDS (staged once per block by the kernel
 // prologue) as uniform-address wide reads, so no SGPR is held across the sub-step runs and nothing waits on a chain of scalar
 // loads; no flag is decoded; the state registers are compile-time indices (no M0-relative moves); the four exponentials of
 // the lane go out as one round of table reads.  Same arithmetic, in the same order, as the merged CVA block of lean_date.
@@ -548,8 +242,6 @@ __global__ __launch_bounds__(MCX_BLOCK, MCX_LEAN_WAVES) void kf_lean(const Fused
         dst[0] = n_block; dst[1] = lds[r]; dst[2] = s1; dst[3] = s2;
     }
 }
-
-#undef FD
 
 // launch of one shape (paths per lane) of the kernel; returns the grid
 template <int NSLOT, int NZ, int SIG, int PPL>
