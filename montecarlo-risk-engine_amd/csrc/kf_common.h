@@ -32,13 +32,13 @@ struct FMetricOp {             // one (netting set, metric date) pair, executed 
 struct ChunkHeader { int32_t n_ev, n_mop, n_terms, bytes; };
 
 // Straight-line record of a date whose program is the common linear-book shape (one netting set; cashflows that are an
-// affine term + <= 4 exponential terms over a pure-exponential or constant numeraire; stateless polynomial exposures; an
-// optional threshold / EPE-ENE record / CVA increment).  Such a date runs ~130 instructions of branch-light code with every
-// control field in SGPRs instead of ~500 instructions of event interpretation; any other date uses the interpreter.
+// affine term + <= 4 exponential terms over a pure-exponential or constant numeraire, or a plain option payoff; polynomial
+// exposures; the exercise event of one two-state product; an optional threshold / EPE-ENE record / CVA increment).  Such a
+// date runs ~130 instructions of branch-light code with every control field in SGPRs instead of ~500 instructions of event
+// interpretation; any other date uses the interpreter.
 struct FastDate {
     // ---- hot head (FastDateHot below is a view of these 144 bytes: ONE batch of scalar loads at the top of a date) ----
-    int32_t valid, flags;            // valid: 0 interpreted, 1 straight-line in every fused kernel, 2 straight-line in kf_lean only
-                                     // (exercise event / state-dependent exposure: flags 128 / 256)
+    int32_t valid, flags;            // valid: 0 interpreted, 1 straight-line (lean_date, in kf_lean and kf_fused alike)
                                      // flags: 1 cash, 2 expo, 4 cva, 8 profile, 16 constant numeraire, 32 metric op present,
                                      // 64: the CVA increment may use the merged discount x survival factor (m_*): no threshold,
                                      //     no EPE / ENE record on this date

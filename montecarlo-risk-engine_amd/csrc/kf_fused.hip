@@ -19,78 +19,16 @@
 
 namespace {
 
-// straight-line evaluation of a FastDate (see the struct); returns false when the date must be interpreted
-template <int NSLOT, int SIG, int NNS, bool STORE>
-__device__ __forceinline__ bool kf_fast_date(const FusedArgs& a, int t, int64_t i, bool live, bool first_tile, double* __restrict__ lds,
-                                             const double (&reg)[2 * NSLOT], double (&cfs)[NNS], double (&cva)[NNS])
-{
-    constexpr int NREG = 2 * NSLOT;
-    if (NNS != 1) return false;
-    if (ldk(&a.fast[t].valid) != 1) return false;
-    const FastDate* __restrict__ fp = a.fast + t;                // every field is a scalar load at its point of use
-#define FD(x) ldk(&fp->x)
-    const K1Args& k = a.k1;
-    if (STORE && k.paths && live) sim_store_state<NSLOT, SIG>(k, t, i, reg);
-    const int flags = FD(flags);
-    const double inv = (flags & 16) ? FD(ni_c0) : mcx_exp(fma(FD(ni_c1), f_regsel<NREG>(FD(ni_reg), reg), FD(ni_c0)));
-    if (flags & 1) {
-        double val = fma(FD(k1), f_regsel<NREG>(FD(lin_reg), reg), FD(k0));
-        const int n_exp = FD(n_exp);
-#pragma unroll 1
-        for (int j = 0; j < n_exp; ++j)
-            val = fma(FD(t_w[j]), mcx_exp(fma(FD(t_c1[j]), f_regsel<NREG>(FD(t_reg[j]), reg), FD(t_c0[j]))), val);
-        cfs[0] = fma(val, inv, cfs[0]);
-    }
-    double e = 0.0;
-    if (flags & 2) {
-        const double x = fma(FD(x_d), f_regsel<NREG>(FD(x_reg), reg), FD(x_a));
-        double p = 0.0;
-        const int off0 = FD(coeff_off0), off1 = FD(coeff_off1);
-        if (off0 >= 0) {
-            const double* __restrict__ c = a.coeffs + off0;
-            double xp = 1.0;
-#pragma unroll 1
-            for (int q = 0; q < a.n_basis; ++q) { p = fma(ldk(c + q), xp, p); xp *= x; }
-        }
-        if (off1 >= 0) {
-            const double* __restrict__ c = a.coeffs + off1;
-            double xp = 1.0;
-#pragma unroll 1
-            for (int q = 0; q < a.n_basis; ++q) { p = fma(ldk(c + q), xp, p); xp *= x; }
-        }
-        e = p * inv;
-    }
-    const int row = ldk(a.date_row + t);
-    if (a.expo && row >= 0 && live) a.expo[(int64_t)row * a.ld_out + i] = e;
-    if (flags & 32) {
-        const double u = dev_thr(e, FD(thr));
-        if (flags & 8) {
-            const int rp = FD(rec_profile);
-            lean_record<1>({fmax(u, 0.0)}, {live}, rp, a.n_rec, first_tile, lds);
-            lean_record<1>({fmin(u, 0.0)}, {live}, rp + 1, a.n_rec, first_tile, lds);
-        }
-        if (flags & 4) {
-            const double sp = FD(s_b) * mcx_exp(fma(FD(s_c1), f_regsel<NREG>(FD(s_reg), reg), FD(s_c0)));
-            double cs = FD(c_a);
-            const double cb = FD(c_b);
-            if (cb != 0.0) cs = fma(cb, mcx_exp(fma(FD(c_c1), f_regsel<NREG>(FD(c_reg), reg), FD(c_c0))), cs);
-            cva[0] = fma(fmax(u, 0.0), sp * (1.0 - cs), cva[0]);
-        }
-    }
-#undef FD
-    return true;
-}
-
 // The book's events + metric operations of ONE timeline date for one lane.  The date's program chunk sits in the wave's
 // private LDS slot (`chunk`): all 64 lanes read the same addresses (LDS broadcast, no bank conflicts), so walking the
 // program costs ds_read latency (~64-128 clk) instead of a chain of dependent L2 round trips per record.
 template <int NSLOT, int SIG, int NNS, int NSTA, bool STORE>
-__device__ __forceinline__ void kf_on_date(const FusedArgs& a, int t, int64_t i, bool live, bool first_tile, double* __restrict__ lds,
+__device__ __forceinline__ void kf_on_date(KArgs& a, int t, int64_t i, bool live, bool first_tile, double* __restrict__ lds,
                                            const unsigned char* __restrict__ chunk, const double (&reg)[2 * NSLOT],
                                            double (&cfs)[NNS], double (&cva)[NNS], int (&est)[NSTA])
 {
     constexpr int NREG = 2 * NSLOT;
-    const K1Args& k = a.k1;
+    const auto& k = a.k1;
     const int n_rec = a.n_rec;
     if (STORE && k.paths && live) sim_store_state<NSLOT, SIG>(k, t, i, reg);
     const ChunkHeader* hdp = (const ChunkHeader*)chunk;
@@ -207,28 +145,35 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // interpreted.
 // SIMULATE = false: the same event/metric program runs on a paths tensor produced earlier by K1 (`k.paths` is then the
 // INPUT [date][state][path]): one pass over the paths replaces K2 + K4 and writes no exposure matrix unless asked to.
+// The arguments are read per code region (block prologue, tile prologue, one run of sub-steps, one date, per-path epilogue,
+// block epilogue) through kargs_region, as in kf_lean.hip: no argument SGPR is kept alive across the loops.
 template <int NSLOT, int NZ, bool INJECT, int SIG, int NNS, int NST, int NPF, bool SIMULATE>
-__device__ __forceinline__ void kf_body(const FusedArgs& a)
+__global__ __launch_bounds__(MCX_BLOCK) void kf_fused(const FusedArgs)      // read through kargs_region(), never by name
 {
     constexpr int NREG = 2 * NSLOT;
     constexpr int NSTA = NST > 0 ? NST : 1;
     constexpr int NPFA = NPF > 0 ? NPF : 1;
     extern __shared__ double lds[];
-    const K1Args& k = a.k1;
-    const int n_rec = a.n_rec;
+    KArgs& a0 = kargs_region(0);                                     // block prologue and epilogue
+    const int n_rec = a0.n_rec;
+    const int64_t n = a0.k1.n;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int rec_area = (9 * n_rec + 1) & ~1;                       // doubles; keeps the program slots 16-byte aligned
-    unsigned char* slot = (unsigned char*)(lds + rec_area) + (size_t)wv * a.chunk_cap;       // wave-private program slot
+    unsigned char* slot = (unsigned char*)(lds + rec_area) + (size_t)wv * a0.chunk_cap;      // wave-private program slot
     for (int q = threadIdx.x; q < 9 * n_rec; q += MCX_BLOCK) lds[q] = 0.0;
-    __shared__ double bm_lds[(SIMULATE && !INJECT) ? MCX_BM_LDS_DOUBLES : 2];      // Box-Muller lookup tables
-    const double* tab = nullptr;
-    if (SIMULATE && !INJECT) { mcx_bm_load(bm_lds); tab = bm_lds; }
+    constexpr int BM = (SIMULATE && !INJECT) ? MCX_BM_LDS_DOUBLES : 0;
+    constexpr int NE = NNS == 1 ? MCX_EXP_LDS_DOUBLES : 0;          // lean_date runs the straight-line dates of one netting set
+    __shared__ double tab_lds[BM + NE > 0 ? BM + NE : 1];           // Box-Muller lookup tables | exp table
+    const double* tab = BM ? tab_lds : nullptr;
+    const double* etab = tab_lds + BM;
+    if (BM) mcx_bm_load(tab_lds);
+    if (NE) mcx_exp_tab_load(tab_lds + BM);
     __syncthreads();
-    const int64_t tiles = (k.n + MCX_BLOCK - 1) / MCX_BLOCK;
+    const int64_t tiles = (n + MCX_BLOCK - 1) / MCX_BLOCK;
     double n_block = 0.0;
 
     u32x4 pf[NPFA];
-    auto prefetch = [&](int t) {             // issue the loads of date t's chunk (NPF > 0)
+    auto prefetch = [&](KArgs& a, int t) {   // issue the loads of date t's chunk (NPF > 0)
         if (NPF > 0 && t < a.n_dates) {
             const int off = ldk(a.date_off + t), end = ldk(a.date_off + t + 1);
 #pragma unroll
@@ -238,7 +183,7 @@ __device__ __forceinline__ void kf_body(const FusedArgs& a)
             }
         }
     };
-    auto stage = [&](int t) {                // make date t's chunk visible in the wave's LDS slot
+    auto stage = [&](KArgs& a, int t) {      // make date t's chunk visible in the wave's LDS slot
         if (NPF > 0) {
 #pragma unroll
             for (int p = 0; p < NPFA; ++p) ((u32x4*)slot)[p * 64 + lane] = pf[p];
@@ -251,55 +196,74 @@ __device__ __forceinline__ void kf_body(const FusedArgs& a)
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const bool first_tile = tile == (int64_t)blockIdx.x;
         const int64_t i_raw = tile * MCX_BLOCK + threadIdx.x;
-        const bool live = i_raw < k.n;
-        const int64_t i = live ? i_raw : k.n - 1;          // dead lanes shadow the last path (no stores, no contribution)
-        { const int64_t rest = k.n - tile * MCX_BLOCK; n_block += (double)(rest < MCX_BLOCK ? rest : MCX_BLOCK); }
+        const bool live = i_raw < n;
+        const int64_t i = live ? i_raw : n - 1;            // dead lanes shadow the last path (no stores, no contribution)
+        { const int64_t rest = n - tile * MCX_BLOCK; n_block += (double)(rest < MCX_BLOCK ? rest : MCX_BLOCK); }
 
-        double reg[NREG];                                  // reg[2s], reg[2s+1] = state of slot s
-        sim_init_state<NSLOT, SIG>(k, reg);
+        double reg1[1][NREG];                              // the one-path shape of lean_date
+        double (&reg)[NREG] = reg1[0];                     // reg[2s], reg[2s+1] = state of slot s
         double cfs[NNS], cva[NNS];
-#pragma unroll
-        for (int q = 0; q < NNS; ++q) { cfs[q] = 0.0; cva[q] = 0.0; }
         int est[NSTA];
+        uint64_t path;
+        int n_dates, n_init, n_steps;
+        {
+            KArgs& a = kargs_region(mcx_region_zero());   // tile prologue
+            sim_init_state<NSLOT, SIG>(a.k1, reg);
 #pragma unroll
-        for (int q = 0; q < NSTA; ++q) est[q] = a.init_state[q];
+            for (int q = 0; q < NNS; ++q) { cfs[q] = 0.0; cva[q] = 0.0; }
+#pragma unroll
+            for (int q = 0; q < NSTA; ++q) est[q] = a.init_state[q];
+            path = a.k1.path_offset + (uint64_t)i;
+            n_dates = a.n_dates; n_init = a.k1.n_initial_store; n_steps = a.k1.n_steps;
+            prefetch(a, 0);
+        }
 
         auto on_date = [&](int t, auto store) {
             constexpr bool ST = decltype(store)::value;
-            const bool fast = kf_fast_date<NSLOT, SIG, NNS, ST>(a, t, i, live, first_tile, lds, reg, cfs, cva);
-            if (!fast) stage(t);
-            prefetch(t + 1);
-            if (!fast) kf_on_date<NSLOT, SIG, NNS, NSTA, ST>(a, t, i, live, first_tile, lds, slot, reg, cfs, cva, est);
-        };
-        int next_t = 0;                                    // timeline dates are visited in increasing order, each once
-        prefetch(0);
-        if (SIMULATE) {
-            for (int t = 0; t < k.n_initial_store; ++t) {
-                on_date(t, std::integral_constant<bool, true>());
-                next_t = t + 1;
+            KArgs& a = kargs_region(mcx_region_zero());   // one date
+            if constexpr (NNS == 1) {
+                if (ldk(&a.fast[t].valid) != 0) {          // a straight-line record: the date program of kf_lean.hip
+                    // such a date has no chunk: the prefetched pieces are dead (kept live through lean_date, they cost 8 VGPRs)
+#pragma unroll
+                    for (int p = 0; p < NPFA; ++p) pf[p] = u32x4{0, 0, 0, 0};
+                    int est1[1] = {est[0]};                // (mcx_fused_create: a stateful event of such a date has sidx 0)
+                    lean_date<NSLOT, SIG, 1, ST>(t, {i}, {live}, first_tile, lds, reg1, cfs, cva, est1, etab);
+                    est[0] = est1[0];
+                    prefetch(a, t + 1);
+                    return;
+                }
             }
-            const uint64_t path = k.path_offset + (uint64_t)i;
+            stage(a, t);
+            prefetch(a, t + 1);
+            kf_on_date<NSLOT, SIG, NNS, NSTA, ST>(a, t, i, live, first_tile, lds, slot, reg, cfs, cva, est);
+        };
+        // timeline dates are visited in increasing order, each once
+        if (SIMULATE) {
+            for (int t = 0; t < n_init; ++t) on_date(t, std::integral_constant<bool, true>());
             // two nested loops: the inner one is the bare sub-step recursion up to the next timeline date (register
             // allocation then treats it as the hot loop: the date program's scalars are not kept alive / spilled through it)
             int step = 0;
 #pragma unroll 1
-            while (step < k.n_steps) {
+            while (step < n_steps) {
                 int st;
+                {
+                    const int zr = mcx_region_zero();     // one run of sub-steps: arguments, Box-Muller coefficients
+                    const auto& k = kargs_region(zr).k1;
+                    const mcx_bm_coef bc = mcx_bm_coef_load(zr);
 #pragma unroll 1
-                do {
-                    sim_substep<NSLOT, NZ, INJECT, SIG>(k, step, path, i, reg, tab);
-                    st = ldk(&k.steps[step].store_idx);
-                    ++step;
-                } while (st < 0 && step < k.n_steps);
-                if (st >= 0) {
-                    on_date(st, std::integral_constant<bool, true>());
-                    next_t = st + 1;
+                    do {
+                        sim_substep<NSLOT, NZ, INJECT, SIG>(k, step, path, i, reg, tab, k.seed, bc);
+                        st = ldk(&k.steps[step].store_idx);
+                        ++step;
+                    } while (st < 0 && step < n_steps);
                 }
+                if (st >= 0) on_date(st, std::integral_constant<bool, true>());
             }
         } else {
-            const int D = k.n_state;
             double nxt[NREG];
             auto load_row = [&](int t, double (&dst)[NREG]) {
+                const auto& k = kargs_region(mcx_region_zero()).k1;
+                const int D = k.n_state;
 #pragma unroll
                 for (int s = 0; s < NSLOT; ++s) {
                     const bool bs = sig_kind(SIG, s) >= 0 ? sig_is_bs(SIG, s) : (k.slots[s].kind == MCX_MODEL_BS);
@@ -310,38 +274,32 @@ __device__ __forceinline__ void kf_body(const FusedArgs& a)
             };
             load_row(0, nxt);
 #pragma unroll 1
-            for (int t = 0; t < a.n_dates; ++t) {
+            for (int t = 0; t < n_dates; ++t) {
 #pragma unroll
                 for (int q = 0; q < NREG; ++q) reg[q] = nxt[q];
-                if (t + 1 < a.n_dates) load_row(t + 1, nxt);      // next date's state streams in while this date's ops run
+                if (t + 1 < n_dates) load_row(t + 1, nxt);      // next date's state streams in while this date's ops run
                 on_date(t, std::integral_constant<bool, false>());
-                next_t = t + 1;
             }
         }
-        (void)next_t;
-        // per-path quantities
-        for (int w = 0; w < a.n_ns; ++w) {
-            double cv = cfs[0], cc = cva[0];
+        {
+            KArgs& a = kargs_region(mcx_region_zero());   // per-path epilogue
+            for (int w = 0; w < a.n_ns; ++w) {
+                double cv = cfs[0], cc = cva[0];
 #pragma unroll
-            for (int q = 1; q < NNS; ++q) { cv = (w == q) ? cfs[q] : cv; cc = (w == q) ? cva[q] : cc; }
-            if (a.cfs && live) a.cfs[(int64_t)w * a.ld_out + i] = cv;
-            if (a.rec_pv[w] >= 0) lean_record<1>({cv}, {live}, a.rec_pv[w], n_rec, first_tile, lds);
-            if (a.rec_cva[w] >= 0) lean_record<1>({cc * a.lgd[w]}, {live}, a.rec_cva[w], n_rec, first_tile, lds);
+                for (int q = 1; q < NNS; ++q) { cv = (w == q) ? cfs[q] : cv; cc = (w == q) ? cva[q] : cc; }
+                if (a.cfs && live) a.cfs[(int64_t)w * a.ld_out + i] = cv;
+                if (a.rec_pv[w] >= 0) lean_record<1>({cv}, {live}, a.rec_pv[w], n_rec, first_tile, lds);
+                if (a.rec_cva[w] >= 0) lean_record<1>({cc * a.lgd[w]}, {live}, a.rec_cva[w], n_rec, first_tile, lds);
+            }
         }
     }
     __syncthreads();
     for (int r = threadIdx.x; r < n_rec; r += MCX_BLOCK) {
         double s1 = 0.0, s2 = 0.0;
         for (int w = 0; w < 4; ++w) { s1 += lds[n_rec + (w * n_rec + r) * 2]; s2 += lds[n_rec + (w * n_rec + r) * 2 + 1]; }
-        double* dst = a.partials + ((int64_t)blockIdx.x * n_rec + r) * 4;
+        double* dst = a0.partials + ((int64_t)blockIdx.x * n_rec + r) * 4;
         dst[0] = n_block; dst[1] = lds[r]; dst[2] = s1; dst[3] = s2;
     }
-}
-
-template <int NSLOT, int NZ, bool INJECT, int SIG, int NNS, int NST, int NPF, bool SIMULATE>
-__global__ __launch_bounds__(MCX_BLOCK) void kf_fused(const FusedArgs a)
-{
-    kf_body<NSLOT, NZ, INJECT, SIG, NNS, NST, NPF, SIMULATE>(a);
 }
 
 // merge per-block records (Chan, Golub, LeVeque pairwise update) -> out[r] = (n, mean, 0, M2).
@@ -380,6 +338,7 @@ void launch_kf(const FusedArgs& a, int grid, size_t lds, int npf, bool inject, b
 #define MCX_KF_NPF(INJ, NNS, NST) do { if (npf == 1) MCX_KF(INJ, NNS, NST, 1); else if (npf == 2) MCX_KF(INJ, NNS, NST, 2); else MCX_KF(INJ, NNS, NST, 0); } while (0)
     if (inject) {
         if (one_ns && no_state) MCX_KF_NPF(true, 1, 0);
+        else if (one_ns) MCX_KF(true, 1, MCX_FUSED_MAX_STATEFUL, 0);      // (straight-line dates have no chunk: NNS = 1 runs them)
         else MCX_KF(true, MCX_FUSED_MAX_NS, MCX_FUSED_MAX_STATEFUL, 0);
     } else {
         if (one_ns && no_state) MCX_KF_NPF(false, 1, 0);
@@ -587,7 +546,7 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
         fd.ni_reg = fd.lin_reg = fd.x_reg = fd.s_reg = fd.c_reg = -1;
         fd.coeff_off0 = fd.coeff_off1 = -1; fd.rec_profile = -1;
         for (int j = 0; j < 4; ++j) fd.t_reg[j] = -1;
-        bool okf = fast_dates_enabled, lean_only = false;
+        bool okf = fast_dates_enabled;
         const FAtom* num = nullptr;
         int n_expo = 0;
         for (size_t ei = 0; ei < by_date[t].size(); ++ei) {
@@ -602,14 +561,14 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
             if ((plain_option || e.kind == MCX_EV_CASHFLOW) && (fd.flags & 512)) { okf = false; break; }      // the payoff's max() stands alone
             if (plain_option) {
                 if (fd.flags & 1) { okf = false; break; }
-                fd.flags |= 512; lean_only = true;
+                fd.flags |= 512;
                 fd.op_strike = e.strike; fd.op_sign = e.sign;
             }
             if (num && memcmp(num, &e.num, sizeof(FAtom)) != 0) { okf = false; break; }     // one numeraire per date
             num = &e.num;
             if (e.kind == MCX_EV_EXERCISE) {
                 if ((fd.flags & (128 | 2)) || e.x.b != 0.0) { okf = false; break; }            // one exercise event, before the exposure
-                fd.flags |= 128; lean_only = true;
+                fd.flags |= 128;
                 fd.ex_term_off = (int32_t)lterms.size(); fd.ex_coeff_off = e.coeff_off; fd.ex_strike = e.strike; fd.ex_sign = e.sign;
                 fd.ex_x_reg = e.x.reg; fd.ex_x_a = e.x.a; fd.ex_x_d = e.x.d; fd.ex_lin_reg = -1;
                 for (int j = e.term_begin; j < e.term_end && okf; ++j) {
@@ -658,7 +617,7 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
                 if ((fd.flags & 256)) { okf = false; break; }
                 fd.flags |= 2; fd.x_reg = e.x.reg; fd.x_a = e.x.a; fd.x_d = e.x.d;
                 int off = e.coeff_off >= 0 ? e.coeff_off + e.init_state * book->n_basis : -1;
-                if (stateful) { fd.flags |= 256; lean_only = true; off = e.coeff_off; if (off < 0) { okf = false; break; } }
+                if (stateful) { fd.flags |= 256; off = e.coeff_off; if (off < 0) { okf = false; break; } }
                 (n_expo == 0 ? fd.coeff_off0 : fd.coeff_off1) = off;
                 n_expo++;
             }
@@ -696,7 +655,7 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
             fd.m_s1 = fd.s_c1;
         }
         if (!okf) lterms.resize(fd.ex_term_off <= (int32_t)lterms.size() && (fd.flags & 128) ? fd.ex_term_off : lterms.size());
-        fd.valid = okf ? (lean_only ? 2 : 1) : 0;
+        fd.valid = okf ? 1 : 0;
         fast[t] = fd;
     }
     // per-date program chunks: header | events | terms | metric ops, 16-byte aligned
@@ -707,7 +666,7 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
     for (int t = 0; t < T; ++t) for (const FEvent& e : by_date[t]) if (e.kind == MCX_EV_EXPO_BS) bs_exposure = true;
     for (int t = 0; t < T; ++t) {
         date_off[t] = (int32_t)prog.size();
-        if (fast[t].valid == 1) continue;              // evaluated from its FastDate record in every kernel: no interpreted chunk
+        if (fast[t].valid) continue;                   // evaluated from its FastDate record by lean_date: no interpreted chunk
         ChunkHeader hd;
         hd.n_ev = (int)by_date[t].size(); hd.n_mop = (int)mop_by_date[t].size(); hd.n_terms = (int)terms_by_date[t].size();
         const size_t bytes = sizeof(hd) + sizeof(FEvent) * by_date[t].size() + sizeof(FTerm) * terms_by_date[t].size() +
@@ -725,7 +684,6 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
     }
     date_off[T] = (int32_t)prog.size();
     if (bs_exposure) { delete f; MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: analytic Black-Scholes exposures are evaluated by the book kernel (K2)"); }
-    // LDS budget: 4 wave slots + the record area must fit comfortably (several blocks per CU)
     bool lean = d->n_netting_sets == 1 && n_stateful <= 1;
     for (int t = 0; t < T; ++t) lean = lean && fast[t].valid != 0;
     // no interpreted date at all: no program slots (NPF = 0, chunk_cap = 0)
@@ -756,6 +714,8 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
             cva_only = false;          // a threshold, an EPE / ENE record or an exercise: the general program
         }
     }
+    // LDS budget: 4 wave slots + the record area (dynamic) must fit comfortably; with kf_fused's static tables (Box-Muller 4 KiB,
+    // exponential 1 KiB) a block holds at most 65 KiB of the CU's 160 KiB
     if ((size_t)4 * f->chunk_cap + sizeof(double) * 9 * (size_t)n_rec > 60 * 1024) {
         delete f;
         MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: a date's event program (%d B) exceeds the per-wave LDS slot budget", max_chunk);

@@ -615,14 +615,6 @@ __device__ __forceinline__ void sim_substep(const KA& k, int step, uint64_t path
     sim_apply<NSLOT, NZ, SIG, POS>(k, step, reg, z, u);
 }
 
-template <int NSLOT, int NZ, bool INJECT, int SIG>
-__device__ __forceinline__ void sim_substep(const K1Args& k, int step, uint64_t path, int64_t i, double (&reg)[2 * NSLOT],
-                                            const double* __restrict__ tab)
-{
-    const mcx_bm_coef bc = mcx_bm_coef_load();
-    sim_substep<NSLOT, NZ, INJECT, SIG>(k, step, path, i, reg, tab, k.seed, bc);
-}
-
 // state columns of a slot kind: Black-Scholes 1, Schwartz two-factor 3 (log S is derived: log F0(t) + x + y), the others 2
 __host__ __device__ constexpr int mcx_kind_state_dim(int kind) { return kind == MCX_MODEL_BS ? 1 : kind == MCX_MODEL_S2F ? 3 : 2; }
 
