@@ -330,6 +330,25 @@ int  mcx_fused_num_records(const mcx_fused* f);
 /* 1 when every timeline date of the program compiled to a straight-line record (the lean kernel: the one-launch plan is then
  * the fastest), 0 when some dates run the generic interpreter (K1 + mcx_fused_eval_paths is usually faster) */
 int  mcx_fused_is_straight_line(const mcx_fused* f);
+/* Route query (read-only; tests, diagnostics): what a pass of f with injected draws (inject != 0) and simulating (simulate != 0,
+ * mcx_fused_run) or streaming a paths tensor (simulate == 0, mcx_fused_eval_paths) launches, from the same host function that
+ * chooses the launch.  out[MCX_FDESC_*] is the header below, then two entries per timeline date t:
+ * out[MCX_FDESC_HEADER + 2 t] = 1 when the date is straight-line (evaluated from its FastDate record), 0 when interpreted, and
+ * out[MCX_FDESC_HEADER + 2 t + 1] = the record's flag bits.  Returns the number of entries (MCX_FDESC_HEADER + 2 n_dates); when
+ * that exceeds cap nothing is written; < 0 on error. */
+enum { MCX_ROUTE_NONE = 0, MCX_ROUTE_LEAN = 1, MCX_ROUTE_FUSED = 2 };
+enum {
+    MCX_FDESC_LEAN = 0,        /* every date straight-line (mcx_fused_is_straight_line)                          */
+    MCX_FDESC_NPF = 1,         /* 1 KiB prefetch pieces of the object (0, 1, 2)                                    */
+    MCX_FDESC_CHUNK_CAP = 2,   /* bytes of a wave's program slot                                                   */
+    MCX_FDESC_MAX_CHUNK = 3,   /* bytes of the largest interpreted date chunk (0: no interpreted date)             */
+    MCX_FDESC_N_NS = 4, MCX_FDESC_N_STATEFUL = 5, MCX_FDESC_N_DATES = 6,
+    MCX_FDESC_CVA_DATES = 7,   /* 1: the cva-date kernel of kf_lean is available to runs without outputs            */
+    MCX_FDESC_KERNEL = 8,      /* MCX_ROUTE_*                                                                      */
+    MCX_FDESC_NNS = 9, MCX_FDESC_NST = 10, MCX_FDESC_KNPF = 11,      /* kf_fused's template bounds (MCX_ROUTE_FUSED)      */
+    MCX_FDESC_HEADER = 16
+};
+int  mcx_fused_describe(const mcx_fused* f, int32_t inject, int32_t simulate, int32_t* out, int32_t cap);
 int  mcx_fused_run(mcx_handle* h, const mcx_fused* f, uint64_t seed, uint64_t path_offset, int64_t n_paths,
                    double* d_paths, int64_t ld, double* d_cfs, double* d_expo, int64_t ld_out,
                    const double* d_inject_z, const double* d_inject_u, mcx_acc* h_out, void* stream);

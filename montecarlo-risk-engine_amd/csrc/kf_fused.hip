@@ -329,20 +329,28 @@ __global__ __launch_bounds__(MCX_BLOCK) void kf_merge(const double* __restrict__
     if (threadIdx.x == 0) { out[r].n = sN[0]; out[r].shift = sM[0]; out[r].s1 = 0.0; out[r].s2 = sQ[0]; }
 }
 
+// The kernel a pass launches, chosen by kf_route() below: kf_lean (every date straight-line), or kf_fused with these template
+// bounds.  launch_kf maps the fields one to one onto instantiations; mcx_fused_describe reports the same record.
+struct KfRoute {
+    int kernel;                // MCX_ROUTE_NONE / MCX_ROUTE_LEAN / MCX_ROUTE_FUSED
+    bool inject;
+    int nns, nst, npf;         // kf_fused's NNS, NST and NPF (0 unless kernel == MCX_ROUTE_FUSED)
+};
+
 template <int NSLOT, int NZ, int SIG>
-void launch_kf(const FusedArgs& a, int grid, size_t lds, int npf, bool inject, bool simulate, hipStream_t s)
+void launch_kf(const FusedArgs& a, int grid, size_t lds, const KfRoute& r, bool simulate, hipStream_t s)
 {
-    const bool one_ns = a.n_ns == 1, no_state = a.n_stateful == 0;
+    const int npf = r.npf;
 #define MCX_KF(INJ, NNS, NST, NPF) do { if (simulate) hipLaunchKernelGGL((kf_fused<NSLOT, NZ, INJ, SIG, NNS, NST, NPF, true>), dim3(grid), dim3(MCX_BLOCK), lds, s, a); \
         else if (!INJ) hipLaunchKernelGGL((kf_fused<NSLOT, NZ, false, SIG, NNS, NST, NPF, false>), dim3(grid), dim3(MCX_BLOCK), lds, s, a); } while (0)
 #define MCX_KF_NPF(INJ, NNS, NST) do { if (npf == 1) MCX_KF(INJ, NNS, NST, 1); else if (npf == 2) MCX_KF(INJ, NNS, NST, 2); else MCX_KF(INJ, NNS, NST, 0); } while (0)
-    if (inject) {
-        if (one_ns && no_state) MCX_KF_NPF(true, 1, 0);
-        else if (one_ns) MCX_KF(true, 1, MCX_FUSED_MAX_STATEFUL, 0);      // (straight-line dates have no chunk: NNS = 1 runs them)
+    if (r.inject) {
+        if (r.nns == 1 && r.nst == 0) MCX_KF_NPF(true, 1, 0);
+        else if (r.nns == 1) MCX_KF(true, 1, MCX_FUSED_MAX_STATEFUL, 0);
         else MCX_KF(true, MCX_FUSED_MAX_NS, MCX_FUSED_MAX_STATEFUL, 0);
     } else {
-        if (one_ns && no_state) MCX_KF_NPF(false, 1, 0);
-        else if (one_ns) MCX_KF_NPF(false, 1, MCX_FUSED_MAX_STATEFUL);
+        if (r.nns == 1 && r.nst == 0) MCX_KF_NPF(false, 1, 0);
+        else if (r.nns == 1) MCX_KF_NPF(false, 1, MCX_FUSED_MAX_STATEFUL);
         else MCX_KF(false, MCX_FUSED_MAX_NS, MCX_FUSED_MAX_STATEFUL, 0);
     }
 #undef MCX_KF_NPF
@@ -359,7 +367,7 @@ struct mcx_fused {
     FastDate* d_fast;
     int32_t* d_date_off;
     int32_t* d_date_row;
-    int chunk_cap, npf;
+    int chunk_cap, npf, max_chunk;      // max_chunk: bytes of the largest interpreted chunk (0: none)
     int lean;                  // every date has a FastDate record kf_lean.hip can run (valid != 0)
     FastDateCva* d_cva;        // [n_dates] when every date runs in the cva-date kernel of kf_lean.hip, else nullptr
     LeanTerm* d_lterms;
@@ -689,6 +697,7 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
     // no interpreted date at all: no program slots (NPF = 0, chunk_cap = 0)
     f->npf = max_chunk == 0 ? 0 : (max_chunk <= 1024 ? 1 : (max_chunk <= 2048 ? 2 : 0));
     f->chunk_cap = f->npf > 0 ? f->npf * 1024 : ((max_chunk + 255) & ~255);
+    f->max_chunk = max_chunk;
     // the straight-line kernel skips the zero test under the CIR++ diffusion root: it needs a positive initial intensity (the
     // reference asserts y0 > 0, cirpp.py:40; the state is floored at 1e-12 after every step); other starts run the interpreter
     for (int q = 0; q < sd.n_slots; ++q)
@@ -750,6 +759,22 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
     return 0;
 }
 
+// the one place that decides which kernel a pass runs (fused_run_impl launches it, mcx_fused_describe reports it)
+static KfRoute kf_route(const mcx_fused* f, bool inject, bool simulate)
+{
+    KfRoute r;
+    r.kernel = MCX_ROUTE_NONE; r.inject = inject; r.nns = 0; r.nst = 0; r.npf = 0;
+    if (f->lean && (simulate || !inject)) { r.kernel = MCX_ROUTE_LEAN; return r; }
+    if (inject && !simulate) return r;                        // a paths tensor is never evaluated with injected draws
+    r.kernel = MCX_ROUTE_FUSED;
+    const bool one_ns = f->n_ns == 1, no_state = f->n_stateful == 0;
+    const int npf = (f->npf == 1 || f->npf == 2) ? f->npf : 0;
+    if (one_ns && no_state) { r.nns = 1; r.nst = 0; r.npf = npf; }
+    else if (one_ns) { r.nns = 1; r.nst = MCX_FUSED_MAX_STATEFUL; r.npf = inject ? 0 : npf; }     // (straight-line dates have no chunk: NNS = 1 runs them)
+    else { r.nns = MCX_FUSED_MAX_NS; r.nst = MCX_FUSED_MAX_STATEFUL; r.npf = 0; }
+    return r;
+}
+
 static int fused_run_impl(mcx_handle* h, const mcx_fused* f, bool simulate, uint64_t seed, uint64_t path_offset, int64_t n_paths,
                           double* d_paths, int64_t ld, double* d_cfs, double* d_expo, int64_t ld_out,
                           const double* d_inject_z, const double* d_inject_u, mcx_acc* h_out, mcx_acc* d_out, void* stream)
@@ -787,7 +812,9 @@ static int fused_run_impl(mcx_handle* h, const mcx_fused* f, bool simulate, uint
     // device address space): no copy kernel and no extra dispatch on the stream between the pass and its result
     const bool direct = !d_out && sizeof(mcx_acc) * (size_t)f->n_rec <= h->pinned_bytes && h->d_pinned_alias;
     mcx_acc* dst = d_out ? d_out : (direct ? (mcx_acc*)h->d_pinned_alias : f->d_out);
-    if (f->lean && (simulate || !inj)) {
+    const KfRoute route = kf_route(f, inj, simulate);
+    if (route.kernel == MCX_ROUTE_NONE) MCX_FAIL(h, -2, "mcx_fused_run: no kernel evaluates a paths tensor with injected draws");
+    if (route.kernel == MCX_ROUTE_LEAN) {
         // every date is a straight-line record: the two-paths-per-lane kernel of kf_lean.hip (simulating, or streaming a paths tensor)
         // (merging the per-block records in the kernel's last block — arrival ticket + device-scope fences — was measured: the
         //  fences cost ~25 us per launch, three times the kernel boundary they save)
@@ -800,21 +827,21 @@ static int fused_run_impl(mcx_handle* h, const mcx_fused* f, bool simulate, uint
         if (tiles > 2048) { int per = (int)((tiles + 2047) / 2048); grid = (int)((tiles + per - 1) / per); }
         const size_t lds = sizeof(double) * (size_t)((9 * f->n_rec + 1) & ~1) + (size_t)4 * f->chunk_cap;
         switch (mcx_sim_signature(sd)) {
-        case SIG_VAS_CIR_E: launch_kf<2, 2, SIG_VAS_CIR_E>(a, grid, lds, f->npf, inj, simulate, s); break;
-        case SIG_BS_A: launch_kf<1, 1, SIG_BS_A>(a, grid, lds, f->npf, inj, simulate, s); break;
-        case SIG_BS_E: launch_kf<1, 1, SIG_BS_E>(a, grid, lds, f->npf, inj, simulate, s); break;
-        case SIG_HESTON_QE: launch_kf<1, 2, SIG_HESTON_QE>(a, grid, lds, f->npf, inj, simulate, s); break;
-        case SIG_HESTON_E: launch_kf<1, 2, SIG_HESTON_E>(a, grid, lds, f->npf, inj, simulate, s); break;
-        case SIG_VAS_E: launch_kf<1, 1, SIG_VAS_E>(a, grid, lds, f->npf, inj, simulate, s); break;
-        case SIG_VAS_A: launch_kf<1, 1, SIG_VAS_A>(a, grid, lds, f->npf, inj, simulate, s); break;
-        case SIG_BS_VAS_CIRDET_E: launch_kf<3, 3, SIG_BS_VAS_CIRDET_E>(a, grid, lds, f->npf, inj, simulate, s); break;
+        case SIG_VAS_CIR_E: launch_kf<2, 2, SIG_VAS_CIR_E>(a, grid, lds, route, simulate, s); break;
+        case SIG_BS_A: launch_kf<1, 1, SIG_BS_A>(a, grid, lds, route, simulate, s); break;
+        case SIG_BS_E: launch_kf<1, 1, SIG_BS_E>(a, grid, lds, route, simulate, s); break;
+        case SIG_HESTON_QE: launch_kf<1, 2, SIG_HESTON_QE>(a, grid, lds, route, simulate, s); break;
+        case SIG_HESTON_E: launch_kf<1, 2, SIG_HESTON_E>(a, grid, lds, route, simulate, s); break;
+        case SIG_VAS_E: launch_kf<1, 1, SIG_VAS_E>(a, grid, lds, route, simulate, s); break;
+        case SIG_VAS_A: launch_kf<1, 1, SIG_VAS_A>(a, grid, lds, route, simulate, s); break;
+        case SIG_BS_VAS_CIRDET_E: launch_kf<3, 3, SIG_BS_VAS_CIRDET_E>(a, grid, lds, route, simulate, s); break;
         default:
             switch (sd.n_slots * 16 + sd.n_z) {
-            case 1 * 16 + 1: launch_kf<1, 1, SIG_GENERIC>(a, grid, lds, f->npf, inj, simulate, s); break;
-            case 1 * 16 + 2: launch_kf<1, 2, SIG_GENERIC>(a, grid, lds, f->npf, inj, simulate, s); break;
-            case 2 * 16 + 2: launch_kf<2, 2, SIG_GENERIC>(a, grid, lds, f->npf, inj, simulate, s); break;
-            case 3 * 16 + 3: launch_kf<3, 3, SIG_GENERIC>(a, grid, lds, f->npf, inj, simulate, s); break;
-            case 4 * 16 + 4: launch_kf<4, 4, SIG_GENERIC>(a, grid, lds, f->npf, inj, simulate, s); break;
+            case 1 * 16 + 1: launch_kf<1, 1, SIG_GENERIC>(a, grid, lds, route, simulate, s); break;
+            case 1 * 16 + 2: launch_kf<1, 2, SIG_GENERIC>(a, grid, lds, route, simulate, s); break;
+            case 2 * 16 + 2: launch_kf<2, 2, SIG_GENERIC>(a, grid, lds, route, simulate, s); break;
+            case 3 * 16 + 3: launch_kf<3, 3, SIG_GENERIC>(a, grid, lds, route, simulate, s); break;
+            case 4 * 16 + 4: launch_kf<4, 4, SIG_GENERIC>(a, grid, lds, route, simulate, s); break;
             default: MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: (slots=%d, z=%d) has no fused instantiation", sd.n_slots, sd.n_z);
             }
         }
@@ -833,6 +860,24 @@ static int fused_run_impl(mcx_handle* h, const mcx_fused* f, bool simulate, uint
 extern "C" int mcx_fused_is_straight_line(const mcx_fused* f)
 {
     return (f && f->lean) ? 1 : 0;
+}
+
+extern "C" int mcx_fused_describe(const mcx_fused* f, int32_t inject, int32_t simulate, int32_t* out, int32_t cap)
+{
+    if (!f || cap < 0 || (cap > 0 && !out)) return -1;
+    const int need = MCX_FDESC_HEADER + 2 * f->n_dates;
+    if (cap < need) return need;
+    const KfRoute r = kf_route(f, inject != 0, simulate != 0);
+    int32_t* o = out;
+    memset(o, 0, sizeof(int32_t) * MCX_FDESC_HEADER);
+    o[MCX_FDESC_LEAN] = f->lean; o[MCX_FDESC_NPF] = f->npf; o[MCX_FDESC_CHUNK_CAP] = f->chunk_cap; o[MCX_FDESC_MAX_CHUNK] = f->max_chunk;
+    o[MCX_FDESC_N_NS] = f->n_ns; o[MCX_FDESC_N_STATEFUL] = f->n_stateful; o[MCX_FDESC_N_DATES] = f->n_dates;
+    o[MCX_FDESC_CVA_DATES] = f->d_cva != nullptr;
+    o[MCX_FDESC_KERNEL] = r.kernel; o[MCX_FDESC_NNS] = r.nns; o[MCX_FDESC_NST] = r.nst; o[MCX_FDESC_KNPF] = r.npf;
+    std::vector<FastDate> fast(f->n_dates);
+    if (f->n_dates > 0 && hipMemcpy(fast.data(), f->d_fast, sizeof(FastDate) * fast.size(), hipMemcpyDeviceToHost) != hipSuccess) return -100;
+    for (int t = 0; t < f->n_dates; ++t) { o[MCX_FDESC_HEADER + 2 * t] = fast[t].valid; o[MCX_FDESC_HEADER + 2 * t + 1] = fast[t].flags; }
+    return need;
 }
 
 extern "C" int mcx_fused_run(mcx_handle* h, const mcx_fused* f, uint64_t seed, uint64_t path_offset, int64_t n_paths,

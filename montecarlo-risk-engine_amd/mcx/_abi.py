@@ -75,6 +75,10 @@ class FusedDesc(C.Structure):
 
 E_NOT_FUSABLE = -10
 FUSED_MAX_NS = 4
+FUSED_MAX_STATEFUL = 4
+# mcx_fused_describe (include/mcx.h): MCX_ROUTE_* and the header length MCX_FDESC_HEADER
+ROUTE_NONE, ROUTE_LEAN, ROUTE_FUSED = 0, 1, 2
+FDESC_HEADER = 16
 
 
 def ptr(a: np.ndarray | None) -> C.c_void_p:

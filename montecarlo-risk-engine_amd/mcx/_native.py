@@ -24,7 +24,7 @@ _EXPORTS = [
     "mcx_book_create", "mcx_book_destroy", "mcx_book_set_coeffs", "mcx_eval_book", "mcx_resolve_atoms",
     "mcx_lsm_stats", "mcx_lsm_step", "mcx_lsm_run", "mcx_lsm_solve", "mcx_lsm_step_batch", "mcx_lsm_step_batch_dev", "mcx_lsm_solve_batch", "mcx_lsm_run_batch", "mcx_book_get_coeffs", "mcx_book_set_coeffs_batch", "mcx_book_set_bridge_rng", "mcx_book_set_exercise_replay",
     "mcx_fused_is_straight_line", "mcx_tangent_paths", "mcx_tangent_lsm", "mcx_tangent_lsm_step", "mcx_tangent_eval", "mcx_tangent_cva", "mcx_tangent_profiles", "mcx_tangent_pick",
-    "mcx_box_muller", "mcx_tangent_european", "mcx_fused_create", "mcx_fused_destroy", "mcx_fused_num_records", "mcx_fused_run", "mcx_fused_eval_paths", "mcx_fused_run_device", "mcx_fused_eval_paths_device", "mcx_fused_set_timing", "mcx_fused_kernel_times",
+    "mcx_box_muller", "mcx_tangent_european", "mcx_fused_create", "mcx_fused_destroy", "mcx_fused_num_records", "mcx_fused_run", "mcx_fused_eval_paths", "mcx_fused_run_device", "mcx_fused_eval_paths_device", "mcx_fused_set_timing", "mcx_fused_kernel_times", "mcx_fused_describe",
     "mcx_value_poly_fit", "mcx_book_collapse_values", "mcx_book_value_poly_info", "mcx_rows_minmax",
     "mcx_reduce_vector", "mcx_reduce_profiles", "mcx_reduce_cva", "mcx_unsecured", "mcx_select_hist", "mcx_select_hist_dev", "mcx_select_narrow", "mcx_select_bracket", "mcx_select_hist_rows",
 ]
@@ -46,6 +46,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_fused_destroy.restype = None
     lib.mcx_fused_num_records.argtypes = [C.c_void_p]
     lib.mcx_fused_is_straight_line.argtypes = [C.c_void_p]
+    lib.mcx_fused_describe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
     if lib.mcx_abi_version() != _abi.ABI_VERSION:
         raise RuntimeError("libmcx_hip.so ABI version mismatch")
     return lib
@@ -324,6 +325,23 @@ class HipBackend:
 
     def fused_is_straight_line(self, f) -> bool:
         return bool(self.lib.mcx_fused_is_straight_line(f.ptr))
+
+    def fused_describe(self, f, inject: bool, simulate: bool) -> dict:
+        """the route of a pass of `f` (mcx_fused_describe): kernel "lean" / "fused" / None, kf_fused's bounds nns / nst / npf, the
+        object's lean / npf / chunk_cap / max_chunk / n_ns / n_stateful / n_dates / cva_dates, and per date `valid` (1: straight-line,
+        0: interpreted) and the FastDate `flags`"""
+        n = self.lib.mcx_fused_describe(f.ptr, int(inject), int(simulate), None, 0)
+        if n < 0:
+            raise RuntimeError(f"mcx_fused_describe failed ({n})")
+        out = np.zeros(n, dtype=np.int32)
+        rc = self.lib.mcx_fused_describe(f.ptr, int(inject), int(simulate), _abi.ptr(out), C.c_int32(n))
+        if rc != n:
+            raise RuntimeError(f"mcx_fused_describe failed ({rc})")
+        h, d = out[:_abi.FDESC_HEADER], out[_abi.FDESC_HEADER:].reshape(-1, 2)
+        kernel = {_abi.ROUTE_LEAN: "lean", _abi.ROUTE_FUSED: "fused"}.get(int(h[8]))
+        return dict(lean=bool(h[0]), npf=int(h[1]), chunk_cap=int(h[2]), max_chunk=int(h[3]), n_ns=int(h[4]), n_stateful=int(h[5]),
+                    n_dates=int(h[6]), cva_dates=bool(h[7]), kernel=kernel, nns=int(h[9]), nst=int(h[10]), kernel_npf=int(h[11]),
+                    valid=d[:, 0].copy(), flags=d[:, 1].copy())
 
     def fused_eval_paths(self, fused, paths: torch.Tensor, cfs=None, expo=None, device_records: bool = False):
         n = paths.shape[2]

@@ -36,6 +36,9 @@ def _run(build, n_main, steps, hip, oracle, materialize=False):
             sc.main_plan = "fused"
             sc.materialize = materialize
         out[be.name] = sc.run_simulation().results
+        if be is hip:      # the route of the pass just run (mcx_fused_describe: the host function that chose the launch)
+            out["route"] = hip.fused_describe(sc._fused, False, True)
+            out["expo"] = sc.last_state["expo"]
     return out
 
 
@@ -68,9 +71,18 @@ NOT_QUALIFYING = {
 @pytest.mark.parametrize("kind", list(NOT_QUALIFYING))
 def test_books_off_the_cva_date_kernel(kind, hip, oracle):
     kw = NOT_QUALIFYING[kind]
-    _check(_run(lambda: _irs_book(3.0, True, 0.25, 1.0, **kw), 300001, 2, hip, oracle), kind)
+    out = _run(lambda: _irs_book(3.0, True, 0.25, 1.0, **kw), 300001, 2, hip, oracle)
+    d = out["route"]
+    # every date straight-line: kf_lean's general date program, not the cva-date kernel and not the interpreter
+    assert d["kernel"] == "lean" and d["lean"] and (d["valid"] == 1).all() and not d["cva_dates"], d
+    assert (d["flags"] & (8 if kind == "added_epe" else 128)).any(), d
+    _check(out, kind)
 
 
 def test_exposure_output_runs_the_general_program(hip, oracle):
     """materialize: the pass also writes paths and exposures, which only the general date program does"""
-    _check(_run(lambda: _irs_book(3.0, True, 0.25, 1.0), 300001, 2, hip, oracle, materialize=True), "materialize")
+    out = _run(lambda: _irs_book(3.0, True, 0.25, 1.0), 300001, 2, hip, oracle, materialize=True)
+    d = out["route"]
+    # the book has the cva-date records, but a run with outputs launches kf_lean's general program (fused_run_impl: a.cva_dates)
+    assert d["kernel"] == "lean" and (d["valid"] == 1).all() and d["cva_dates"] and out["expo"] is not None, d
+    _check(out, "materialize")

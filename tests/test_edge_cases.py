@@ -239,21 +239,34 @@ class _Unpadded:
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
-def test_cir_intensity_starting_at_zero(fused, hip, oracle, monkeypatch):
+@pytest.mark.parametrize("fused,plan", [(True, "auto"), (False, "auto"), (True, "fused")], ids=["fused", "unfused", "one-launch"])
+def test_cir_intensity_starting_at_zero(fused, plan, hip, oracle, monkeypatch):
     """the reference asserts y0 > 0 (cirpp.py:40), and the one-launch kernel relies on it (no zero test under the diffusion root);
     a C-ABI caller may still hand over a zero start: mcx_fused_create then routes the book to the interpreter kernel, and every
-    plan reproduces sqrt(clamp(0, 0)) = 0 of cirpp.py:194 (same paths and CVA as the CPU oracle)"""
+    plan reproduces sqrt(clamp(0, 0)) = 0 of cirpp.py:194 (same paths and CVA as the CPU oracle).  The default plan streams K1's
+    paths through the interpreter; main_plan="fused" simulates in it, every date straight-line (lean_date), and without outputs
+    takes lean_date's CVA-only branch"""
     from mcx.models.cirpp import CIRPPModel
     monkeypatch.setattr(CIRPPModel, "_initial_state", lambda self: [0.0, 0.0])
     out = {}
     for be in (hip, oracle):
         sc, _ = cases.make_controller("irs_cva", be, inject=False, fused=fused and be is hip)
+        if be is hip:
+            sc.main_plan = plan
         res = sc.run_simulation()
         out[be.name] = (np.array(res.results[0][0][0]), sc.last_state["paths"].cpu().numpy() if be is hip else sc.last_state["paths"].numpy())
+        if be is hip and plan == "fused":
+            d = hip.fused_describe(sc._fused, False, True)
+            assert d["kernel"] == "fused" and not d["lean"] and (d["nns"], d["nst"]) == (1, 0), d
+            assert (d["valid"] == 1).all() and d["max_chunk"] == 0 and d["kernel_npf"] == 0, d
+            sc.materialize = False                 # no outputs: the CVA-only branch of lean_date inside kf_fused
+            out["no_outputs"] = np.array(sc.run_simulation().results[0][0][0])
+            assert sc.last_state["paths"] is None and sc.last_state["expo"] is None
     assert np.all(np.isfinite(out["hip"][1]))
     assert np.allclose(out["hip"][1], out["oracle"][1], rtol=1e-10, atol=1e-13)
     assert np.allclose(out["hip"][0], out["oracle"][0], rtol=1e-8, atol=1e-14), (out["hip"][0], out["oracle"][0])
+    if plan == "fused":
+        assert np.allclose(out["no_outputs"], out["oracle"][0], rtol=1e-8, atol=1e-14), (out["no_outputs"], out["oracle"][0])
 
 
 @pytest.mark.gpu
