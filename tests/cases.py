@@ -6,6 +6,7 @@ import torch
 
 from mcx.common.enums import SimulationScheme
 from mcx.controller.controller import SimulationController
+from mcx.maths.regression import PolyomialRegression
 from mcx.metrics.ce_metric import CEMetric
 from mcx.metrics.cva_metric import CVAMetric
 from mcx.metrics.eepe_metric import EEPEMetric
@@ -213,6 +214,14 @@ def flexicall():
         RiskMetrics([PVMetric(), EPEMetric()], exposure_timeline=tl)
 
 
+def flexicall5():
+    model = BlackScholesModel(0, 100.0, 0.03, 0.25)
+    opts = [EuropeanOption(Equity(), 0.2 * (k + 1), 97.0 + 1.5 * k, OptionType.PUT) for k in range(6)]
+    fc = FlexiCall(opts, 5); fc.name = "flexi5"
+    tl = np.array([0.0, 0.2, 0.4, 0.6, 0.8, 1.0, 1.2])
+    return [NettingSet(name="flexi5", products=[fc])], model, RiskMetrics([PVMetric(), EPEMetric()], exposure_timeline=tl)
+
+
 def _mixed_book_products(mod):
     """every product family of the reference's large-book script (pv_performance_large_netting_set.py:86-233), a few of each;
     `mod` supplies the classes (the reference's modules here, mcx's in tests/cases.py)"""
@@ -303,6 +312,9 @@ CASES = {
     "barrier_euler": (barrier, 0, 2048, 3, E, False),
     "barrier_bridge": (barrier_bridge, 0, 2048, 2, A, False),
     "flexicall": (flexicall, 2048, 1024, 1, A, False),
+    # regression polynomials of other degrees than the default 2 (REGRESSION_DEGREE)
+    "bermudan_swaption_deg3": (bermudan_swaption, 1024, 1024, 1, E, False),
+    "flexicall5_deg1": (flexicall5, 2048, 1024, 1, A, False),
     "mixed_book_multi": (mixed_book_multi, 128, 128, 1, E, False),
     "s2f_european": (s2f_european, 0, 1024, 4, A, False),
     "s2f_european_euler": (s2f_european, 0, 1024, 6, E, False),
@@ -313,6 +325,7 @@ CASES = {
     "bermudan_swaption_aad": (bermudan_swaption, 1024, 1024, 1, E, True),
     "american_put_aad": (american, 2048, 1024, 1, A, True),
 }
+REGRESSION_DEGREE = {"bermudan_swaption_deg3": 3, "flexicall5_deg1": 1}      # PolyomialRegression(degree) of a case; default 2
 DRAWS_FROM = {"irs_cva_aad": "irs_cva", "mixed_cva_aad": "mixed_cva", "bermudan_swaption_aad": "bermudan_swaption",
               "american_put_aad": "american_put"}
 
@@ -324,7 +337,8 @@ def load_golden(name):
 def make_controller(name, backend, inject=True, fused=True):
     build, n_pre, n_main, steps, scheme, diff = CASES[name]
     ns, model, rm = build()
-    sc = SimulationController(ns, model, rm, n_main, n_pre, steps, scheme, differentiate=diff, backend=backend)
+    kw = {"regression_function": PolyomialRegression(degree=REGRESSION_DEGREE[name])} if name in REGRESSION_DEGREE else {}
+    sc = SimulationController(ns, model, rm, n_main, n_pre, steps, scheme, differentiate=diff, backend=backend, **kw)
     sc.materialize = True
     sc.allow_fused = fused
     g = load_golden(name)

@@ -24,6 +24,7 @@ import torch
 from common.enums import SimulationScheme
 from controller.controller import SimulationController
 from engine.engine import MonteCarloEngine
+from maths.regression import PolyomialRegression
 from metrics.ce_metric import CEMetric
 from metrics.cva_metric import CVAMetric
 from metrics.eepe_metric import EEPEMetric
@@ -104,8 +105,9 @@ def npf(x):
     return np.asarray(x)
 
 
-def run_controller_case(name, build, n_pre, n_main, num_steps, scheme, differentiate=False, extra=None):
-    """Run one SimulationController case under the recorder and dump everything."""
+def run_controller_case(name, build, n_pre, n_main, num_steps, scheme, differentiate=False, extra=None, degree=None):
+    """Run one SimulationController case under the recorder and dump everything (degree: of the LSM regression polynomial, the
+    controller's default 2 when None)."""
     netting_sets, model, risk_metrics = build()
     captured = {"paths": [], "eval": []}
 
@@ -129,6 +131,7 @@ def run_controller_case(name, build, n_pre, n_main, num_steps, scheme, different
             netting_sets=netting_sets, model=model, risk_metrics=risk_metrics,
             num_paths_mainsim=n_main, num_paths_presim=n_pre, num_steps=num_steps,
             simulation_scheme=scheme, differentiate=differentiate,
+            **({} if degree is None else {"regression_function": PolyomialRegression(degree=degree)}),
         )
         with DrawRecorder() as rec:
             res = sc.run_simulation()
@@ -498,6 +501,15 @@ def case_flexicall():
         RiskMetrics([PVMetric(), EPEMetric()], exposure_timeline=tl)
 
 
+def case_flexicall5():
+    """a 5-right FlexiCall (6 exercise states) on six puts, exposures via the regression"""
+    model = BlackScholesModel(0, 100.0, 0.03, 0.25)
+    opts = [EuropeanOption(Equity(), 0.2 * (k + 1), 97.0 + 1.5 * k, OptionType.PUT) for k in range(6)]
+    fc = FlexiCall(opts, 5); fc.name = "flexi5"
+    tl = np.array([0.0, 0.2, 0.4, 0.6, 0.8, 1.0, 1.2])
+    return [NettingSet(name="flexi5", products=[fc])], model, RiskMetrics([PVMetric(), EPEMetric()], exposure_timeline=tl)
+
+
 def _mixed_book_products(mod):
     """every product family of the reference's large-book script (pv_performance_large_netting_set.py:86-233), a few of each;
     `mod` supplies the classes (the reference's modules here, mcx's in tests/cases.py)"""
@@ -659,6 +671,10 @@ NEW_CASES = {
                                       slim_to_gradients("bermudan_swaption_aad")),
     "american_put_aad": lambda: (run_controller_case("american_put_aad", case_american, 2048, 1024, 1, SimulationScheme.ANALYTICAL, differentiate=True),
                                  slim_to_gradients("american_put_aad")),
+    # regression polynomials of other degrees than the default 2 (basis sizes K = 4 and K = 2)
+    "bermudan_swaption_deg3": lambda: run_controller_case("bermudan_swaption_deg3", case_bermudan_swaption, 1024, 1024, 1,
+                                                          SimulationScheme.EULER, degree=3),
+    "flexicall5_deg1": lambda: run_controller_case("flexicall5_deg1", case_flexicall5, 2048, 1024, 1, SimulationScheme.ANALYTICAL, degree=1),
     "netting_interp": gen_netting_interp,
     "mc_chol_nofma": gen_mc_chol_nofma,
 }
