@@ -12,6 +12,7 @@
  *   RequestInterface.resolve_requests      request_interface.py:115-130   mcx_resolve_atoms / fused in K2
  *   SimulationController._evaluate_product controller/controller.py:385-471   mcx_eval_book           (K2)
  *   SimulationController._perform_regression_for_product  controller.py:294-383  mcx_lsm_stats, mcx_lsm_step (K3)
+ *   Storage.compute_normalized_cashflows (gas storage)              products/storage.py:219-308   mcx_storage_lsm_run, mcx_storage_eval (K6)
  *   NettingSet.compute_unsecured_exposure_profiles  products/netting_set.py:156-184   (prologue of K4/K5)
  *   Metric._compute_mc_mean_and_error + PV/CE/EPE/ENE/CVA  metrics/<metric>.py   mcx_reduce_vector, mcx_reduce_profiles, mcx_reduce_cva (K4)
  *   PFEMetric.evaluate_numerically (torch.sort)     metrics/pfe_metric.py:49-73       mcx_select_hist  (K5)
@@ -596,6 +597,72 @@ int  mcx_select_bracket(mcx_handle* h, const mcx_unsecured_desc* u, const double
                         void* stream);
 int  mcx_select_hist_rows(mcx_handle* h, const double* d_rows, int32_t n_rows, int64_t ld, const uint64_t* d_row_n,
                           int32_t n_sel, const uint64_t* d_prefix, int32_t shift, int32_t bits, uint64_t* d_hist, void* stream);
+
+/* K6 — gas storage (products/storage.py, controller/controller.py:294-471; csrc/k6_storage.hip).
+ * The storage is the one product whose Longstaff-Schwartz state is REAL-valued: the position s in [0, S-1] of the inventory inside
+ * the volume window of the date, volume = vmin + s * step.  Per action date three candidates [inject, hold, withdraw] lead to
+ * next volumes (rate curves piecewise linear in the volume, flat outside the knots, clamped into the next window), next states
+ * (v - next_vmin) * next_scale and cash -dv * (spot + c_inj) resp. -dv * (spot - c_wd) (hold: by the sign of dv); the value of a
+ * candidate is cash + the date's regression polynomials of the grid states, evaluated at the spot and interpolated linearly at
+ * the candidate's next state (0 on the last date).  The FIRST maximum of [inject, hold, withdraw] wins.  A storage owns no events
+ * of the book program; it reads the book's atoms and reads / writes blocks of the book's coefficient array.
+ *   mcx_storage_date  one action date.  inj_* / wd_*: the knots (ascending) and rates of the two curves, n_* in
+ *                     [1, MCX_STORAGE_MAX_KNOTS]; two knots closer than 1e-8 + 1e-5 |right knot| interpolate with weight 0.
+ *                     coeff_off: the date's [n_states][K] regression block in the book's coefficient array.
+ *   trans             [n_dates][n_states][3][2] = (next state, dv) of the INTEGER states under the three candidates (host
+ *                     arithmetic): in the backward roll every path starts from the integer states, so only the spot varies. */
+#define MCX_STORAGE_MAX_STATES 32
+#define MCX_STORAGE_MAX_KNOTS  8
+typedef struct {
+    double  vmin, step;                         /* window of the action date                                              */
+    double  next_vmin, next_vmax, next_scale;   /* window of the next date; next_scale = 0: the window is one point        */
+    double  period, c_inj, c_wd;
+    double  inj_x[MCX_STORAGE_MAX_KNOTS], inj_r[MCX_STORAGE_MAX_KNOTS];
+    double  wd_x[MCX_STORAGE_MAX_KNOTS], wd_r[MCX_STORAGE_MAX_KNOTS];
+    int64_t coeff_off;
+    int32_t n_inj, n_wd;
+    int32_t num_atom, x_atom;                   /* numeraire and spot of the action date (atoms of the book)               */
+    int32_t is_last, reserved;                  /* is_last: the next date is the end date, continuation 0                   */
+} mcx_storage_date;
+typedef struct {
+    int32_t n_states, n_dates, netting_set, reserved;
+    const mcx_storage_date* dates;              /* [n_dates]                                                               */
+    const double* trans;                        /* [n_dates][n_states][3][2]                                               */
+} mcx_storage_desc;
+typedef struct mcx_storage mcx_storage;
+int  mcx_storage_create(mcx_handle* h, const mcx_book* book, const mcx_storage_desc* desc, mcx_storage** out);
+void mcx_storage_destroy(mcx_storage* st);
+/* One date of the backward induction.  roll_date >= 0: W_new[s] = cash_s / numeraire + lerp(W_old, next state) for every integer
+ * start state s along the policy of action date roll_date (MCX_LSM_F32_CACHE: the cash term is rounded to float32 first, the
+ * reference's float32 step buffer, controller.py:330-351), moments from W_new; roll_date < 0: moments from W_old, d_W_new is not
+ * touched.  Moments as mcx_lsm_step: d_moments[k] = sum z^k, d_moments[2K-1 + s*K + k] = sum z^k numeraire(num_atom) W[s],
+ * z = (x_atom - shift) * scale.  d_W_old / d_W_new: [n_states][ld_w], distinct buffers (W_new[s] reads all of W_old). */
+int  mcx_storage_lsm_step(mcx_handle* h, const mcx_book* book, const mcx_storage* st, int32_t roll_date, int32_t num_atom,
+                          int32_t x_atom, double shift, double scale, const double* d_paths, int64_t n_paths, int64_t ld,
+                          const double* d_W_old, double* d_W_new, int64_t ld_w, double* d_moments, int32_t flags, void* stream);
+/* The whole backward induction of one storage, enqueued back to back: step, (all-reduce with a communicator on the handle), the
+ * K x K solve with n_states right-hand sides and the coefficient scatter, per date of h_dates in order; one synchronisation at the
+ * end.  d_W: [2][n_states][ld_w], zeroed by the caller (the two halves alternate).  h_coeffs [n_dates][n_states][K],
+ * h_status[d] != 0: numerically singular, coefficients of that date not written (as mcx_lsm_run). */
+typedef struct {
+    int32_t roll_date, num_atom, x_atom, degenerate;
+    int64_t coeff_off[2];
+    double  shift, scale, x0;
+} mcx_storage_lsm_date;
+int  mcx_storage_lsm_run(mcx_handle* h, mcx_book* book, const mcx_storage* st, const mcx_storage_lsm_date* h_dates, int32_t n_dates,
+                         const double* d_paths, int64_t n_paths, int64_t ld, double* d_W, int64_t ld_w,
+                         double* h_coeffs, int32_t* h_status, int32_t flags, void* stream);
+/* Main simulation: the realised state of every path walked through h_ops in order.  kind 0: action date `index` (cash / numeraire
+ * ADDED to d_cfs[netting_set] when d_cfs is given); kind 1: exposure row `index` — the [n_states][K] block at coeff_off evaluated at
+ * x_atom, interpolated at the realised state, divided by num_atom, ADDED to d_expo[netting_set][index] (controller.py:414-461).
+ * d_cfs [n_netting_sets][ld_out], d_expo [n_netting_sets][n_expo_rows][ld_out] as written by mcx_eval_book before. */
+typedef struct {
+    int32_t kind, index, num_atom, x_atom;
+    int64_t coeff_off;
+} mcx_storage_op;
+int  mcx_storage_eval(mcx_handle* h, const mcx_book* book, const mcx_storage* st, const mcx_storage_op* h_ops, int32_t n_ops,
+                      const double* d_paths, int64_t n_paths, int64_t ld, double* d_cfs, double* d_expo, int64_t ld_out,
+                      void* stream);
 
 /* Multi-GPU exchange (paths shard over the GPUs of a node, one process per GPU; the only data that crosses
  * GPUs are accumulator records, LSM moments and select histograms).  RCCL over xGMI, loaded at run time (librccl.so.1 — the

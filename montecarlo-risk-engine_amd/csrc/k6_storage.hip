@@ -1,0 +1,577 @@
+// k6_storage.hip — K6: the gas storage (products/storage.py of the reference; include/mcx.h "K6 — gas storage").
+//
+// The storage's Longstaff-Schwartz state is a real number s in [0, S-1] (position of the inventory in the volume window of the
+// date), so neither the exercise machine of k3_lsm.hip (integer states, one decision bit) nor the event program of k2_book.hip
+// fits.  Three kernels:
+//   k6_step          one backward date: every path rolls ALL S integer start states one action date forward (the next states and
+//                    volume changes of integer states are path-independent: the host's transition table, scalar loads), writes
+//                    W_new[s] = cash / numeraire + lerp(W_old, next state) and accumulates the moments of the regression.
+//                    One path per lane; a moment is reduced over the wave as soon as it is formed (S*K of them do not fit in
+//                    registers), lane 0 of each wave adds it to the wave's LDS row, one barrier at the end.
+//   k6_finish_solve  sums the per-block partials and solves the K x K normal equations for S right-hand sides, lane s taking
+//                    state s (same algorithm as k3_solve_t: LU with partial pivoting, back-transformation of the shifted /
+//                    scaled basis, minimum-norm solution of the exactly rank-1 system of the calibration date).
+//   k6_eval          main simulation: the realised state of a path in a register, walked through the action dates and the
+//                    exposure rows; the date record and its [S][K] coefficient block are staged in LDS once per block and date.
+// Exact ties between candidates are the rule (a full store: inject == hold): every candidate goes through ONE inline function,
+// so tied candidates are bit-identical, and the first of [inject, hold, withdraw] wins as torch.argmax does.
+#include "mcx_internal.h"
+
+#define K6_MAX_S MCX_STORAGE_MAX_STATES
+#define K6_MAX_KNOTS MCX_STORAGE_MAX_KNOTS
+
+struct K6Date {                 // device image of mcx_storage_date, atoms flattened
+    double vmin, step, nvmin, nvmax, nscale, period, c_inj, c_wd;
+    double inj_x[K6_MAX_KNOTS], inj_r[K6_MAX_KNOTS], wd_x[K6_MAX_KNOTS], wd_r[K6_MAX_KNOTS];
+    DevAtom num, x;
+    int64_t coeff_off;
+    int32_t n_inj, n_wd, is_last, pad;
+};
+static_assert(sizeof(K6Date) % 8 == 0, "copied to LDS in dwords");
+
+struct mcx_storage {
+    int n_states, n_dates, netting_set, n_basis;
+    int64_t n_coeffs;           // of the book the storage was created on
+    K6Date* d_dates;
+    double* d_trans;            // [n_dates][S][3][2]
+    std::vector<K6Date> h_dates;
+};
+
+namespace {
+
+template <int K>
+__device__ __forceinline__ double k6_poly(const double* __restrict__ c, double x)
+{
+    double v = 0.0, xp = 1.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { v = fma(c[k], xp, v); xp *= x; }
+    return v;
+}
+// the same with a wave-uniform coefficient row (scalar loads)
+template <int K>
+__device__ __forceinline__ double k6_poly_uniform(const double* __restrict__ c, double x)
+{
+    double v = 0.0, xp = 1.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { v = fma(ldk(c + k), xp, v); xp *= x; }
+    return v;
+}
+
+// piecewise-linear rate at volume v (storage_helpers.py interpolate_rate_tensor): segment = the last knot below v, clamped to
+// the first / last segment; weight 0 where the segment's knots coincide under torch.isclose; flat outside the knots.  The knots
+// are wave-uniform, v is per lane: selects, no dynamic indexing.
+__device__ __forceinline__ double k6_rate(const double* __restrict__ xs, const double* __restrict__ rs, int n, double v)
+{
+    if (n == 1) return rs[0];
+    double x0 = xs[0], x1 = xs[1], y0 = rs[0], y1 = rs[1];
+    for (int j = 1; j < n - 1; ++j) {
+        const bool m = xs[j] < v;
+        x0 = m ? xs[j] : x0; x1 = m ? xs[j + 1] : x1;
+        y0 = m ? rs[j] : y0; y1 = m ? rs[j + 1] : y1;
+    }
+    const bool close = fabs(x0 - x1) <= 1e-8 + 1e-5 * fabs(x1);
+    const double w = close ? 0.0 : (v - x0) / (x1 - x0);
+    double r = y0 + w * (y1 - y0);
+    r = v <= xs[0] ? rs[0] : r;
+    r = v >= xs[n - 1] ? rs[n - 1] : r;
+    return r;
+}
+
+// ---- backward step ---------------------------------------------------------------------------------------------------
+struct K6StepArgs {
+    const double* __restrict__ paths;
+    const double* __restrict__ W_old;
+    double* __restrict__ W_new;
+    double* __restrict__ partials;         // [gridDim.x][NM]
+    const double* __restrict__ coeffs;     // [S][K] block of the rolled date (unused when is_last)
+    const double* __restrict__ trans;      // [S][3][2] of the rolled date
+    DevAtom num, x;                        // regression date
+    DevAtom rnum, rx;                      // rolled action date
+    double shift, scale, c_inj, c_wd;
+    int64_t n, ld, ld_w;
+    int32_t S, n_state, roll, is_last, f32_cache;
+};
+
+// one candidate of an integer start state: (next state, dv) wave-uniform, the price per lane.  -> cash, value, cached tail
+template <int K>
+__device__ __forceinline__ void k6_step_candidate(const K6StepArgs& a, double ns, double dv, double price, double spot, int64_t i,
+                                                  double& cash, double& value, double& tail)
+{
+    const double b = fmin(fmax(ns, 0.0), (double)(a.S - 1));
+    const double fl = floor(b), w = b - fl;
+    const int lo = (int)fl, hi = (int)ceil(b);
+    double cont = 0.0;
+    if (!a.is_last) {
+        const double g_lo = k6_poly_uniform<K>(a.coeffs + lo * K, spot);
+        const double g_hi = hi != lo ? k6_poly_uniform<K>(a.coeffs + hi * K, spot) : g_lo;
+        cont = g_lo + w * (g_hi - g_lo);
+    }
+    const double w_lo = a.W_old[(int64_t)lo * a.ld_w + i];
+    const double w_hi = hi != lo ? a.W_old[(int64_t)hi * a.ld_w + i] : w_lo;
+    tail = w_lo + w * (w_hi - w_lo);
+    cash = -dv * price;
+    value = cash + cont;
+}
+
+template <int K>
+__global__ __launch_bounds__(MCX_BLOCK) void k6_step(const K6StepArgs a)
+{
+    constexpr int NB = 2 * K - 1;
+    __shared__ double rows[4][NB + K6_MAX_S * K];
+    const int NM = NB + a.S * K;
+    const int lane = threadIdx.x & (MCX_WAVE - 1), wv = threadIdx.x >> 6;
+    for (int q = lane; q < NM; q += MCX_WAVE) rows[wv][q] = 0.0;       // (each wave owns its row: no barrier needed before use)
+    const int64_t D = a.n_state;
+    for (int64_t base = (int64_t)blockIdx.x * MCX_BLOCK; base < a.n; base += (int64_t)gridDim.x * MCX_BLOCK) {
+        const int64_t i_raw = base + threadIdx.x;
+        const bool live = i_raw < a.n;
+        const int64_t i = live ? i_raw : a.n - 1;                       // idle lanes read a valid path and contribute zero
+        const double num = dev_atom(a.num, a.paths, D, a.ld, i);
+        const double z = (dev_atom(a.x, a.paths, D, a.ld, i) - a.shift) * a.scale;
+        double zp = 1.0;
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const double r = wave_sum(live ? zp : 0.0);
+            if (lane == 0) rows[wv][k] += r;
+            zp *= z;
+        }
+        double spot = 0.0, rnum = 1.0;
+        if (a.roll) { spot = dev_atom(a.rx, a.paths, D, a.ld, i); rnum = dev_atom(a.rnum, a.paths, D, a.ld, i); }
+        const double p_inj = spot + a.c_inj, p_wd = spot - a.c_wd;
+        for (int s = 0; s < a.S; ++s) {
+            double w;
+            if (a.roll) {
+                const double* __restrict__ t = a.trans + s * 6;
+                const double ns0 = ldk(t + 0), dv0 = ldk(t + 1), ns1 = ldk(t + 2), dv1 = ldk(t + 3), ns2 = ldk(t + 4), dv2 = ldk(t + 5);
+                double c0, v0, t0, c1, v1, t1, c2, v2, t2;
+                k6_step_candidate<K>(a, ns0, dv0, p_inj, spot, i, c0, v0, t0);                          // inject
+                k6_step_candidate<K>(a, ns1, dv1, dv1 >= 0.0 ? p_inj : p_wd, spot, i, c1, v1, t1);      // hold
+                k6_step_candidate<K>(a, ns2, dv2, p_wd, spot, i, c2, v2, t2);                          // withdraw
+                double cb = c0, vb = v0, tb = t0;                          // the first maximum wins (torch.argmax)
+                if (v1 > vb) { cb = c1; vb = v1; tb = t1; }
+                if (v2 > vb) { cb = c2; vb = v2; tb = t2; }
+                double c = cb / rnum;
+                if (a.f32_cache) c = (double)(float)c;                     // float32 step buffer (controller.py:330, 341)
+                w = c + tb;
+                if (live) a.W_new[(int64_t)s * a.ld_w + i] = w;
+            } else {
+                w = a.W_old[(int64_t)s * a.ld_w + i];
+            }
+            const double y = num * w;
+            zp = 1.0;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const double r = wave_sum(live ? zp * y : 0.0);
+                if (lane == 0) rows[wv][NB + s * K + k] += r;
+                zp *= z;
+            }
+        }
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < NM; q += MCX_BLOCK)
+        a.partials[(int64_t)blockIdx.x * NM + q] = (rows[0][q] + rows[1][q]) + (rows[2][q] + rows[3][q]);
+}
+
+// ---- solve -----------------------------------------------------------------------------------------------------------
+struct K6Solve {
+    double shift, scale, x0;
+    int64_t off0, off1;
+    int32_t degenerate, S, date, pad;
+};
+
+// right-hand side s of the K x K system in m[] (k3_solve_t for one state; every lane factorises the same Gram matrix in registers)
+template <int K>
+__device__ __forceinline__ void k6_solve_state(const double* __restrict__ m, const K6Solve& q, int s, double* __restrict__ coeffs,
+                                               double* __restrict__ table, int32_t* __restrict__ status)
+{
+    double out[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) out[k] = 0.0;
+    const double n = m[0];
+    int st = 0;
+    if (n > 0.0 && q.degenerate) {
+        double v[K], vv = 0.0, xp = 1.0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) { v[k] = xp; vv += xp * xp; xp *= q.x0; }
+        const double mean_y = m[(2 * K - 1) + s * K] / n;
+#pragma unroll
+        for (int k = 0; k < K; ++k) out[k] = v[k] * (mean_y / vv);
+    } else if (n > 0.0) {
+        double G[K][K], B[K];
+        double gmax = 0.0;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+#pragma unroll
+            for (int k = 0; k < K; ++k) { G[j][k] = m[j + k]; gmax = fmax(gmax, fabs(G[j][k])); }
+#pragma unroll
+        for (int k = 0; k < K; ++k) B[k] = m[(2 * K - 1) + s * K + k];
+#pragma unroll
+        for (int c = 0; c < K; ++c) {                                  // LU, partial pivoting by conditional row swaps
+#pragma unroll
+            for (int r = c + 1; r < K; ++r) {
+                const bool sw = fabs(G[r][c]) > fabs(G[c][c]);
+#pragma unroll
+                for (int k = 0; k < K; ++k) { const double x = G[c][k], y = G[r][k]; G[c][k] = sw ? y : x; G[r][k] = sw ? x : y; }
+                { const double x = B[c], y = B[r]; B[c] = sw ? y : x; B[r] = sw ? x : y; }
+            }
+            if (!(fabs(G[c][c]) > 1e-14 * gmax)) st = 1;               // numerically singular: reported, not written
+            const double piv = st ? 1.0 : G[c][c];
+#pragma unroll
+            for (int r = c + 1; r < K; ++r) {
+                const double f = G[r][c] / piv;
+#pragma unroll
+                for (int k = c + 1; k < K; ++k) G[r][k] -= f * G[c][k];
+                B[r] -= f * B[c];
+            }
+        }
+        if (st == 0) {
+#pragma unroll
+            for (int c = K - 1; c >= 0; --c) {
+                double acc = B[c];
+#pragma unroll
+                for (int k = c + 1; k < K; ++k) acc -= G[c][k] * B[k];
+                B[c] = acc / G[c][c];
+            }
+            double sp = 1.0;                                           // coefficient of x^j in z^k = scale^k C(k, j) (-shift)^(k-j)
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                double binom = 1.0;
+#pragma unroll
+                for (int j = 0; j <= k; ++j) {
+                    double ms = 1.0;
+                    for (int e = 0; e < k - j; ++e) ms *= -q.shift;
+                    out[j] += sp * binom * ms * B[k];
+                    binom = binom * (double)(k - j) / (double)(j + 1);
+                }
+                sp *= q.scale;
+            }
+        }
+    }
+    if (s == 0) status[q.date] = st;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (table) table[((int64_t)q.date * q.S + s) * K + k] = out[k];
+        if (st == 0) {
+            if (q.off0 >= 0) coeffs[q.off0 + s * K + k] = out[k];
+            if (q.off1 >= 0) coeffs[q.off1 + s * K + k] = out[k];
+        }
+    }
+}
+
+// n_blocks > 0: wave q of the block sums moment q over the step kernel's partials (fixed order) into LDS and mom_out;
+// n_blocks == 0: the moments are read from mom_out (all-reduced by the caller).  do_solve: lane s < S then solves state s.
+template <int K>
+__global__ __launch_bounds__(1024) void k6_finish_solve(const double* __restrict__ partials, int n_blocks, double* __restrict__ mom_out,
+                                                        int do_solve, const K6Solve q, double* __restrict__ coeffs,
+                                                        double* __restrict__ table, int32_t* __restrict__ status)
+{
+    __shared__ double m[(2 * K - 1) + K6_MAX_S * K];
+    const int nm = (2 * K - 1) + q.S * K;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (n_blocks > 0) {
+        for (int j = wv; j < nm; j += 16) {
+            double s = 0.0;
+            for (int b = lane; b < n_blocks; b += MCX_WAVE) s += partials[(int64_t)b * nm + j];
+            s = wave_sum(s);
+            if (lane == 0) { m[j] = s; mom_out[j] = s; }
+        }
+    } else {
+        for (int j = threadIdx.x; j < nm; j += 1024) m[j] = mom_out[j];
+    }
+    __syncthreads();
+    if (do_solve && (int)threadIdx.x < q.S) k6_solve_state<K>(m, q, threadIdx.x, coeffs, table, status);
+}
+
+// ---- main simulation -------------------------------------------------------------------------------------------------
+struct K6EvalArgs {
+    const double* __restrict__ paths;
+    const K6Date* __restrict__ dates;
+    const mcx_storage_op* __restrict__ ops;
+    const DevAtom* __restrict__ atoms;
+    const double* __restrict__ coeffs;
+    double* __restrict__ cfs;              // the netting set's row or nullptr
+    double* __restrict__ expo;             // the netting set's [n_expo_rows][ld_out] block or nullptr
+    int64_t n, ld, ld_out;
+    int32_t n_ops, S, n_state, pad;
+};
+
+// polynomial grid of the staged coefficient block interpolated at a per-lane state
+template <int K>
+__device__ __forceinline__ double k6_lerp_grid(const double* __restrict__ sc, int S, double state, double x)
+{
+    const double b = fmin(fmax(state, 0.0), (double)(S - 1));
+    const double fl = floor(b), w = b - fl;
+    const int lo = (int)fl, hi = (int)ceil(b);
+    const double g_lo = k6_poly<K>(sc + lo * K, x), g_hi = k6_poly<K>(sc + hi * K, x);
+    return g_lo + w * (g_hi - g_lo);
+}
+
+// one candidate of the realised state: next volume nv from volume v at `price`
+template <int K>
+__device__ __forceinline__ void k6_eval_candidate(const K6Date& d, const double* __restrict__ sc, int S, double nv, double v, double price,
+                                                  double spot, double& ns, double& cash, double& value)
+{
+    ns = d.nscale == 0.0 ? 0.0 : (nv - d.nvmin) * d.nscale;
+    cash = -(nv - v) * price;
+    value = cash + (d.is_last ? 0.0 : k6_lerp_grid<K>(sc, S, ns, spot));
+}
+
+template <int K>
+__global__ __launch_bounds__(MCX_BLOCK) void k6_eval(const K6EvalArgs a)
+{
+    __shared__ K6Date sd;
+    __shared__ double sc[K6_MAX_S * K];
+    const int64_t i_raw = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x;
+    const bool live = i_raw < a.n;
+    const int64_t i = live ? i_raw : a.n - 1;
+    const int64_t D = a.n_state;
+    double state = 0.0, cf = 0.0;                                       // get_initial_state() = 0.0
+    for (int op = 0; op < a.n_ops; ++op) {
+        const mcx_storage_op o = ldk_struct(a.ops + op);
+        __syncthreads();                                                // the previous op's readers are done with sd / sc
+        int64_t off = o.coeff_off;
+        bool need_coeffs = true;
+        if (o.kind == 0) {
+            const uint32_t* __restrict__ src = (const uint32_t*)(a.dates + o.index);
+            for (int q = threadIdx.x; q < (int)(sizeof(K6Date) / 4); q += MCX_BLOCK) ((uint32_t*)&sd)[q] = src[q];
+            off = ldk(&a.dates[o.index].coeff_off);
+            need_coeffs = ldk(&a.dates[o.index].is_last) == 0;
+        }
+        if (need_coeffs)
+            for (int q = threadIdx.x; q < a.S * K; q += MCX_BLOCK) sc[q] = a.coeffs[off + q];
+        __syncthreads();
+        if (o.kind == 0) {
+            const double spot = dev_atom(sd.x, a.paths, D, a.ld, i), num = dev_atom(sd.num, a.paths, D, a.ld, i);
+            const double v = sd.vmin + state * sd.step;
+            const double r_inj = k6_rate(sd.inj_x, sd.inj_r, sd.n_inj, v), r_wd = k6_rate(sd.wd_x, sd.wd_r, sd.n_wd, v);
+            const double nv0 = fmin(v + r_inj * sd.period, sd.nvmax);
+            const double nv1 = fmin(fmax(v, sd.nvmin), sd.nvmax);
+            const double nv2 = fmax(v - r_wd * sd.period, sd.nvmin);
+            const double p_inj = spot + sd.c_inj, p_wd = spot - sd.c_wd;
+            double s0, c0, v0, s1, c1, v1, s2, c2, v2;
+            k6_eval_candidate<K>(sd, sc, a.S, nv0, v, p_inj, spot, s0, c0, v0);                              // inject
+            k6_eval_candidate<K>(sd, sc, a.S, nv1, v, (nv1 - v) >= 0.0 ? p_inj : p_wd, spot, s1, c1, v1);    // hold
+            k6_eval_candidate<K>(sd, sc, a.S, nv2, v, p_wd, spot, s2, c2, v2);                              // withdraw
+            double sb = s0, cb = c0, vb = v0;                           // the first maximum wins (torch.argmax)
+            if (v1 > vb) { sb = s1; cb = c1; vb = v1; }
+            if (v2 > vb) { sb = s2; cb = c2; vb = v2; }
+            state = sb;
+            cf += cb / num;
+        } else {
+            const DevAtom an = ldk_struct(a.atoms + o.num_atom), ax = ldk_struct(a.atoms + o.x_atom);
+            const double x = dev_atom(ax, a.paths, D, a.ld, i), num = dev_atom(an, a.paths, D, a.ld, i);
+            const double e = k6_lerp_grid<K>(sc, a.S, state, x) / num;
+            if (live && a.expo) a.expo[(int64_t)o.index * a.ld_out + i] += e;
+        }
+    }
+    if (live && a.cfs) a.cfs[i] += cf;
+}
+
+#define K6_DISPATCH(K, CALL)                                          \
+    switch (K) {                                                      \
+    case 1: { constexpr int KK = 1; CALL; } break;                    \
+    case 2: { constexpr int KK = 2; CALL; } break;                    \
+    case 3: { constexpr int KK = 3; CALL; } break;                    \
+    case 4: { constexpr int KK = 4; CALL; } break;                    \
+    case 5: { constexpr int KK = 5; CALL; } break;                    \
+    case 6: { constexpr int KK = 6; CALL; } break;                    \
+    default: break;                                                   \
+    }
+
+DevAtom k6_flat(const mcx_atom& q)
+{
+    DevAtom o;
+    o.t_idx = q.t_idx; o.col = q.col; o.a = q.a; o.d = q.d; o.b = q.b; o.c0 = q.c0; o.c1 = q.c1;
+    return o;
+}
+
+// step of one date on the stream: per-block partials in h->d_ws, *grid_out blocks (0: no paths)
+int k6_step_launch(mcx_handle* h, const mcx_book* b, const mcx_storage* st, int32_t roll_date, int32_t num_atom, int32_t x_atom,
+                   double shift, double scale, const double* d_paths, int64_t n_paths, int64_t ld, const double* d_W_old,
+                   double* d_W_new, int64_t ld_w, int32_t flags, hipStream_t s, const char* who, int* grid_out)
+{
+    if (st->n_basis != b->n_basis || st->n_coeffs != b->n_coeffs) MCX_FAIL(h, -2, "%s: the storage was created on another book", who);
+    if (roll_date >= st->n_dates) MCX_FAIL(h, -2, "%s: roll date out of range", who);
+    if (num_atom < 0 || num_atom >= b->n_atoms || x_atom < 0 || x_atom >= b->n_atoms) MCX_FAIL(h, -2, "%s: atom out of range", who);
+    if (ld < n_paths || ld_w < n_paths) MCX_FAIL(h, -2, "%s: leading dimension < n_paths", who);
+    if (roll_date >= 0 && (!d_W_new || d_W_new == d_W_old)) MCX_FAIL(h, -2, "%s: a roll needs a second cache buffer", who);
+    const int K = st->n_basis, S = st->n_states, NM = (2 * K - 1) + S * K;
+    *grid_out = 0;
+    if (n_paths <= 0) return 0;
+    const int grid = mcx_grid_for(n_paths, MCX_BLOCK, 4 * h->n_cu);
+    if ((size_t)grid * NM * sizeof(double) > h->ws_bytes) MCX_FAIL(h, -2, "%s: workspace too small", who);
+    K6StepArgs a;
+    a.paths = d_paths; a.W_old = d_W_old; a.W_new = d_W_new; a.partials = h->d_ws;
+    a.num = k6_flat(b->h_atoms[num_atom]); a.x = k6_flat(b->h_atoms[x_atom]);
+    a.shift = shift; a.scale = scale; a.n = n_paths; a.ld = ld; a.ld_w = ld_w; a.S = S; a.n_state = b->n_state;
+    a.f32_cache = (flags & MCX_LSM_F32_CACHE) ? 1 : 0;
+    a.roll = roll_date >= 0;
+    a.coeffs = b->d_coeffs; a.trans = st->d_trans; a.rnum = a.num; a.rx = a.x; a.c_inj = a.c_wd = 0.0; a.is_last = 1;
+    if (a.roll) {
+        const K6Date& d = st->h_dates[roll_date];
+        a.coeffs = b->d_coeffs + d.coeff_off; a.trans = st->d_trans + (size_t)roll_date * S * 6;
+        a.rnum = d.num; a.rx = d.x; a.c_inj = d.c_inj; a.c_wd = d.c_wd; a.is_last = d.is_last;
+    }
+    K6_DISPATCH(K, hipLaunchKernelGGL((k6_step<KK>), dim3(grid), dim3(MCX_BLOCK), 0, s, a));
+    MCX_HIP(h, hipGetLastError());
+    *grid_out = grid;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int mcx_storage_create(mcx_handle* h, const mcx_book* b, const mcx_storage_desc* d, mcx_storage** out)
+{
+    if (!h || !b || !d || !out || !d->dates || !d->trans) return -1;
+    const int S = d->n_states, K = b->n_basis;
+    if (S < 2 || S > MCX_STORAGE_MAX_STATES) MCX_FAIL(h, -2, "mcx_storage_create: n_states %d outside [2, %d]", S, MCX_STORAGE_MAX_STATES);
+    if (d->n_dates < 1) MCX_FAIL(h, -2, "mcx_storage_create: no action dates");
+    if (d->netting_set < 0 || d->netting_set >= b->n_netting_sets) MCX_FAIL(h, -2, "mcx_storage_create: netting set out of range");
+    std::vector<K6Date> dates((size_t)d->n_dates);
+    for (int j = 0; j < d->n_dates; ++j) {
+        const mcx_storage_date& q = d->dates[j];
+        if (q.n_inj < 1 || q.n_inj > MCX_STORAGE_MAX_KNOTS || q.n_wd < 1 || q.n_wd > MCX_STORAGE_MAX_KNOTS)
+            MCX_FAIL(h, -3, "mcx_storage_create: date %d: knot count outside [1, %d]", j, MCX_STORAGE_MAX_KNOTS);
+        if (q.num_atom < 0 || q.num_atom >= b->n_atoms || q.x_atom < 0 || q.x_atom >= b->n_atoms)
+            MCX_FAIL(h, -3, "mcx_storage_create: date %d: atom out of range", j);
+        if (q.coeff_off < 0 || q.coeff_off + (int64_t)S * K > b->n_coeffs)
+            MCX_FAIL(h, -3, "mcx_storage_create: date %d: coefficient block out of range", j);
+        K6Date& o = dates[j];
+        memset(&o, 0, sizeof(o));
+        o.vmin = q.vmin; o.step = q.step; o.nvmin = q.next_vmin; o.nvmax = q.next_vmax; o.nscale = q.next_scale;
+        o.period = q.period; o.c_inj = q.c_inj; o.c_wd = q.c_wd;
+        memcpy(o.inj_x, q.inj_x, sizeof(o.inj_x)); memcpy(o.inj_r, q.inj_r, sizeof(o.inj_r));
+        memcpy(o.wd_x, q.wd_x, sizeof(o.wd_x)); memcpy(o.wd_r, q.wd_r, sizeof(o.wd_r));
+        o.num = k6_flat(b->h_atoms[q.num_atom]); o.x = k6_flat(b->h_atoms[q.x_atom]);
+        o.coeff_off = q.coeff_off; o.n_inj = q.n_inj; o.n_wd = q.n_wd; o.is_last = q.is_last ? 1 : 0;
+    }
+    MCX_HIP(h, hipSetDevice(h->device));
+    mcx_storage* st = new mcx_storage();
+    st->n_states = S; st->n_dates = d->n_dates; st->netting_set = d->netting_set; st->n_basis = K; st->n_coeffs = b->n_coeffs;
+    st->d_dates = nullptr; st->d_trans = nullptr;
+    st->h_dates = dates;
+    const size_t db = sizeof(K6Date) * dates.size(), tb = sizeof(double) * (size_t)d->n_dates * S * 6;
+    if (hipMalloc((void**)&st->d_dates, db) != hipSuccess || hipMalloc((void**)&st->d_trans, tb) != hipSuccess ||
+        hipMemcpy(st->d_dates, dates.data(), db, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(st->d_trans, d->trans, tb, hipMemcpyHostToDevice) != hipSuccess) {
+        mcx_storage_destroy(st);
+        MCX_FAIL(h, -100, "mcx_storage_create: device allocation / upload failed");
+    }
+    *out = st;
+    return 0;
+}
+
+extern "C" void mcx_storage_destroy(mcx_storage* st)
+{
+    if (!st) return;
+    hipFree(st->d_dates);
+    hipFree(st->d_trans);
+    delete st;
+}
+
+extern "C" int mcx_storage_lsm_step(mcx_handle* h, const mcx_book* b, const mcx_storage* st, int32_t roll_date, int32_t num_atom,
+                                    int32_t x_atom, double shift, double scale, const double* d_paths, int64_t n_paths, int64_t ld,
+                                    const double* d_W_old, double* d_W_new, int64_t ld_w, double* d_moments, int32_t flags, void* stream)
+{
+    if (!h || !b || !st || !d_paths || !d_W_old || !d_moments) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    const int K = st->n_basis, NM = (2 * K - 1) + st->n_states * K;
+    int grid = 0;
+    const int rc = k6_step_launch(h, b, st, roll_date, num_atom, x_atom, shift, scale, d_paths, n_paths, ld, d_W_old, d_W_new, ld_w,
+                                  flags, s, "mcx_storage_lsm_step", &grid);
+    if (rc != 0) return rc;
+    if (grid == 0) { MCX_HIP(h, hipMemsetAsync(d_moments, 0, sizeof(double) * NM, s)); return 0; }
+    K6Solve sv;
+    memset(&sv, 0, sizeof(sv));
+    sv.S = st->n_states;
+    K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve<KK>), dim3(1), dim3(1024), 0, s, h->d_ws, grid, d_moments, 0, sv,
+                                      (double*)nullptr, (double*)nullptr, (int32_t*)nullptr));
+    MCX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+extern "C" int mcx_storage_lsm_run(mcx_handle* h, mcx_book* b, const mcx_storage* st, const mcx_storage_lsm_date* h_dates, int32_t n_dates,
+                                   const double* d_paths, int64_t n_paths, int64_t ld, double* d_W, int64_t ld_w,
+                                   double* h_coeffs, int32_t* h_status, int32_t flags, void* stream)
+{
+    if (!h || !b || !st || !h_dates || !d_paths || !d_W || !h_coeffs || !h_status) return -1;
+    if (n_dates <= 0) return 0;
+    const int K = st->n_basis, S = st->n_states, NM = (2 * K - 1) + S * K;
+    for (int d = 0; d < n_dates; ++d)
+        for (int w = 0; w < 2; ++w)
+            if (h_dates[d].coeff_off[w] >= 0 && h_dates[d].coeff_off[w] + (int64_t)S * K > b->n_coeffs)
+                MCX_FAIL(h, -2, "mcx_storage_lsm_run: date %d coefficient offset out of range", d);
+    const size_t tab_bytes = sizeof(double) * (size_t)n_dates * S * K, st_bytes = sizeof(int32_t) * (size_t)n_dates;
+    hipStream_t s = (hipStream_t)stream;
+    double* d_ws = (double*)mcx_scratch(h, 1, sizeof(double) * NM + tab_bytes + st_bytes + 64);
+    if (!d_ws) return -100;
+    double* d_mom = d_ws;
+    double* d_tab = d_ws + NM;
+    int32_t* d_st = (int32_t*)(d_tab + (size_t)n_dates * S * K);
+    const bool multi = h->comm && h->comm_ranks > 1;
+    int cur = 0, rc = 0;
+    for (int d = 0; d < n_dates && rc == 0; ++d) {
+        const mcx_storage_lsm_date& q = h_dates[d];
+        double* W_old = d_W + (size_t)cur * S * ld_w;
+        double* W_new = d_W + (size_t)(1 - cur) * S * ld_w;
+        int grid = 0;
+        rc = k6_step_launch(h, b, st, q.roll_date, q.num_atom, q.x_atom, q.shift, q.scale, d_paths, n_paths, ld, W_old, W_new, ld_w,
+                            flags, s, "mcx_storage_lsm_run", &grid);
+        if (rc != 0) break;
+        if (q.roll_date >= 0) cur = 1 - cur;
+        K6Solve sv;
+        sv.shift = q.shift; sv.scale = q.scale; sv.x0 = q.x0; sv.off0 = q.coeff_off[0]; sv.off1 = q.coeff_off[1];
+        sv.degenerate = q.degenerate; sv.S = S; sv.date = d; sv.pad = 0;
+        if (grid == 0 && hipMemsetAsync(d_mom, 0, sizeof(double) * NM, s) != hipSuccess) { h->err = "mcx_storage_lsm_run: memset failed"; rc = -100; break; }
+        if (multi || grid == 0) {
+            if (grid > 0) K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve<KK>), dim3(1), dim3(1024), 0, s, h->d_ws, grid, d_mom, 0, sv,
+                                                           b->d_coeffs, d_tab, d_st));
+            if (multi) { rc = mcx_allreduce_f64(h, d_mom, NM, stream); if (rc != 0) break; }     // stream-ordered
+            K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve<KK>), dim3(1), dim3(1024), 0, s, (const double*)nullptr, 0, d_mom, 1, sv,
+                                              b->d_coeffs, d_tab, d_st));
+        } else {
+            K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve<KK>), dim3(1), dim3(1024), 0, s, h->d_ws, grid, d_mom, 1, sv,
+                                              b->d_coeffs, d_tab, d_st));
+        }
+        if (hipGetLastError() != hipSuccess) { h->err = "mcx_storage_lsm_run: launch failed"; rc = -100; }
+    }
+    if (rc == 0 && (hipMemcpyAsync(h_coeffs, d_tab, tab_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                    hipMemcpyAsync(h_status, d_st, st_bytes, hipMemcpyDeviceToHost, s) != hipSuccess)) { h->err = "mcx_storage_lsm_run: copy failed"; rc = -100; }
+    if (hipStreamSynchronize(s) != hipSuccess && rc == 0) { h->err = "mcx_storage_lsm_run: synchronise failed"; rc = -100; }
+    return rc;
+}
+
+extern "C" int mcx_storage_eval(mcx_handle* h, const mcx_book* b, const mcx_storage* st, const mcx_storage_op* h_ops, int32_t n_ops,
+                                const double* d_paths, int64_t n_paths, int64_t ld, double* d_cfs, double* d_expo, int64_t ld_out,
+                                void* stream)
+{
+    if (!h || !b || !st || !h_ops || !d_paths) return -1;
+    if (n_paths <= 0 || n_ops <= 0) return 0;
+    if (st->n_basis != b->n_basis || st->n_coeffs != b->n_coeffs) MCX_FAIL(h, -2, "mcx_storage_eval: the storage was created on another book");
+    if (ld < n_paths || ld_out < n_paths) MCX_FAIL(h, -2, "mcx_storage_eval: leading dimension < n_paths");
+    if (st->netting_set >= b->n_netting_sets) MCX_FAIL(h, -2, "mcx_storage_eval: netting set out of range");
+    const int K = st->n_basis, S = st->n_states;
+    for (int q = 0; q < n_ops; ++q) {
+        const mcx_storage_op& o = h_ops[q];
+        if (o.kind == 0) {
+            if (o.index < 0 || o.index >= st->n_dates) MCX_FAIL(h, -2, "mcx_storage_eval: op %d: action date out of range", q);
+        } else if (o.kind == 1) {
+            if (!d_expo || o.index < 0 || o.index >= b->n_expo_rows) MCX_FAIL(h, -2, "mcx_storage_eval: op %d: exposure row out of range", q);
+            if (o.num_atom < 0 || o.num_atom >= b->n_atoms || o.x_atom < 0 || o.x_atom >= b->n_atoms)
+                MCX_FAIL(h, -2, "mcx_storage_eval: op %d: atom out of range", q);
+            if (o.coeff_off < 0 || o.coeff_off + (int64_t)S * K > b->n_coeffs) MCX_FAIL(h, -2, "mcx_storage_eval: op %d: coefficient block out of range", q);
+        } else MCX_FAIL(h, -2, "mcx_storage_eval: op %d: bad kind", q);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const mcx_storage_op* d_ops = (const mcx_storage_op*)mcx_stage_small(h, h_ops, sizeof(mcx_storage_op) * (size_t)n_ops, s);
+    if (!d_ops) return -100;
+    K6EvalArgs a;
+    a.paths = d_paths; a.dates = st->d_dates; a.ops = d_ops; a.atoms = b->d_atoms; a.coeffs = b->d_coeffs;
+    a.cfs = d_cfs ? d_cfs + (size_t)st->netting_set * ld_out : nullptr;
+    a.expo = d_expo ? d_expo + (size_t)st->netting_set * b->n_expo_rows * ld_out : nullptr;
+    a.n = n_paths; a.ld = ld; a.ld_out = ld_out; a.n_ops = n_ops; a.S = S; a.n_state = b->n_state; a.pad = 0;
+    const int grid = (int)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK);
+    K6_DISPATCH(K, hipLaunchKernelGGL((k6_eval<KK>), dim3(grid), dim3(MCX_BLOCK), 0, s, a));
+    MCX_HIP(h, hipGetLastError());
+    return 0;          // stream-ordered
+}

@@ -14,6 +14,8 @@ SLOT_NPARAM = 8
 AUX = 8
 MAX_BASIS = 6
 MAX_STATES = 8
+STORAGE_MAX_STATES = 32     # MCX_STORAGE_MAX_STATES: grid states of a gas storage (its own limit; MAX_STATES is the exercise machines')
+STORAGE_MAX_KNOTS = 8
 
 SCHEME_EULER, SCHEME_MILSTEIN, SCHEME_ANALYTICAL, SCHEME_QE = 0, 1, 2, 3
 MODEL_BS, MODEL_HESTON, MODEL_VASICEK, MODEL_CIRPP, MODEL_CIRPP_DET, MODEL_HW, MODEL_S2F = 1, 2, 3, 4, 5, 6, 7
@@ -103,3 +105,24 @@ LSM_SOLVE_JOB_DTYPE = np.dtype([("shift", np.float64), ("scale", np.float64), ("
 assert LSM_SOLVE_JOB_DTYPE.itemsize == 48
 
 TANGENT_NP = 4          # MCX_TANGENT_NP: model parameters per forward-mode pass (csrc/kt_book.hip)
+
+# gas storage (include/mcx.h "K6"): mcx_storage_date, mcx_storage_desc, mcx_storage_lsm_date, mcx_storage_op
+STORAGE_DATE_DTYPE = np.dtype([("vmin", "<f8"), ("step", "<f8"), ("next_vmin", "<f8"), ("next_vmax", "<f8"), ("next_scale", "<f8"),
+                               ("period", "<f8"), ("c_inj", "<f8"), ("c_wd", "<f8"),
+                               ("inj_x", "<f8", (STORAGE_MAX_KNOTS,)), ("inj_r", "<f8", (STORAGE_MAX_KNOTS,)),
+                               ("wd_x", "<f8", (STORAGE_MAX_KNOTS,)), ("wd_r", "<f8", (STORAGE_MAX_KNOTS,)),
+                               ("coeff_off", "<i8"), ("n_inj", "<i4"), ("n_wd", "<i4"), ("num_atom", "<i4"), ("x_atom", "<i4"),
+                               ("is_last", "<i4"), ("reserved", "<i4")])
+assert STORAGE_DATE_DTYPE.itemsize == 8 * 8 + 4 * 8 * STORAGE_MAX_KNOTS + 8 + 6 * 4
+
+
+class StorageDesc(C.Structure):
+    _fields_ = [("n_states", C.c_int32), ("n_dates", C.c_int32), ("netting_set", C.c_int32), ("reserved", C.c_int32),
+                ("dates", C.c_void_p), ("trans", C.c_void_p)]
+
+
+STORAGE_LSM_DATE_DTYPE = np.dtype([("roll_date", "<i4"), ("num_atom", "<i4"), ("x_atom", "<i4"), ("degenerate", "<i4"),
+                                   ("coeff_off", "<i8", (2,)), ("shift", "<f8"), ("scale", "<f8"), ("x0", "<f8")])
+STORAGE_OP_DTYPE = np.dtype([("kind", "<i4"), ("index", "<i4"), ("num_atom", "<i4"), ("x_atom", "<i4"), ("coeff_off", "<i8")])
+assert STORAGE_LSM_DATE_DTYPE.itemsize == 56 and STORAGE_OP_DTYPE.itemsize == 24
+STORAGE_OP_ACTION, STORAGE_OP_EXPOSURE = 0, 1

@@ -26,6 +26,7 @@ _EXPORTS = [
     "mcx_fused_is_straight_line", "mcx_tangent_paths", "mcx_tangent_lsm", "mcx_tangent_lsm_step", "mcx_tangent_eval", "mcx_tangent_cva", "mcx_tangent_profiles", "mcx_tangent_pick",
     "mcx_box_muller", "mcx_tangent_european", "mcx_fused_create", "mcx_fused_destroy", "mcx_fused_num_records", "mcx_fused_run", "mcx_fused_eval_paths", "mcx_fused_run_device", "mcx_fused_eval_paths_device", "mcx_fused_set_timing", "mcx_fused_kernel_times", "mcx_fused_describe",
     "mcx_value_poly_fit", "mcx_book_collapse_values", "mcx_book_value_poly_info", "mcx_rows_minmax",
+    "mcx_storage_create", "mcx_storage_destroy", "mcx_storage_lsm_step", "mcx_storage_lsm_run", "mcx_storage_eval",
     "mcx_reduce_vector", "mcx_reduce_profiles", "mcx_reduce_cva", "mcx_unsecured", "mcx_select_hist", "mcx_select_hist_dev", "mcx_select_narrow", "mcx_select_bracket", "mcx_select_hist_rows",
 ]
 
@@ -44,6 +45,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_sim_destroy.restype = None
     lib.mcx_book_destroy.restype = None
     lib.mcx_fused_destroy.restype = None
+    lib.mcx_storage_destroy.restype = None
+    lib.mcx_storage_destroy.argtypes = [C.c_void_p]
+    i32, i64, f64, vp = C.c_int32, C.c_int64, C.c_double, C.c_void_p
+    lib.mcx_storage_create.argtypes = [vp, vp, vp, vp]
+    lib.mcx_storage_lsm_step.argtypes = [vp, vp, vp, i32, i32, i32, f64, f64, vp, i64, i64, vp, vp, i64, vp, i32, vp]
+    lib.mcx_storage_lsm_run.argtypes = [vp, vp, vp, vp, i32, vp, i64, i64, vp, i64, vp, vp, i32, vp]
+    lib.mcx_storage_eval.argtypes = [vp, vp, vp, vp, i32, vp, i64, i64, vp, vp, i64, vp]
     lib.mcx_fused_num_records.argtypes = [C.c_void_p]
     lib.mcx_fused_is_straight_line.argtypes = [C.c_void_p]
     lib.mcx_fused_describe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
@@ -582,6 +590,52 @@ class HipBackend:
             C.c_int64(n), C.c_int64(_ld(paths)), _vp(W.data_ptr()), C.c_int64(ld_w), C.c_int64(W.numel()), C.byref(flag), C.c_int32(int(flags)),
             self._stream()), "mcx_lsm_run_batch")
         return int(flag.value)
+
+    # ---- K6: gas storage ------------------------------------------------------------------------------------------
+    def storage_create(self, book, dates: np.ndarray, trans: np.ndarray, n_states: int, netting_set: int):
+        """dates: STORAGE_DATE_DTYPE [n_dates] (atoms and coefficient offsets filled in), trans [n_dates][S][3][2]"""
+        dates = np.ascontiguousarray(dates, dtype=_abi.STORAGE_DATE_DTYPE)
+        trans = np.ascontiguousarray(trans, dtype=np.float64)
+        assert trans.shape == (len(dates), n_states, 3, 2)
+        desc = _abi.StorageDesc(n_states, len(dates), netting_set, 0, _abi.ptr(dates), _abi.ptr(trans))
+        out = C.c_void_p()
+        self._check(self.lib.mcx_storage_create(self.h, book.ptr, C.byref(desc), C.byref(out)), "mcx_storage_create")
+        return _Owned(out, self.lib.mcx_storage_destroy, (dates, trans))
+
+    def storage_lsm_step(self, book, storage, roll_date: int, num_atom: int, x_atom: int, shift: float, scale: float,
+                         paths: torch.Tensor, W_old: torch.Tensor, W_new: torch.Tensor, flags: int = 0) -> torch.Tensor:
+        """one backward date (mcx_storage_lsm_step): W_old, W_new [S][n] distinct; -> moments (device)"""
+        n, K, S = paths.shape[2], book.plan.n_basis, W_old.shape[0]
+        assert W_old.shape == W_new.shape and W_old.is_contiguous() and W_new.is_contiguous() and W_old.data_ptr() != W_new.data_ptr()
+        moments = self.empty((2 * K - 1) + S * K)
+        self._check(self.lib.mcx_storage_lsm_step(
+            self.h, book.ptr, storage.ptr, int(roll_date), int(num_atom), int(x_atom), float(shift), float(scale), paths.data_ptr(),
+            n, _ld(paths), W_old.data_ptr(), W_new.data_ptr(), W_old.shape[1], moments.data_ptr(), int(flags), self._stream()),
+            "mcx_storage_lsm_step")
+        return moments
+
+    def storage_lsm_run(self, book, storage, dates: np.ndarray, paths: torch.Tensor, W: torch.Tensor, flags: int = 0):
+        """the backward induction of one storage in one call (mcx_storage_lsm_run): dates = STORAGE_LSM_DATE_DTYPE in induction
+        order, W [2][S][n] zeroed -> (coefficients [n_dates][S][K], status [n_dates])"""
+        dates = np.ascontiguousarray(dates, dtype=_abi.STORAGE_LSM_DATE_DTYPE)
+        n, K = paths.shape[2], book.plan.n_basis
+        assert W.dim() == 3 and W.shape[0] == 2 and W.is_contiguous()
+        S = W.shape[1]
+        coeffs = np.zeros((len(dates), S, K))
+        status = np.zeros(len(dates), dtype=np.int32)
+        self._check(self.lib.mcx_storage_lsm_run(
+            self.h, book.ptr, storage.ptr, _abi.ptr(dates), len(dates), paths.data_ptr(), n, _ld(paths), W.data_ptr(), W.shape[2],
+            _abi.ptr(coeffs), _abi.ptr(status), int(flags), self._stream()), "mcx_storage_lsm_run")
+        return coeffs, status
+
+    def storage_eval(self, book, storage, ops: np.ndarray, paths: torch.Tensor, cfs, expo):
+        """the main-simulation walk of one storage, ADDED into cfs [ns][n] / expo [ns][rows][n] (mcx_storage_eval)"""
+        ops = np.ascontiguousarray(ops, dtype=_abi.STORAGE_OP_DTYPE)
+        n = paths.shape[2]
+        self._check(self.lib.mcx_storage_eval(
+            self.h, book.ptr, storage.ptr, _abi.ptr(ops), len(ops), paths.data_ptr(), n, _ld(paths),
+            cfs.data_ptr() if cfs is not None else None, expo.data_ptr() if expo is not None else None, _ld_out(cfs, expo, n),
+            self._stream()), "mcx_storage_eval")
 
     def book_get_coeffs(self, book) -> np.ndarray:
         out = np.zeros(len(book.plan.coeffs))

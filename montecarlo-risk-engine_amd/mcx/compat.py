@@ -22,6 +22,7 @@ _MODULES = [
     "models.hull_white", "models.black_scholes_multi", "models.schwartz_two_factor",
     "products.product", "products.equity", "products.bond", "products.swap", "products.european_option",
     "products.bermudan_option", "products.netting_set", "products.basket_option", "products.binary_option", "products.asian_option", "products.barrier_option", "products.flexicall",
+    "products.storage_helpers", "products.storage",
     "request_interface.request_types", "request_interface.request_interface",
 ]
 

@@ -121,6 +121,8 @@ class SimulationController:
         self._backend = backend
         for i, p in enumerate(products):
             p.product_id = i
+        if differentiate and any(getattr(p, "is_storage", False) for p in products):
+            raise NotImplementedError("sensitivities through the storage policy are not implemented (differentiate=True with a Storage)")
         if differentiate:
             self.model.requires_grad()
 
@@ -130,7 +132,10 @@ class SimulationController:
         self.regression_coeffs = []
         for p in products:
             p._allocate_regression_coeffs(regression_function)
-            if p.get_num_states() > _abi.MAX_STATES:
+            if getattr(p, "is_storage", False):
+                if p.get_num_states() > _abi.STORAGE_MAX_STATES:
+                    raise ValueError(f"a storage of {p.get_num_states()} grid states exceeds MCX_STORAGE_MAX_STATES={_abi.STORAGE_MAX_STATES}")
+            elif p.get_num_states() > _abi.MAX_STATES:
                 raise ValueError("too many exercise states")
             self.regression_coeffs.append(torch.zeros((len(self.exposure_timeline), p.get_num_states(), K), dtype=FLOAT))
 
@@ -257,6 +262,7 @@ class SimulationController:
         self._extra_coeff_base = []
         self._mc_products = []
         self._mc_set = set()
+        self._storage_meta, self._storage_handles = {}, {}       # gas storages: atoms per product; native objects per uploaded book
         off = 0
         for p_i, p in enumerate(self.products):
             S = p.get_num_states()
@@ -356,6 +362,18 @@ class SimulationController:
                 pid = id(p)
                 memo[("skip", pid)], memo[("analytic", pid)], memo[("regression", pid)] = False, rec["analytic"], rec["requires_reg"]
                 self._member_rec[p_i] = rec
+                continue
+            if getattr(p, "is_storage", False):
+                # a storage owns no events: its state is real-valued (csrc/k6_storage.hip); the book sees a product without events
+                n_states[p_i], init_state[p_i] = 1, 0
+                cash_start[p_i + 1] = len(cash_rows)
+                asset = p.asset_ids[0]
+                self._storage_meta[p_i] = dict(
+                    action=[(comp.atom(p.numeraire_requests[j], "numeraire", t), comp.atom(p.spot_requests[(j, asset)], asset, t))
+                            for j, t in enumerate(self._timelines(p)[0])],
+                    expo=expo_atoms(asset) if want_expo else None)
+                mc_products.append(p_i)
+                mc_set.add(p_i)
                 continue
             S = p.get_num_states()
             n_states[p_i], init_state[p_i] = S, p.get_initial_state()
@@ -516,12 +534,12 @@ class SimulationController:
         self.last_state["paths_pre"] = paths
         K = self.regression_function.get_degree()
         comp = self._comp
-        jobs = []
+        jobs, storage_jobs = [], []
         for p_i, p in enumerate(self.products):
             if p_i not in self._mc_set or not self._product_requires_regression(p):
                 continue
             sched = self._regression_schedule(p_i, p)
-            jobs.append((p_i, p, sched, self._regression_atoms(sched, p.asset_ids[0])))
+            (storage_jobs if p_i in self._storage_meta else jobs).append((p_i, p, sched, self._regression_atoms(sched, p.asset_ids[0])))
         self._book_ready()               # (everything above ran beside a big book's upload)
         self._collapse_values(shard, paths)
         self._set_bridge_rng(eng.seed, off, "bridge_pre")
@@ -529,13 +547,15 @@ class SimulationController:
         if len(self._comp.atoms) != len(self.book_plan.atoms):
             raise RuntimeError("internal: regression atoms must be registered before the book is frozen")
         # range of every explanatory variable (conditioning of the monomial basis; exact-degeneracy detection)
-        x_ids = sorted({x for _, _, _, atoms in jobs for _, x in atoms})
+        x_ids = sorted({x for _, _, _, atoms in jobs + storage_jobs for _, x in atoms})
         if x_ids:
             mm = be.lsm_stats(self.book, x_ids, paths)
             g = shard.all_gather_np(mm)
             lo, hi = g[:, :, 0].min(axis=0), g[:, :, 1].max(axis=0)
             x_range = {x: (lo[i], hi[i]) for i, x in enumerate(x_ids)}
         lsm_flags = (_abi.LSM_MFMA if self.use_mfma else 0) | (_abi.LSM_F32_CACHE if self.reference_float32_cf_cache else 0)
+        for p_i, p, sched, atoms in storage_jobs:
+            self._storage_regression(shard, p_i, p, sched, atoms, x_range, paths, n_local, K, lsm_flags)
         if not jobs:
             return
         if self.batch_lsm and not self.use_mfma and len(jobs) >= 4:       # (one or two products: the per-product loop has less fixed cost per step)
@@ -561,6 +581,94 @@ class SimulationController:
                 if expo_idx is not None:
                     self.regression_coeffs[p_i][expo_idx] = torch.from_numpy(coeffs)
                     be.book_set_coeffs(self.book, self._expo_coeff_base[p_i] + expo_idx * S * K, coeffs)
+
+    # ---- gas storage (csrc/k6_storage.hip) ---------------------------------------------------------------------------
+    def _storage_handle(self, p_i: int):
+        """the native image of storage p_i on the uploaded book: per-date tables + integer-state transition table"""
+        hit = self._storage_handles.get(p_i)
+        if hit is None:
+            p, meta = self.products[p_i], self._storage_meta[p_i]
+            S, K = p.get_num_states(), self.regression_function.get_degree()
+            dates = p._device_dates()
+            dates["num_atom"] = [a_[0] for a_ in meta["action"]]
+            dates["x_atom"] = [a_[1] for a_ in meta["action"]]
+            dates["coeff_off"] = self._reg_coeff_base[p_i] + np.arange(len(dates), dtype=np.int64) * (S * K)
+            hit = self._storage_handles[p_i] = self.backend.storage_create(self._book_ready(), dates, p._transition_table(), S,
+                                                                           self.product_to_netting_set_idx[p_i])
+        return hit
+
+    def _storage_regression(self, shard: Shard, p_i, p, sched, atoms, x_range, paths, n_local: int, K: int, lsm_flags: int):
+        """backward induction of one storage (controller.py:294-383 with the storage's compute_normalized_cashflows).  Every
+        action date is a regression date, so a step rolls at most ONE action date, from the integer grid states.  One rank: the
+        whole induction in one library call; several ranks (or a singular system on the device): per date step -> all-reduce ->
+        host solve."""
+        be = self.backend
+        S = p.get_num_states()
+        st = self._storage_handle(p_i)
+        dates = np.zeros(len(sched), dtype=_abi.STORAGE_LSM_DATE_DTYPE)
+        for j, ((t_reg, r0, r1, prod_idx, expo_idx), (num, x)) in enumerate(zip(sched, atoms)):
+            if r1 - r0 > 1:
+                raise RuntimeError("internal: a storage step rolls at most one action date")
+            xmin, xmax = x_range[x]
+            degenerate = not (xmax > xmin)
+            d = dates[j]
+            d["roll_date"], d["num_atom"], d["x_atom"], d["degenerate"] = (r0 if r1 > r0 else -1), num, x, int(degenerate)
+            d["shift"] = 0.5 * (xmin + xmax) if not degenerate else xmin
+            d["scale"] = 2.0 / (xmax - xmin) if not degenerate else 1.0
+            d["x0"] = xmin
+            d["coeff_off"][0] = -1 if prod_idx is None else self._reg_coeff_base[p_i] + prod_idx * S * K
+            d["coeff_off"][1] = -1 if expo_idx is None else self._expo_coeff_base[p_i] + expo_idx * S * K
+        W = be.zeros(2, S, n_local)
+        coeffs = None
+        if shard.world == 1:
+            coeffs, status = be.storage_lsm_run(self.book, st, dates, paths, W, flags=lsm_flags)
+            if status.any():
+                coeffs = None
+                W.zero_()
+        if coeffs is None:
+            coeffs = np.zeros((len(dates), S, K))
+            cur = 0
+            for j, d in enumerate(dates):
+                mom = be.storage_lsm_step(self.book, st, int(d["roll_date"]), int(d["num_atom"]), int(d["x_atom"]), float(d["shift"]),
+                                          float(d["scale"]), paths, W[cur], W[1 - cur], flags=lsm_flags)
+                if d["roll_date"] >= 0:
+                    cur = 1 - cur
+                shard.all_reduce_(mom)
+                coeffs[j] = solve_normal_equations(mom.detach().cpu().numpy(), K, S, float(d["shift"]), float(d["scale"]),
+                                                   bool(d["degenerate"]), float(d["x0"]))
+                for off in d["coeff_off"]:
+                    if off >= 0:
+                        be.book_set_coeffs(self.book, int(off), coeffs[j])
+        for j, (t_reg, r0, r1, prod_idx, expo_idx) in enumerate(sched):
+            if prod_idx is not None:
+                p.regression_coeffs[prod_idx] = torch.from_numpy(coeffs[j].copy())
+            if expo_idx is not None:
+                self.regression_coeffs[p_i][expo_idx] = torch.from_numpy(coeffs[j].copy())
+
+    def _storage_ops(self, p_i: int) -> np.ndarray:
+        """the walk of the realised state through the main simulation (controller.py:399-461): action dates up to and including
+        each exposure date, the exposure row, and the remaining action dates when cashflows are wanted"""
+        p, meta = self.products[p_i], self._storage_meta[p_i]
+        rm = self.risk_metrics
+        S, K = p.get_num_states(), self.regression_function.get_degree()
+        pdates = self._timelines(p)[0]
+        ops = []
+        j = 0
+        if rm.requires_exposure_profiles():
+            for i, t in enumerate(float(t) for t in self.exposure_timeline):
+                while j < len(pdates) and pdates[j] <= t:
+                    ops.append((_abi.STORAGE_OP_ACTION, j, -1, -1, -1))
+                    j += 1
+                num, x = meta["expo"][i]
+                ops.append((_abi.STORAGE_OP_EXPOSURE, i, num, x, self._expo_coeff_base[p_i] + i * S * K))
+        if rm.requires_discounted_cashflows():
+            ops.extend((_abi.STORAGE_OP_ACTION, q, -1, -1, -1) for q in range(j, len(pdates)))
+        return np.array(ops, dtype=_abi.STORAGE_OP_DTYPE)
+
+    def _storage_eval(self, paths, cfs, expo):
+        """every storage adds its discounted cashflows / exposures to the matrices mcx_eval_book has just written"""
+        for p_i in self._storage_meta:
+            self.backend.storage_eval(self.book, self._storage_handle(p_i), self._storage_ops(p_i), paths, cfs, expo)
 
     def _collapse_values(self, shard: Shard, paths):
         """events that sum many atoms of one state variable (a Bermudan swaption's exercise value: the underlying swap priced
@@ -993,6 +1101,9 @@ class SimulationController:
         """everything before the main simulation: descriptor compilation + (if needed) pre-simulation and LSM regression
         (the reference's perform_prepocessing, controller.py:257-292)"""
         be = self.backend
+        if any(getattr(p, "is_storage", False) for p in self.products) and not hasattr(be, "storage_lsm_run"):
+            raise NotImplementedError(f"the {getattr(be, 'name', type(be).__name__)} backend has no gas-storage entry points "
+                                      "(mcx_storage_*): a Storage runs on the HIP backend only")
         self._shard = self.shard_factory()
         self.last_state = {}             # release the previous run's device buffers first: the allocator can reuse them
         t0 = time.perf_counter()
@@ -1020,6 +1131,8 @@ class SimulationController:
     def _build_fused(self):
         """FusedPlan for the one-launch main pass, or None when some requested metric needs the separate kernels"""
         rm = self.risk_metrics
+        if self._storage_meta:           # a storage is not part of the event program: K1 -> K2 -> mcx_storage_eval -> K4 / K5
+            return None
         if len(self.netting_sets) > _abi.FUSED_MAX_NS or any(ns.is_collateralized() for ns in self.netting_sets):
             return None
         if not all(m._native for m in rm.metrics):
@@ -1184,6 +1297,7 @@ class SimulationController:
             return self._fused_pass(paths_out)
         paths = self._main_engine.generate_paths_native(out=paths_out)
         cfs, expo = be.eval_book(self.book, paths) if self._mc_products else (None, None)
+        self._storage_eval(paths, cfs, expo)
         self.last_state.update(paths=paths, cfs=cfs, expo=expo)
         return self._evaluate_all(self._shard, cfs, expo, paths)
 
@@ -1227,6 +1341,7 @@ class SimulationController:
         be.synchronize()
         t2 = time.perf_counter()
         cfs, expo = be.eval_book(self.book, paths) if self._mc_products else (None, None)
+        self._storage_eval(paths, cfs, expo)
         be.synchronize()
         t3 = time.perf_counter()
         self.last_state.update(paths=paths, cfs=cfs, expo=expo)

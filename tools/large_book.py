@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Large mixed netting sets: the books of the reference's three performance scripts — Europeans, binaries,
 baskets, Asians, barriers, Americans, FlexiCalls on a 4-asset BlackScholesMulti (book builder: pv_tests/
-pv_performance_large_netting_set.py:86-233), WITHOUT the gas-storage products (out of scope), 1000 + 1000 paths:
+pv_performance_large_netting_set.py:86-233), 1000 + 1000 paths.  The reference's books also carry gas storages (10 per 4,990
+products); they are left out by default so that the recorded figures stay comparable, `--storages N` adds N of them:
 
   --book cva  tests/exposure_tests/cva_perfprmance_large_netting_set.py:69-148 — 4,990 products, + CIR++ credit, 10-day MPoR
               collateral, CVA on 80 exposure dates, one Euler step per date
@@ -11,7 +12,7 @@ pv_performance_large_netting_set.py:86-233), WITHOUT the gas-storage products (o
 
 Prints products/s of run_simulation() like the reference scripts.
 
-    python tools/large_book.py [--book cva] [--scale 1.0] [--paths 1000]"""
+    python tools/large_book.py [--book cva] [--scale 1.0] [--paths 1000] [--storages 0]"""
 import argparse
 import json
 import os
@@ -43,6 +44,8 @@ from mcx.products.european_option import EuropeanOption                         
 from mcx.products.flexicall import FlexiCall                                           # noqa: E402
 from mcx.products.netting_set import NettingSet                                        # noqa: E402
 from mcx.products.product import OptionType                                            # noqa: E402
+from mcx.products.storage import Storage                                               # noqa: E402
+from mcx.products.storage_helpers import StorageConfig                                 # noqa: E402
 
 CP = "mixed_book_counterparty"
 HAZARDS = {0.5: 0.006402303360855854, 1.0: 0.01553038972325307, 2.0: 0.009729741230773657, 3.0: 0.015552544648116201,
@@ -94,6 +97,31 @@ def build_mixed_book(asset_ids, n_eur, n_bin, n_bas, n_asi, n_bar, n_ame, n_flx)
     return P
 
 
+def build_storages(asset_ids, n):
+    """storages shaped like the reference scripts' (pv_performance_large_netting_set.py:43-84, 235-251): three volume windows (ramp-up,
+    plateau, release), two-knot rate curves that change with the windows, a 10 % cost step at the start of the release"""
+    P = []
+    for i in range(n):
+        mat, cap = [1.0, 1.5, 2.0, 2.5][i % 4], [18.0, 26.0, 34.0, 42.0][i % 4]
+        c_inj, c_wd = 0.10 + 0.02 * (i % 4), 0.08 + 0.015 * (i % 4)
+        ramp, plateau = 0.35 * mat, 0.70 * mat
+        c = StorageConfig()
+        for t0, t1, lo, hi in ((0.0, ramp, 0.0, 0.55), (ramp, plateau, 0.10, 0.85), (plateau, mat, 0.0, 1.0)):
+            c.add_volume_constraint(t0, t1, lo * cap, hi * cap, 0.0)
+        for add, rows in ((c.add_injection_flexibility, ((0.0, ramp, 0.30, 0.18), (ramp, mat, 0.22, 0.12))),
+                          (c.add_withdrawal_flexibility, ((0.0, plateau, 0.16, 0.24), (plateau, mat, 0.24, 0.32)))):
+            for t0, t1, r_empty, r_full in rows:
+                add(t0, t1, 0.0, r_empty * cap)
+                add(t0, t1, 0.60 * cap, r_full * cap)
+        for add, cost in ((c.add_variable_injection_cost, c_inj), (c.add_variable_withdrawal_cost, c_wd)):
+            add(0.0, cost)
+            add(plateau, cost * 1.10)
+        p = Storage(asset_ids[i % len(asset_ids)], 0.0, mat, 2.0 + 0.5 * (i % 5), c, 6 + (i % 5), [0.05, 0.10, 0.125][i % 3])
+        p.name = f"storage_{i}"
+        P.append(p)
+    return P
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="fraction of the reference script's 4,990 non-storage products")
@@ -101,6 +129,7 @@ def main():
     ap.add_argument("--exposure-points", type=int, default=80)
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--book", choices=("cva", "ee", "pv"), default="cva")
+    ap.add_argument("--storages", type=int, default=0, help="gas storages added to the book (the reference scripts: 10 per 4,990 products)")
     ap.add_argument("--profile", action="store_true", help="cProfile the last repetition's run_simulation (top functions to stderr)")
     args = ap.parse_args()
     from mcx import _native
@@ -111,7 +140,7 @@ def main():
     for rep in range(args.repeat):
         corr = np.full((4, 4), 0.35); np.fill_diagonal(corr, 1.0)
         market = BlackScholesMulti(0.0, 0.03, ids, [95.0 + 7.5 * k for k in range(4)], [0.18 + 0.03 * k for k in range(4)], corr)
-        products = build_mixed_book(ids, *counts)
+        products = build_mixed_book(ids, *counts) + build_storages(ids, args.storages)
         horizon = max(float(p.modeling_timeline[-1]) for p in products)
         tl = np.linspace(0.0, horizon, args.exposure_points)
         if args.book == "cva":
@@ -136,7 +165,7 @@ def main():
             res = sc.run_simulation()
         be.synchronize()
         t2 = time.perf_counter()
-        out = dict(book=args.book, products=len(products), counts=counts, paths=args.paths, exposure_points=args.exposure_points,
+        out = dict(book=args.book, products=len(products), counts=counts, storages=args.storages, paths=args.paths, exposure_points=args.exposure_points,
                    timeline_size=int(sc.simulation_timeline.numel()), construct_s=t1 - t0, run_s=t2 - t1,
                    products_per_second=len(products) / (t2 - t1), timings=sc.timings, prepare=getattr(sc, 'prepare_timings', None),
                    lsm_singular_retries=getattr(sc, 'lsm_singular_retries', 0))
