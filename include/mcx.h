@@ -664,6 +664,37 @@ int  mcx_storage_eval(mcx_handle* h, const mcx_book* book, const mcx_storage* st
                       const double* d_paths, int64_t n_paths, int64_t ld, double* d_cfs, double* d_expo, int64_t ld_out,
                       void* stream);
 
+/* Sensitivities through the storage (csrc/kt_storage.hip): the dual images of mcx_storage_lsm_step / mcx_storage_eval and dual
+ * paths of the Schwartz two-factor slot, MCX_TANGENT_NP parameters per pass, tensors laid out as the forward-mode block above
+ * describes (d_dpaths [NP][T][D][ld], d_datoms [n_atoms][5][NP]).  The derivative is the reference tape's (products/storage.py:
+ * 219-308): the action values feed argmax only, so decisions, next states and volume changes carry no gradient; it flows through
+ * cash / numeraire of the chosen action, the interpolation of the cache at fixed weights, the normal equations (host) and the
+ * exposure polynomials.  Decisions are taken from the primal values and from d_coeffs — the BASE run's coefficients —, image 0 is
+ * formed by the primal kernels' arithmetic.  The storage is passed as its host descriptor (the one mcx_storage_create was given):
+ * the tangent kernels need the atom ids of every date, which the native object does not keep.  Basis size <= 4.
+ * mcx_tangent_storage_lsm_step: one backward date.  d_W_* [S][ld_w], d_dW_* [NP][S][ld_w], old and new distinct, zero before the
+ *   first step; roll_date < 0: moments from the old pair, the new pair is not touched.  MCX_LSM_F32_CACHE rounds the PRIMAL cash term
+ *   to float32 as mcx_storage_lsm_step does (W equals the base run's); its tangent is not rounded.  h_moments
+ *   [1+NP][(2K-1) + S K] in the layout of mcx_tangent_lsm_step: sums of z^k, then of z^k numeraire W_s per state, z dual.
+ * mcx_tangent_storage_eval: the walk of mcx_storage_eval, ADDED into d_cfs [1+NP][n_ns][ld_out] and d_expo
+ *   [1+NP][n_ns][n_rows][ld_out] as mcx_tangent_eval has just written them, with the d_coeffs / d_dcoeffs that call received.
+ * mcx_tangent_paths_s2f: mcx_tangent_paths for a single MCX_MODEL_S2F slot, EULER or ANALYTICAL.  The correlation is a model
+ *   parameter, so the Cholesky factors carry tangents: h_dchol [n_chol][2][2][NP] next to h_dslot [1][MCX_SLOT_NPARAM][NP],
+ *   h_dinit [3][NP], h_daux [n_steps][1][MCX_AUX][NP].  d_paths [T][3][ld] (log S, x, y), d_dpaths [NP][T][3][ld].
+ * All three synchronise the stream. */
+int  mcx_tangent_storage_lsm_step(mcx_handle* h, const mcx_book* book, const mcx_storage_desc* desc, int32_t roll_date, int32_t num_atom,
+                                  int32_t x_atom, double shift, double scale, const double* d_datoms, const double* d_coeffs,
+                                  const double* d_paths, const double* d_dpaths, int64_t n_paths, int64_t ld, int32_t n_dates,
+                                  const double* d_W_old, const double* d_dW_old, double* d_W_new, double* d_dW_new, int64_t ld_w,
+                                  double* h_moments, int32_t flags, void* stream);
+int  mcx_tangent_storage_eval(mcx_handle* h, const mcx_book* book, const mcx_storage_desc* desc, const mcx_storage_op* h_ops, int32_t n_ops,
+                              const double* d_datoms, const double* d_coeffs, const double* d_dcoeffs, const double* d_paths,
+                              const double* d_dpaths, int64_t n_paths, int64_t ld, int32_t n_dates, double* d_cfs, double* d_expo,
+                              int64_t ld_out, void* stream);
+int  mcx_tangent_paths_s2f(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                           const double* h_dchol, uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths,
+                           double* d_dpaths, int64_t ld, const double* d_inject_z, void* stream);
+
 /* Multi-GPU exchange (paths shard over the GPUs of a node, one process per GPU; the only data that crosses
  * GPUs are accumulator records, LSM moments and select histograms).  RCCL over xGMI, loaded at run time (librccl.so.1 — the
  * library has no link-time dependency on it).  A caller without torch.distributed creates the id on rank 0

@@ -27,8 +27,17 @@ _EXPORTS = [
     "mcx_box_muller", "mcx_tangent_european", "mcx_fused_create", "mcx_fused_destroy", "mcx_fused_num_records", "mcx_fused_run", "mcx_fused_eval_paths", "mcx_fused_run_device", "mcx_fused_eval_paths_device", "mcx_fused_set_timing", "mcx_fused_kernel_times", "mcx_fused_describe",
     "mcx_value_poly_fit", "mcx_book_collapse_values", "mcx_book_value_poly_info", "mcx_rows_minmax",
     "mcx_storage_create", "mcx_storage_destroy", "mcx_storage_lsm_step", "mcx_storage_lsm_run", "mcx_storage_eval",
+    "mcx_tangent_storage_lsm_step", "mcx_tangent_storage_eval", "mcx_tangent_paths_s2f",
     "mcx_reduce_vector", "mcx_reduce_profiles", "mcx_reduce_cva", "mcx_unsecured", "mcx_select_hist", "mcx_select_hist_dev", "mcx_select_narrow", "mcx_select_bracket", "mcx_select_hist_rows",
 ]
+
+
+class McxError(RuntimeError):
+    """a library call returned a non-zero status; `code` is that status (mcx.h MCX_E_*)"""
+
+    def __init__(self, message: str, code: int):
+        super().__init__(message)
+        self.code = code
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
@@ -52,6 +61,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_storage_lsm_step.argtypes = [vp, vp, vp, i32, i32, i32, f64, f64, vp, i64, i64, vp, vp, i64, vp, i32, vp]
     lib.mcx_storage_lsm_run.argtypes = [vp, vp, vp, vp, i32, vp, i64, i64, vp, i64, vp, vp, i32, vp]
     lib.mcx_storage_eval.argtypes = [vp, vp, vp, vp, i32, vp, i64, i64, vp, vp, i64, vp]
+    lib.mcx_tangent_storage_lsm_step.argtypes = [vp, vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp, i32, vp]
+    lib.mcx_tangent_storage_eval.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i64, vp]
+    lib.mcx_tangent_paths_s2f.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_fused_num_records.argtypes = [C.c_void_p]
     lib.mcx_fused_is_straight_line.argtypes = [C.c_void_p]
     lib.mcx_fused_describe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
@@ -118,7 +130,7 @@ class HipBackend:
     def _check(self, rc: int, what: str):
         if rc != 0:
             msg = self.lib.mcx_last_error(self.h)
-            raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            raise McxError(f"{what} failed ({rc}): {msg.decode() if msg else ''}", rc)
 
     def _stream(self) -> C.c_void_p:
         return _vp(torch.cuda.current_stream(self.device).cuda_stream)
@@ -600,7 +612,9 @@ class HipBackend:
         desc = _abi.StorageDesc(n_states, len(dates), netting_set, 0, _abi.ptr(dates), _abi.ptr(trans))
         out = C.c_void_p()
         self._check(self.lib.mcx_storage_create(self.h, book.ptr, C.byref(desc), C.byref(out)), "mcx_storage_create")
-        return _Owned(out, self.lib.mcx_storage_destroy, (dates, trans))
+        st = _Owned(out, self.lib.mcx_storage_destroy, (dates, trans))
+        st.n_states, st.netting_set = int(n_states), int(netting_set)      # (the tangent entry points take the host descriptor)
+        return st
 
     def storage_lsm_step(self, book, storage, roll_date: int, num_atom: int, x_atom: int, shift: float, scale: float,
                          paths: torch.Tensor, W_old: torch.Tensor, W_new: torch.Tensor, flags: int = 0) -> torch.Tensor:
@@ -636,6 +650,64 @@ class HipBackend:
             self.h, book.ptr, storage.ptr, _abi.ptr(ops), len(ops), paths.data_ptr(), n, _ld(paths),
             cfs.data_ptr() if cfs is not None else None, expo.data_ptr() if expo is not None else None, _ld_out(cfs, expo, n),
             self._stream()), "mcx_storage_eval")
+
+    # ---- sensitivities through the storage (csrc/kt_storage.hip) -----------------------------------------------------
+    @staticmethod
+    def _storage_desc(storage):
+        dates, trans = storage.plan
+        return _abi.StorageDesc(storage.n_states, len(dates), storage.netting_set, 0, _abi.ptr(dates), _abi.ptr(trans))
+
+    def tangent_storage_lsm_step(self, book, storage, roll_date: int, num_atom: int, x_atom: int, shift: float, scale: float,
+                                 datoms: torch.Tensor, coeffs: torch.Tensor, paths: torch.Tensor, dpaths: torch.Tensor,
+                                 W_old: torch.Tensor, dW_old: torch.Tensor, W_new: torch.Tensor, dW_new: torch.Tensor,
+                                 flags: int = 0) -> np.ndarray:
+        """one backward date of a storage in dual numbers (mcx_tangent_storage_lsm_step): W_* [S][n], dW_* [NP][S][n], old and new
+        distinct; decisions from `coeffs` (the base run's array, device); -> moments [1+NP][(2K-1) + S K]"""
+        NP, K, S, n = _abi.TANGENT_NP, book.plan.n_basis, W_old.shape[0], paths.shape[2]
+        assert S == storage.n_states and W_old.shape == W_new.shape and dW_old.shape == dW_new.shape == (NP, S, W_old.shape[1])
+        assert all(t.is_contiguous() for t in (W_old, W_new, dW_old, dW_new, paths, dpaths)) and W_old.shape[1] >= n
+        assert W_old.data_ptr() != W_new.data_ptr() and dW_old.data_ptr() != dW_new.data_ptr()
+        assert dpaths.shape == (NP,) + tuple(paths.shape) and coeffs.numel() >= len(book.plan.coeffs)
+        out = np.zeros((1 + NP, (2 * K - 1) + S * K))
+        desc = self._storage_desc(storage)
+        self._check(self.lib.mcx_tangent_storage_lsm_step(
+            self.h, book.ptr, C.byref(desc), int(roll_date), int(num_atom), int(x_atom), float(shift), float(scale),
+            datoms.data_ptr(), coeffs.data_ptr(), paths.data_ptr(), dpaths.data_ptr(), n, n, paths.shape[0],
+            W_old.data_ptr(), dW_old.data_ptr(), W_new.data_ptr(), dW_new.data_ptr(), W_old.shape[1], _abi.ptr(out), int(flags),
+            self._stream()), "mcx_tangent_storage_lsm_step")
+        return out
+
+    def tangent_storage_eval(self, book, storage, ops: np.ndarray, datoms: torch.Tensor, coeffs: torch.Tensor, dcoeffs: torch.Tensor,
+                             paths: torch.Tensor, dpaths: torch.Tensor, cfs: torch.Tensor, expo: torch.Tensor):
+        """the main-simulation walk of one storage in dual numbers, ADDED into the images of tangent_eval (mcx_tangent_storage_eval):
+        cfs [1+NP][ns][n], expo [1+NP][ns][rows][n]"""
+        ops = np.ascontiguousarray(ops, dtype=_abi.STORAGE_OP_DTYPE)
+        NP, n = _abi.TANGENT_NP, paths.shape[2]
+        plan = book.plan
+        assert cfs.is_contiguous() and expo.is_contiguous() and paths.is_contiguous() and dpaths.is_contiguous()
+        assert cfs.shape == (1 + NP, plan.n_netting_sets, n) and expo.shape == (1 + NP, plan.n_netting_sets, max(plan.n_expo_rows, 1), n)
+        assert dpaths.shape == (NP,) + tuple(paths.shape) and coeffs.numel() >= len(plan.coeffs) and dcoeffs.shape == (coeffs.numel(), NP)
+        desc = self._storage_desc(storage)
+        self._check(self.lib.mcx_tangent_storage_eval(
+            self.h, book.ptr, C.byref(desc), _abi.ptr(ops), len(ops), datoms.data_ptr(), coeffs.data_ptr(), dcoeffs.data_ptr(),
+            paths.data_ptr(), dpaths.data_ptr(), n, n, paths.shape[0], cfs.data_ptr(), expo.data_ptr(), n, self._stream()),
+            "mcx_tangent_storage_eval")
+
+    def tangent_paths_s2f(self, sim, dslot: np.ndarray, dinit: np.ndarray, daux: np.ndarray, dchol: np.ndarray, seed: int,
+                          path_offset: int, n_paths: int, inject_z=None):
+        """tangent_paths for a single Schwartz two-factor slot, EULER or ANALYTICAL (mcx_tangent_paths_s2f); dchol [n_chol][2][2][NP]"""
+        plan = sim.plan
+        NP = _abi.TANGENT_NP
+        paths = self.empty(plan.n_dates, plan.n_state, n_paths)
+        dpaths = self.empty(NP, plan.n_dates, plan.n_state, n_paths)
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (dslot, dinit, daux, dchol)]
+        assert a[0].shape == (1, _abi.SLOT_NPARAM, NP) and a[1].shape == (3, NP) and a[2].shape == (plan.n_steps, 1, _abi.AUX, NP)
+        assert a[3].shape == (len(plan.chol), 2, 2, NP)
+        self._check(self.lib.mcx_tangent_paths_s2f(
+            self.h, sim.ptr, _abi.ptr(a[0]), _abi.ptr(a[1]), _abi.ptr(a[2]), _abi.ptr(a[3]), seed, path_offset, n_paths,
+            paths.data_ptr(), dpaths.data_ptr(), n_paths, inject_z.data_ptr() if inject_z is not None else None, self._stream()),
+            "mcx_tangent_paths_s2f")
+        return paths, dpaths
 
     def book_get_coeffs(self, book) -> np.ndarray:
         out = np.zeros(len(book.plan.coeffs))

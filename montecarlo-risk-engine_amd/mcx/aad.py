@@ -234,7 +234,10 @@ def _host_descriptors(sc, model=None, dtype=np.float64):
         atoms[q] = (co.a, co.d, co.b, co.c0, co.c1)
         cols.append(-1 if co.col is None else co.col)
     shape = (tuple(cols), tuple(sp.kind for sp in specs))
-    return dict(slots=slots, init=np.array(model._initial_state(), dtype=dtype), aux=aux, atoms=atoms), shape
+    out = dict(slots=slots, init=np.array(model._initial_state(), dtype=dtype), aux=aux, atoms=atoms)
+    if hasattr(model, "_cholesky_entries"):          # factors that depend on the parameters (a correlation that is one of them)
+        out["chol"] = np.array([model._cholesky_entries(sim.scheme, dt) for dt in sim.chol_dt], dtype=dtype).reshape(len(sim.chol_dt), sim.n_z, sim.n_z)
+    return out, shape
 
 
 def _set_complex_step(model, j: int, h: float):
@@ -299,7 +302,10 @@ def run_with_tangent_book(sc):
     if sc.requires_higher_order_derivatives:
         raise _NoTangentForm("second order")
     rm = sc.risk_metrics
-    if sc.simulation_scheme.name != "EULER":
+    # Schwartz two-factor dual paths serve books that hold a storage; every other book keeps the route it had (no tangent form)
+    s2f = hasattr(sc.model, "_cholesky_entries") and hasattr(sc.backend, "tangent_paths_s2f") \
+        and any(getattr(p, "is_storage", False) for p in sc.products)
+    if sc.simulation_scheme.name != "EULER" and not (s2f and sc.simulation_scheme.name == "ANALYTICAL"):
         raise _NoTangentForm("scheme")
     if any(m.metric_type not in (MetricType.PV, MetricType.CVA, MetricType.EPE, MetricType.ENE, MetricType.CE, MetricType.EEPE,
                                  MetricType.PFE) or not m._native for m in rm.metrics):
@@ -381,11 +387,19 @@ def run_with_tangent_book(sc):
     def mean_of(vec):
         return mean_and_error(shard.all_gather_np(be.reduce_vector(vec).view(np.float64)))[0]
 
+    storages = getattr(base, "_storage_meta", {})
+    lsm_flags = _abi.LSM_F32_CACHE if base.reference_float32_cf_cache else 0
+
     for c0 in range(0, P, NP):
         sel = list(range(c0, min(c0 + NP, P)))
         pad = lambda a: np.ascontiguousarray(np.concatenate([a[..., sel], np.zeros(a.shape[:-1] + (NP - len(sel),))], axis=-1))
         dslot, dinit, daux = pad(dd["slots"]), pad(dd["init"]), pad(dd["aux"])
         datoms = be.from_numpy(pad(dd["atoms"]))
+
+        def dual_paths(seed, off_, n_, inject_z):
+            if s2f:
+                return be.tangent_paths_s2f(sim, dslot, dinit, daux, pad(dd["chol"]), seed, off_, n_, inject_z)
+            return be.tangent_paths(sim, dslot, dinit, daux, seed, off_, n_, inject_z)
         coeffs, dcoeffs = np.zeros(max(n_coeffs, 1)), np.zeros((max(n_coeffs, 1), NP))
         if has_exercise and n_coeffs:
             # exercise decisions are taken from the PRIMAL coefficients of the base run (the reference's tape has no gradient through
@@ -394,8 +408,7 @@ def run_with_tangent_book(sc):
         t1 = time.perf_counter()
         if jobs:
             off, n_pre = shard.split(sc.num_paths_presim)
-            paths_pre, dpaths_pre = be.tangent_paths(sim, dslot, dinit, daux, 42 + sc.seed_offset, off, n_pre,
-                                                     sc._inject.get("pre", (None, None))[0])
+            paths_pre, dpaths_pre = dual_paths(42 + sc.seed_offset, off, n_pre, sc._inject.get("pre", (None, None))[0])
             plan = [(p_i, p, base._regression_schedule(p_i, p)) for p_i, p in jobs]
             plan = [(p_i, p, sched, base._regression_atoms(sched, p.asset_ids[0])) for p_i, p, sched in plan]
             x_ids = sorted({x for _, _, _, atoms in plan for _, x in atoms})
@@ -404,6 +417,32 @@ def run_with_tangent_book(sc):
             x_range = {x: (lo[i], hi[i]) for i, x in enumerate(x_ids)}
             for p_i, p, sched, atoms in plan:
                 S = p.get_num_states()
+                if p_i in storages:
+                    # the storage's backward induction in dual numbers (mcx_tangent_storage_lsm_step): every step rolls at most one
+                    # action date from the integer grid states along the base run's policy; old and new cache alternate
+                    st = base._storage_handle(p_i)
+                    W, dW = be.zeros(2, S, n_pre), be.zeros(2, NP, S, n_pre)
+                    decide = be.from_numpy(coeffs)
+                    cur = 0
+                    for (t_reg, r0, r1, _prod_idx, expo_idx), (num, x) in zip(sched, atoms):
+                        if r1 - r0 > 1:
+                            raise RuntimeError("internal: a storage step rolls at most one action date")
+                        xmin, xmax = x_range[x]
+                        degenerate = not (xmax > xmin)
+                        shift = 0.5 * (xmin + xmax) if not degenerate else xmin
+                        scale = 2.0 / (xmax - xmin) if not degenerate else 1.0
+                        roll = r0 if r1 > r0 else -1
+                        mom = shard.all_reduce_np(be.tangent_storage_lsm_step(book, st, roll, num, x, shift, scale, datoms, decide, paths_pre,
+                                                                              dpaths_pre, W[cur], dW[cur], W[1 - cur], dW[1 - cur], flags=lsm_flags))
+                        if roll >= 0:
+                            cur = 1 - cur
+                        if expo_idx is None:
+                            continue
+                        c, dc = _solve_dual_states(mom, K, S, shift, scale, degenerate, NP)
+                        o = base._expo_coeff_base[p_i] + expo_idx * S * K
+                        dcoeffs[o:o + S * K] = dc.reshape(NP, S * K).T
+                    del W, dW, decide
+                    continue
                 if S > 1:
                     # backward induction with the cashflow cache of every hypothetical state rolled in dual numbers along the
                     # frozen policy (mcx_tangent_lsm_step); the coefficient tangents of the exposure rows feed the main pass
@@ -440,8 +479,7 @@ def run_with_tangent_book(sc):
         t2 = time.perf_counter()
         t_pre += t2 - t1
         off, n_main = shard.split(sc.num_paths_mainsim)
-        paths, dpaths = be.tangent_paths(sim, dslot, dinit, daux, 43 + sc.seed_offset, off, n_main,
-                                         sc._inject.get("main", (None, None))[0])
+        paths, dpaths = dual_paths(43 + sc.seed_offset, off, n_main, sc._inject.get("main", (None, None))[0])
         # analytic Black-Scholes exposure events: which tangent slot of this pass is their sigma / their rate
         ev_param = None
         ev_kind = base.book_plan.events["kind"]
@@ -454,7 +492,10 @@ def run_with_tangent_book(sc):
                     rows_bs = np.arange(b0, b1)[ev_kind[b0:b1] == _abi.EV_EXPO_BS]
                     ev_param[rows_bs, 0] = sel.index(i_v) if i_v in sel else -1
                     ev_param[rows_bs, 1] = sel.index(i_r) if i_r in sel else -1
-        cfs, expo = be.tangent_eval(book, datoms, be.from_numpy(coeffs), be.from_numpy(dcoeffs), paths, dpaths, ev_param)
+        d_coeffs, d_dcoeffs = be.from_numpy(coeffs), be.from_numpy(dcoeffs)
+        cfs, expo = be.tangent_eval(book, datoms, d_coeffs, d_dcoeffs, paths, dpaths, ev_param)
+        for p_i in storages:                  # a storage owns no events: its dual walk adds to the images just written
+            be.tangent_storage_eval(book, base._storage_handle(p_i), base._storage_ops(p_i), datoms, d_coeffs, d_dcoeffs, paths, dpaths, cfs, expo)
         for ns_i, ns in enumerate(sc.netting_sets):
             prof = None
             coll = ns.is_collateralized()

@@ -121,8 +121,10 @@ class SimulationController:
         self._backend = backend
         for i, p in enumerate(products):
             p.product_id = i
-        if differentiate and any(getattr(p, "is_storage", False) for p in products):
-            raise NotImplementedError("sensitivities through the storage policy are not implemented (differentiate=True with a Storage)")
+        if differentiate and any(getattr(p, "is_storage", False) for p in products) \
+                and backend is not None and not hasattr(backend, "tangent_storage_eval"):
+            raise NotImplementedError(f"sensitivities through the storage policy run in forward mode on the HIP backend only: the "
+                                      f"{getattr(backend, 'name', type(backend).__name__)} backend has no mcx_tangent_storage_* entry points")
         if differentiate:
             self.model.requires_grad()
 
@@ -1301,6 +1303,31 @@ class SimulationController:
         self.last_state.update(paths=paths, cfs=cfs, expo=expo)
         return self._evaluate_all(self._shard, cfs, expo, paths)
 
+    def _storage_products(self):
+        return [p for p in self.products if getattr(p, "is_storage", False)]
+
+    def _differentiate_storage_book(self, run_with_tangent_book, no_form):
+        """a book that holds a storage is differentiated in forward mode or not at all: the reference's tape holds the storage
+        policy fixed, while a bump-and-revalue run would difference across decision flips (replaying S x dates x N decisions is
+        not built), and second-order differences of first-order passes inherit the same problem"""
+        why = None
+        if not hasattr(self.backend, "tangent_storage_eval"):
+            why = "the backend has no mcx_tangent_storage_* entry points"
+        elif not self.forward_mode:
+            why = "forward_mode is False and bump-and-revalue would difference across decision flips"
+        elif self.requires_higher_order_derivatives:
+            why = "second-order derivatives are differences of first-order passes across decision flips"
+        if why is None:
+            try:
+                return run_with_tangent_book(self)
+            except no_form as e:
+                why = f"the forward-mode pass cannot take this book ({e})"
+            except RuntimeError as e:                           # MCX_E_NOT_FUSABLE from the library: no tangent form
+                if getattr(e, "code", None) != _abi.E_NOT_FUSABLE:
+                    raise
+                why = f"the forward-mode kernels cannot take this book ({e})"
+        raise NotImplementedError(f"sensitivities through the storage policy are not implemented for this configuration: {why}")
+
     @single_threaded_host()
     def run_simulation(self) -> SimulationResults:
         if self.differentiate:
@@ -1308,6 +1335,8 @@ class SimulationController:
                                run_with_tangent_book, run_with_tangents, tangent_kernels_apply)
             if analytic_controller(self):
                 return run_analytic_with_autograd(self)             # PVMetric(ANALYTICAL): autograd on the closed form
+            if self._storage_products():
+                return self._differentiate_storage_book(run_with_tangent_book, _NoTangentForm)
             if self.requires_higher_order_derivatives:
                 from ..aad import run_second_order
                 return run_second_order(self)                       # Monte-Carlo metrics: differences of the first-order pass

@@ -14,7 +14,7 @@ from .. import _abi
 from ..common.enums import SimulationScheme
 from ..common.packages import FLOAT, device
 from ..request_interface.request_types import AtomicRequestType as RT
-from .model import AtomCoef, Model, SlotSpec
+from .model import AtomCoef, Model, SlotSpec, cexp, csqrt
 
 
 class SchwartzTwoFactorModel(Model):
@@ -81,6 +81,22 @@ class SchwartzTwoFactorModel(Model):
         cov = rho * math.sqrt(max(var_s * var_l, 0.0))
         return torch.tensor([[var_s, cov], [cov, var_l]], dtype=FLOAT, device=device)
 
+    def _cholesky_entries(self, scheme, delta_t):
+        """the lower factor of the correlation matrix (EULER) or of the per-dt covariance matrix (ANALYTICAL) in closed form:
+        [[sqrt(a), 0], [b / sqrt(a), sqrt(c - b^2 / a)]].  Complex-safe: rho (and under ANALYTICAL kappa and the volatilities) are
+        model parameters, so the factors carry tangents (mcx/aad.py evaluates this at theta + i h; csrc/kt_storage.hip kts_paths)."""
+        kappa, sig_s, sig_l, rho = self._pf(1), self._pf(2), self._pf(4), self._pf(5)
+        if scheme == SimulationScheme.ANALYTICAL:
+            dt = float(delta_t)
+            a = sig_s * sig_s * dt if abs(kappa) <= 1e-12 else sig_s * sig_s * (1.0 - cexp(-2.0 * kappa * dt)) / (2.0 * kappa)
+            c = sig_l * sig_l * dt
+            b = rho * csqrt(a * c)
+        else:
+            a, b, c = 1.0, rho, 1.0
+        l00 = csqrt(a)
+        l10 = b / l00
+        return [[l00, 0.0], [l10, csqrt(c - l10 * l10)]]
+
     # ---- native hooks -------------------------------------------------------------------------------------------
     def _slots(self):
         return [SlotSpec(_abi.MODEL_S2F, [self._pf(i) for i in range(6)] + [math.log(self._curve_value(self.t0()))], 3, 2)]
@@ -90,7 +106,7 @@ class SchwartzTwoFactorModel(Model):
 
     def _step_aux(self, scheme, t1, dt):
         kappa = self._pf(1)
-        decay = 1.0 if abs(kappa) <= 1e-12 else math.exp(-kappa * dt)
+        decay = 1.0 if abs(kappa) <= 1e-12 else cexp(-kappa * dt)
         return [[decay, math.log(self._curve_value(t1 + dt))]]
 
     def _atom(self, req, asset_id):
@@ -98,14 +114,14 @@ class SchwartzTwoFactorModel(Model):
         if k == RT.SPOT:
             return AtomCoef(col=0, b=1.0, c0=0.0, c1=1.0)                        # exp(log S)
         if k == RT.DISCOUNT_FACTOR:
-            return AtomCoef(a=math.exp(-r * (float(req.time1) - t0)))
+            return AtomCoef(a=cexp(-r * (float(req.time1) - t0)))
         if k == RT.NUMERAIRE:
-            return AtomCoef(a=math.exp(r * (float(req.time1) - t0)))
+            return AtomCoef(a=cexp(r * (float(req.time1) - t0)))
         if k == RT.FORWARD_RATE:
-            return AtomCoef(a=math.exp(r * (float(req.time2) - float(req.time1))))
+            return AtomCoef(a=cexp(r * (float(req.time2) - float(req.time1))))
         if k == RT.LIBOR_RATE:
             tau = float(req.time2) - float(req.time1)
-            return AtomCoef(a=(math.exp(r * tau) - 1.0) / tau)
+            return AtomCoef(a=(cexp(r * tau) - 1.0) / tau)
         raise NotImplementedError(f"Request type {k} not supported.")
 
     def _supports_scheme(self, scheme):

@@ -69,6 +69,7 @@ class SimPlan:
         self.n_steps = len(steps)
         self.aux = np.ascontiguousarray(np.stack(aux)) if aux else np.zeros((0, self.n_slots, _abi.AUX))
         self.chol = np.ascontiguousarray(np.stack(chols)) if chols else np.zeros((0, self.n_z, self.n_z))
+        self.chol_dt = [dt_ for dt_, _ in sorted(chol_key.items(), key=lambda kv: kv[1])]      # the dt behind every factor (None: dt-independent)
         self.init_state = np.array(model._initial_state(), dtype=np.float64)
         self.flags = _abi.FLAG_SMOOTHING if model.perform_smoothing else 0
 
