@@ -12,7 +12,7 @@
  *   RequestInterface.resolve_requests      request_interface.py:115-130   mcx_resolve_atoms / fused in K2
  *   SimulationController._evaluate_product controller/controller.py:385-471   mcx_eval_book           (K2)
  *   SimulationController._perform_regression_for_product  controller.py:294-383  mcx_lsm_stats, mcx_lsm_step (K3)
- *   Storage.compute_normalized_cashflows (gas storage)              products/storage.py:219-308   mcx_storage_lsm_run, mcx_storage_eval (K6)
+ *   Storage.compute_normalized_cashflows (gas storage)              products/storage.py:219-308   mcx_storage_lsm_run[_batch], mcx_storage_eval (K6)
  *   NettingSet.compute_unsecured_exposure_profiles  products/netting_set.py:156-184   (prologue of K4/K5)
  *   Metric._compute_mc_mean_and_error + PV/CE/EPE/ENE/CVA  metrics/<metric>.py   mcx_reduce_vector, mcx_reduce_profiles, mcx_reduce_cva (K4)
  *   PFEMetric.evaluate_numerically (torch.sort)     metrics/pfe_metric.py:49-73       mcx_select_hist  (K5)
@@ -652,6 +652,49 @@ typedef struct {
 int  mcx_storage_lsm_run(mcx_handle* h, mcx_book* book, const mcx_storage* st, const mcx_storage_lsm_date* h_dates, int32_t n_dates,
                          const double* d_paths, int64_t n_paths, int64_t ld, double* d_W, int64_t ld_w,
                          double* h_coeffs, int32_t* h_status, int32_t flags, void* stream);
+/* The backward inductions of MANY storages of one book at once.  Storages are independent, so step r of every storage's schedule
+ * runs in ONE launch (k6_step_batch, grid = tiles x jobs) followed by one launch that sums and solves (k6_finish_solve_batch, one
+ * block per job): the chain is max_j L_j steps long instead of sum_j L_j.  A job is one (storage, date) pair; per job the kernels do
+ * exactly what mcx_storage_lsm_step / _run do for that storage (same tiling mcx picks for n_paths, same summation order), so the
+ * results are bit-equal to the per-storage calls.  Storages of mixed n_states share a launch.
+ *   storage          index into storages[] (every one created on `book`); a storage appears at most once per step.
+ *   w_old, w_new     offsets in doubles of two [n_states][ld_w] blocks inside d_W (w_len doubles, zeroed by the caller before the
+ *                    first step): the step reads w_old and, when roll_date >= 0, writes w_new (distinct); the caller alternates a
+ *                    storage's two blocks at every step that rolls.  w_new is ignored when roll_date < 0.
+ *   other fields     as mcx_storage_lsm_date.
+ * mcx_storage_lsm_step_batch   one step: d_moments [n_jobs][mom_stride], row j = the NM_j = 2K-1 + n_states_j K moments of job j as
+ *                    mcx_storage_lsm_step writes them, zero behind them (mom_stride >= every NM_j): one all-reduce covers the step.
+ * mcx_storage_lsm_solve_batch  the K x K solves of one step from (all-reduced) d_moments, coefficients scattered to coeff_off;
+ *                    d_coeff_table (may be NULL): packed, job j's [n_states_j][K] block at sum_{i<j} n_states_i K; d_status [n_jobs].
+ * mcx_storage_lsm_run_batch    every step: jobs [h_step_begin[t], h_step_begin[t+1]) form step t.  The job table is uploaded once;
+ *                    per step (step, [all-reduce with a communicator of more than one rank on the handle], solve) are enqueued
+ *                    back to back, ONE synchronisation at the end.  h_coeffs: packed over ALL jobs as d_coeff_table; h_status
+ *                    [n_jobs] as in mcx_storage_lsm_run.
+ * Everything is checked on the host before the first launch (-2 and mcx_last_error, nothing enqueued): storage index in range and
+ * created on this book, roll_date < n_dates, atoms in range, coeff_off + n_states K <= n_coeffs, w_old / w_new inside
+ * [0, w_len - n_states ld_w] and distinct when rolling, ld >= n_paths, ld_w >= n_paths, no storage twice in one step.
+ * Partial sums: [job][tile][NM_j] in library scratch memory.  A step whose jobs need more than 64 MiB of them is split over several
+ * launches (whole jobs; the tiling of a job never shrinks, so results do not depend on the split).  The environment variable
+ * MCX_STORAGE_BATCH_PARTIAL_BYTES (a positive integer, read at each call) replaces the 64 MiB — for tests of the split; unset,
+ * nothing changes. */
+typedef struct {
+    int32_t storage;
+    int32_t roll_date, num_atom, x_atom, degenerate, reserved;
+    int64_t coeff_off[2];
+    int64_t w_old, w_new;
+    double  shift, scale, x0;
+} mcx_storage_lsm_job;
+int  mcx_storage_lsm_step_batch(mcx_handle* h, const mcx_book* book, const mcx_storage* const* storages, int32_t n_storages,
+                                const mcx_storage_lsm_job* h_jobs, int32_t n_jobs, const double* d_paths, int64_t n_paths, int64_t ld,
+                                double* d_W, int64_t ld_w, int64_t w_len, double* d_moments, int64_t mom_stride, int32_t flags,
+                                void* stream);
+int  mcx_storage_lsm_solve_batch(mcx_handle* h, mcx_book* book, const mcx_storage* const* storages, int32_t n_storages,
+                                 const mcx_storage_lsm_job* h_jobs, int32_t n_jobs, double* d_moments, int64_t mom_stride,
+                                 double* d_coeff_table, int32_t* d_status, void* stream);
+int  mcx_storage_lsm_run_batch(mcx_handle* h, mcx_book* book, const mcx_storage* const* storages, int32_t n_storages,
+                               const mcx_storage_lsm_job* h_jobs, const int32_t* h_step_begin, int32_t n_steps,
+                               const double* d_paths, int64_t n_paths, int64_t ld, double* d_W, int64_t ld_w, int64_t w_len,
+                               double* h_coeffs, int32_t* h_status, int32_t flags, void* stream);
 /* Main simulation: the realised state of every path walked through h_ops in order.  kind 0: action date `index` (cash / numeraire
  * ADDED to d_cfs[netting_set] when d_cfs is given); kind 1: exposure row `index` — the [n_states][K] block at coeff_off evaluated at
  * x_atom, interpolated at the realised state, divided by num_atom, ADDED to d_expo[netting_set][index] (controller.py:414-461).

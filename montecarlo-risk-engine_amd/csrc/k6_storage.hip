@@ -2,7 +2,7 @@
 //
 // The storage's Longstaff-Schwartz state is a real number s in [0, S-1] (position of the inventory in the volume window of the
 // date), so neither the exercise machine of k3_lsm.hip (integer states, one decision bit) nor the event program of k2_book.hip
-// fits.  Three kernels:
+// fits.  The kernels:
 //   k6_step          one backward date: every path rolls ALL S integer start states one action date forward (the next states and
 //                    volume changes of integer states are path-independent: the host's transition table, scalar loads), writes
 //                    W_new[s] = cash / numeraire + lerp(W_old, next state) and accumulates the moments of the regression.
@@ -11,11 +11,17 @@
 //   k6_finish_solve  sums the per-block partials and solves the K x K normal equations for S right-hand sides, lane s taking
 //                    state s (same algorithm as k3_solve_t: LU with partial pivoting, back-transformation of the shifted /
 //                    scaled basis, minimum-norm solution of the exactly rank-1 system of the calibration date).
+//   k6_step_batch / k6_finish_solve_batch   the same two for step r of MANY storages in one launch each (grid.y resp. grid.x = job):
+//                    the bodies of k6_step / k6_finish_solve as device functions, the job's record read with scalar loads.
 //   k6_eval          main simulation: the realised state of a path in a register, walked through the action dates and the
 //                    exposure rows; the date record and its [S][K] coefficient block are staged in LDS once per block and date.
 // Exact ties between candidates are the rule (a full store: inject == hold): every candidate goes through ONE inline function,
 // so tied candidates are bit-identical, and the first of [inject, hold, withdraw] wins as torch.argmax does.
 #include "mcx_internal.h"
+
+#include <stdlib.h>
+
+#include <algorithm>
 
 #define K6_MAX_S MCX_STORAGE_MAX_STATES
 #define K6_MAX_KNOTS MCX_STORAGE_MAX_KNOTS
@@ -78,7 +84,7 @@ __device__ __forceinline__ double k6_rate(const double* __restrict__ xs, const d
 }
 
 // ---- backward step ---------------------------------------------------------------------------------------------------
-struct K6StepArgs {
+struct K6StepArgs {                        // kernel argument of k6_step; one record of k6_step_batch's job table
     const double* __restrict__ paths;
     const double* __restrict__ W_old;
     double* __restrict__ W_new;
@@ -91,6 +97,7 @@ struct K6StepArgs {
     int64_t n, ld, ld_w;
     int32_t S, n_state, roll, is_last, f32_cache;
 };
+static_assert(sizeof(K6StepArgs) % 4 == 0, "read with ldk_struct");
 
 // one candidate of an integer start state: (next state, dv) wave-uniform, the price per lane.  -> cash, value, cached tail
 template <int K>
@@ -113,8 +120,10 @@ __device__ __forceinline__ void k6_step_candidate(const K6StepArgs& a, double ns
     value = cash + cont;
 }
 
+// the backward step of ONE storage for the block's tiles (blockIdx.x of gridDim.x): shared by k6_step and k6_step_batch, so the
+// per-path arithmetic, the wave_sum order and the FMA contraction of the two kernels are the same program text
 template <int K>
-__global__ __launch_bounds__(MCX_BLOCK) void k6_step(const K6StepArgs a)
+__device__ __forceinline__ void k6_step_body(const K6StepArgs a)          // (by value: k6_step then compiles to the code it had as a kernel of its own)
 {
     constexpr int NB = 2 * K - 1;
     __shared__ double rows[4][NB + K6_MAX_S * K];
@@ -172,6 +181,23 @@ __global__ __launch_bounds__(MCX_BLOCK) void k6_step(const K6StepArgs a)
         a.partials[(int64_t)blockIdx.x * NM + q] = (rows[0][q] + rows[1][q]) + (rows[2][q] + rows[3][q]);
 }
 
+template <int K>
+__global__ __launch_bounds__(MCX_BLOCK) void k6_step(const K6StepArgs a)
+{
+    k6_step_body<K>(a);
+}
+
+// step r of MANY storages in one launch: grid (tiles, jobs), blockIdx.y selects the job.  Its record is a complete K6StepArgs
+// (block-uniform: scalar loads) whose `partials` points at the job's own [tiles][NM_j] block, so every block does for its job
+// exactly what a k6_step block does for its single storage.  Jobs of one launch share paths and path count (the same tiling);
+// S, the roll and the atoms differ per job.
+template <int K>
+__global__ __launch_bounds__(MCX_BLOCK) void k6_step_batch(const K6StepArgs* __restrict__ jobs)
+{
+    const K6StepArgs a = ldk_struct(jobs + blockIdx.y);
+    k6_step_body<K>(a);
+}
+
 // ---- solve -----------------------------------------------------------------------------------------------------------
 struct K6Solve {
     double shift, scale, x0;
@@ -179,7 +205,8 @@ struct K6Solve {
     int32_t degenerate, S, date, pad;
 };
 
-// right-hand side s of the K x K system in m[] (k3_solve_t for one state; every lane factorises the same Gram matrix in registers)
+// right-hand side s of the K x K system in m[] (k3_solve_t for one state; every lane factorises the same Gram matrix in registers);
+// table: the system's own [S][K] block or nullptr, status: the system's own word
 template <int K>
 __device__ __forceinline__ void k6_solve_state(const double* __restrict__ m, const K6Solve& q, int s, double* __restrict__ coeffs,
                                                double* __restrict__ table, int32_t* __restrict__ status)
@@ -247,10 +274,10 @@ __device__ __forceinline__ void k6_solve_state(const double* __restrict__ m, con
             }
         }
     }
-    if (s == 0) status[q.date] = st;
+    if (s == 0) *status = st;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        if (table) table[((int64_t)q.date * q.S + s) * K + k] = out[k];
+        if (table) table[s * K + k] = out[k];
         if (st == 0) {
             if (q.off0 >= 0) coeffs[q.off0 + s * K + k] = out[k];
             if (q.off1 >= 0) coeffs[q.off1 + s * K + k] = out[k];
@@ -258,12 +285,13 @@ __device__ __forceinline__ void k6_solve_state(const double* __restrict__ m, con
     }
 }
 
-// n_blocks > 0: wave q of the block sums moment q over the step kernel's partials (fixed order) into LDS and mom_out;
+// n_blocks > 0: wave q of the block sums moment q over the step kernel's partials (fixed order) into LDS and mom_out, and zeroes
+// mom_out[nm .. mom_len) (the padding of a batched step's row; mom_len <= nm: none);
 // n_blocks == 0: the moments are read from mom_out (all-reduced by the caller).  do_solve: lane s < S then solves state s.
 template <int K>
-__global__ __launch_bounds__(1024) void k6_finish_solve(const double* __restrict__ partials, int n_blocks, double* __restrict__ mom_out,
-                                                        int do_solve, const K6Solve q, double* __restrict__ coeffs,
-                                                        double* __restrict__ table, int32_t* __restrict__ status)
+__device__ __forceinline__ void k6_finish_body(const double* __restrict__ partials, int n_blocks, double* __restrict__ mom_out, int mom_len,
+                                               int do_solve, const K6Solve& q, double* __restrict__ coeffs, double* __restrict__ table,
+                                               int32_t* __restrict__ status)
 {
     __shared__ double m[(2 * K - 1) + K6_MAX_S * K];
     const int nm = (2 * K - 1) + q.S * K;
@@ -275,11 +303,43 @@ __global__ __launch_bounds__(1024) void k6_finish_solve(const double* __restrict
             s = wave_sum(s);
             if (lane == 0) { m[j] = s; mom_out[j] = s; }
         }
+        for (int j = nm + threadIdx.x; j < mom_len; j += 1024) mom_out[j] = 0.0;
     } else {
         for (int j = threadIdx.x; j < nm; j += 1024) m[j] = mom_out[j];
     }
     __syncthreads();
     if (do_solve && (int)threadIdx.x < q.S) k6_solve_state<K>(m, q, threadIdx.x, coeffs, table, status);
+}
+
+// one storage: table [n_dates][S][K] and status [n_dates] of the run, the system is date q.date
+template <int K>
+__global__ __launch_bounds__(1024) void k6_finish_solve(const double* __restrict__ partials, int n_blocks, double* __restrict__ mom_out,
+                                                        int do_solve, const K6Solve q, double* __restrict__ coeffs,
+                                                        double* __restrict__ table, int32_t* __restrict__ status)
+{
+    k6_finish_body<K>(partials, n_blocks, mom_out, 0, do_solve, q, coeffs, table ? table + (int64_t)q.date * q.S * K : nullptr,
+                      status + q.date);
+}
+
+// one block per job of a batched step (the record is block-uniform: scalar loads).  Row blockIdx.x of `mom` ([jobs][mom_stride],
+// zero-padded behind the job's NM moments, so ONE all-reduce covers the step); the job's [S][K] block of the packed table at
+// tab_off; status[q.date], q.date = the job's index in the table of the call.  do_sum == 0: the moments are read (all-reduced).
+struct K6BatchSolve {
+    K6Solve q;
+    int64_t part_off, tab_off;          // doubles: the job's [n_blocks][NM] partials in the launch's buffer; its block of the table
+    int32_t n_blocks, pad;
+};
+static_assert(sizeof(K6BatchSolve) % 8 == 0, "read with ldk_struct");
+
+template <int K>
+__global__ __launch_bounds__(1024) void k6_finish_solve_batch(const K6BatchSolve* __restrict__ jobs, const double* __restrict__ partials,
+                                                              int do_sum, double* __restrict__ mom, int64_t mom_stride, int do_solve,
+                                                              double* __restrict__ coeffs, double* __restrict__ table,
+                                                              int32_t* __restrict__ status)
+{
+    const K6BatchSolve j = ldk_struct(jobs + blockIdx.x);
+    k6_finish_body<K>(partials + j.part_off, do_sum ? j.n_blocks : 0, mom + (int64_t)blockIdx.x * mom_stride, (int)mom_stride, do_solve,
+                      j.q, coeffs, table ? table + j.tab_off : nullptr, status + j.q.date);
 }
 
 // ---- main simulation -------------------------------------------------------------------------------------------------
@@ -538,6 +598,251 @@ extern "C" int mcx_storage_lsm_run(mcx_handle* h, mcx_book* b, const mcx_storage
     if (rc == 0 && (hipMemcpyAsync(h_coeffs, d_tab, tab_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
                     hipMemcpyAsync(h_status, d_st, st_bytes, hipMemcpyDeviceToHost, s) != hipSuccess)) { h->err = "mcx_storage_lsm_run: copy failed"; rc = -100; }
     if (hipStreamSynchronize(s) != hipSuccess && rc == 0) { h->err = "mcx_storage_lsm_run: synchronise failed"; rc = -100; }
+    return rc;
+}
+
+// ---- product-batched backward induction ---------------------------------------------------------------------------------------
+namespace {
+
+// upper bound (bytes) of the partial sums one k6_step_batch launch may need: a step whose jobs need more is split over several
+// launches, the tiling of a job never shrinks (a launch always takes at least one job: <= 4 n_cu tiles x 203 moments).
+// MCX_STORAGE_BATCH_PARTIAL_BYTES overrides it (include/mcx.h); unset or unparsable: 64 MiB.
+size_t k6_partial_cap()
+{
+    const char* e = getenv("MCX_STORAGE_BATCH_PARTIAL_BYTES");
+    if (e && *e) {
+        char* end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        if (end != e && *end == 0 && v > 0) return (size_t)v;
+    }
+    return (size_t)64 << 20;
+}
+constexpr int K6_MAX_LAUNCH_JOBS = 32768;     // gridDim.y
+
+struct K6Batch {
+    std::vector<K6StepArgs> step;          // partials: set by k6_batch_place once the launch buffer is known
+    std::vector<K6BatchSolve> solve;
+    std::vector<int32_t> launch_begin;     // launches [launch_begin[l], launch_begin[l+1]) never cross a step
+    size_t part_doubles = 0;               // of the largest launch
+    int64_t tab_doubles = 0;               // of the packed coefficient table
+    int widest = 0, nm_max = 0, tiles = 0; // jobs of the widest step; largest moment count; tiles per job
+};
+
+// every host-side check of a job table (nothing is launched before all of them pass) and its device image
+int k6_batch_build(mcx_handle* h, const mcx_book* b, const mcx_storage* const* storages, int32_t n_storages,
+                   const mcx_storage_lsm_job* h_jobs, const int32_t* h_step_begin, int32_t n_steps, const double* d_paths,
+                   int64_t n_paths, int64_t ld, double* d_W, int64_t ld_w, int64_t w_len, int32_t flags, const char* who, K6Batch& out)
+{
+    const int K = b->n_basis;
+    if (K < 1 || K > 6) MCX_FAIL(h, -3, "%s: unsupported basis size %d", who, K);
+    if (n_storages < 1) MCX_FAIL(h, -2, "%s: no storages", who);
+    if (ld < n_paths || ld_w < n_paths) MCX_FAIL(h, -2, "%s: leading dimension < n_paths", who);
+    if (h_step_begin[0] != 0) MCX_FAIL(h, -2, "%s: step table must start at job 0", who);
+    for (int q = 0; q < n_storages; ++q) {
+        if (!storages[q]) MCX_FAIL(h, -2, "%s: storage %d is null", who, q);
+        if (storages[q]->n_basis != K || storages[q]->n_coeffs != b->n_coeffs) MCX_FAIL(h, -2, "%s: storage %d was created on another book", who, q);
+    }
+    for (int t = 0; t < n_steps; ++t)
+        if (h_step_begin[t + 1] < h_step_begin[t]) MCX_FAIL(h, -2, "%s: step table not ascending at step %d", who, t);
+    const int n_jobs = h_step_begin[n_steps];
+    out.tiles = n_paths > 0 ? mcx_grid_for(n_paths, MCX_BLOCK, 4 * h->n_cu) : 0;
+    const size_t cap = k6_partial_cap() / sizeof(double);
+    out.step.resize((size_t)n_jobs); out.solve.resize((size_t)n_jobs);
+    out.launch_begin.assign(1, 0);
+    std::vector<int32_t> seen((size_t)n_storages, -1);
+    for (int t = 0; t < n_steps; ++t) {
+        size_t used = 0;
+        if (h_step_begin[t + 1] - h_step_begin[t] > out.widest) out.widest = h_step_begin[t + 1] - h_step_begin[t];
+        for (int j = h_step_begin[t]; j < h_step_begin[t + 1]; ++j) {
+            const mcx_storage_lsm_job& q = h_jobs[j];
+            if (q.storage < 0 || q.storage >= n_storages) MCX_FAIL(h, -2, "%s: job %d: storage index out of range", who, j);
+            if (seen[q.storage] == t) MCX_FAIL(h, -2, "%s: job %d: storage %d appears twice in step %d", who, j, q.storage, t);
+            seen[q.storage] = t;
+            const mcx_storage* st = storages[q.storage];
+            const int S = st->n_states, NM = (2 * K - 1) + S * K;
+            const bool roll = q.roll_date >= 0;
+            if (q.roll_date >= st->n_dates) MCX_FAIL(h, -2, "%s: job %d: roll date out of range", who, j);
+            if (q.num_atom < 0 || q.num_atom >= b->n_atoms || q.x_atom < 0 || q.x_atom >= b->n_atoms) MCX_FAIL(h, -2, "%s: job %d: atom out of range", who, j);
+            for (int w = 0; w < 2; ++w)
+                if (q.coeff_off[w] >= 0 && q.coeff_off[w] + (int64_t)S * K > b->n_coeffs) MCX_FAIL(h, -2, "%s: job %d: coefficient offset out of range", who, j);
+            const int64_t w_last = w_len - (int64_t)S * ld_w;
+            if (q.w_old < 0 || q.w_old > w_last) MCX_FAIL(h, -2, "%s: job %d: w_old outside d_W", who, j);
+            if (roll && (q.w_new < 0 || q.w_new > w_last)) MCX_FAIL(h, -2, "%s: job %d: w_new outside d_W", who, j);
+            if (roll && q.w_new == q.w_old) MCX_FAIL(h, -2, "%s: job %d: a roll needs a second cache block (w_new == w_old)", who, j);
+            // a new launch where the partials would pass the cap (or gridDim.y its limit); a launch holds at least one job
+            const size_t need = (size_t)out.tiles * NM;
+            if (j > out.launch_begin.back() && (used + need > cap || j - out.launch_begin.back() >= K6_MAX_LAUNCH_JOBS)) { out.launch_begin.push_back(j); used = 0; }
+            K6StepArgs& a = out.step[j];
+            memset(&a, 0, sizeof(a));
+            a.paths = d_paths; a.W_old = d_W + q.w_old; a.W_new = roll ? d_W + q.w_new : nullptr;
+            a.num = k6_flat(b->h_atoms[q.num_atom]); a.x = k6_flat(b->h_atoms[q.x_atom]);
+            a.shift = q.shift; a.scale = q.scale; a.n = n_paths; a.ld = ld; a.ld_w = ld_w; a.S = S; a.n_state = b->n_state;
+            a.f32_cache = (flags & MCX_LSM_F32_CACHE) ? 1 : 0;
+            a.roll = roll;
+            a.coeffs = b->d_coeffs; a.trans = st->d_trans; a.rnum = a.num; a.rx = a.x; a.c_inj = a.c_wd = 0.0; a.is_last = 1;
+            if (roll) {
+                const K6Date& d = st->h_dates[q.roll_date];
+                a.coeffs = b->d_coeffs + d.coeff_off; a.trans = st->d_trans + (size_t)q.roll_date * S * 6;
+                a.rnum = d.num; a.rx = d.x; a.c_inj = d.c_inj; a.c_wd = d.c_wd; a.is_last = d.is_last;
+            }
+            K6BatchSolve& v = out.solve[j];
+            memset(&v, 0, sizeof(v));
+            v.q.shift = q.shift; v.q.scale = q.scale; v.q.x0 = q.x0; v.q.off0 = q.coeff_off[0]; v.q.off1 = q.coeff_off[1];
+            v.q.degenerate = q.degenerate; v.q.S = S; v.q.date = j;
+            v.part_off = (int64_t)used; v.tab_off = out.tab_doubles; v.n_blocks = out.tiles;
+            used += need;
+            out.tab_doubles += (int64_t)S * K;
+            if (used > out.part_doubles) out.part_doubles = used;
+            if (NM > out.nm_max) out.nm_max = NM;
+        }
+        if (h_step_begin[t + 1] > out.launch_begin.back()) out.launch_begin.push_back(h_step_begin[t + 1]);
+    }
+    return 0;
+}
+
+void k6_batch_place(K6Batch& bt, double* d_part)
+{
+    for (size_t j = 0; j < bt.step.size(); ++j) bt.step[j].partials = d_part + bt.solve[j].part_off;
+}
+
+// the launches of jobs [j0, j1) of ONE step on the stream: k6_step_batch, then the fixed-order sums into rows j - j0 of d_mom
+// (with the solve when do_solve).  n_paths <= 0: the rows are zeroed.
+int k6_batch_step(mcx_handle* h, const mcx_book* b, const K6Batch& bt, const K6StepArgs* d_step, const K6BatchSolve* d_solve, int j0, int j1,
+                  const double* d_part, double* d_mom, int64_t mom_stride, int do_solve, double* d_tab, int32_t* d_st, hipStream_t s)
+{
+    const int K = b->n_basis;
+    if (j1 <= j0) return 0;
+    if (bt.tiles == 0) {
+        MCX_HIP(h, hipMemsetAsync(d_mom, 0, sizeof(double) * (size_t)(j1 - j0) * mom_stride, s));
+        if (do_solve) K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve_batch<KK>), dim3(j1 - j0), dim3(1024), 0, s, d_solve + j0, d_part, 0, d_mom,
+                                                         mom_stride, 1, b->d_coeffs, d_tab, d_st));
+        MCX_HIP(h, hipGetLastError());
+        return 0;
+    }
+    size_t l = std::upper_bound(bt.launch_begin.begin(), bt.launch_begin.end(), (int32_t)j0) - bt.launch_begin.begin() - 1;
+    for (; l + 1 < bt.launch_begin.size() && bt.launch_begin[l] < j1; ++l) {
+        const int a0 = bt.launch_begin[l], nj = bt.launch_begin[l + 1] - a0;
+        K6_DISPATCH(K, hipLaunchKernelGGL((k6_step_batch<KK>), dim3(bt.tiles, nj), dim3(MCX_BLOCK), 0, s, d_step + a0));
+        K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve_batch<KK>), dim3(nj), dim3(1024), 0, s, d_solve + a0, d_part, 1,
+                                          d_mom + (size_t)(a0 - j0) * mom_stride, mom_stride, do_solve, b->d_coeffs, d_tab, d_st));
+        MCX_HIP(h, hipGetLastError());
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int mcx_storage_lsm_step_batch(mcx_handle* h, const mcx_book* b, const mcx_storage* const* storages, int32_t n_storages,
+                                          const mcx_storage_lsm_job* h_jobs, int32_t n_jobs, const double* d_paths, int64_t n_paths,
+                                          int64_t ld, double* d_W, int64_t ld_w, int64_t w_len, double* d_moments, int64_t mom_stride,
+                                          int32_t flags, void* stream)
+{
+    if (!h || !b || !storages || !h_jobs || !d_paths || !d_W || !d_moments) return -1;
+    if (n_jobs <= 0) return 0;
+    const int32_t step_begin[2] = {0, n_jobs};
+    K6Batch bt;
+    const int rc = k6_batch_build(h, b, storages, n_storages, h_jobs, step_begin, 1, d_paths, n_paths, ld, d_W, ld_w, w_len, flags,
+                                  "mcx_storage_lsm_step_batch", bt);
+    if (rc != 0) return rc;
+    if (mom_stride < bt.nm_max) MCX_FAIL(h, -2, "mcx_storage_lsm_step_batch: mom_stride %lld < %d moments of a job", (long long)mom_stride, bt.nm_max);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t step_bytes = sizeof(K6StepArgs) * (size_t)n_jobs, solve_bytes = sizeof(K6BatchSolve) * (size_t)n_jobs;
+    double* d_part = (double*)mcx_scratch(h, 2, sizeof(double) * bt.part_doubles);
+    unsigned char* d_fb = (unsigned char*)mcx_scratch(h, 1, step_bytes + solve_bytes);
+    if (!d_part || !d_fb) return -100;
+    k6_batch_place(bt, d_part);
+    const K6StepArgs* d_step = (const K6StepArgs*)mcx_upload_call_data(h, bt.step.data(), step_bytes, d_fb, s);
+    const K6BatchSolve* d_solve = (const K6BatchSolve*)mcx_upload_call_data(h, bt.solve.data(), solve_bytes, d_fb + step_bytes, s);
+    if (!d_step || !d_solve) return -100;
+    return k6_batch_step(h, b, bt, d_step, d_solve, 0, n_jobs, d_part, d_moments, mom_stride, 0, nullptr, nullptr, s);     // stream-ordered
+}
+
+extern "C" int mcx_storage_lsm_solve_batch(mcx_handle* h, mcx_book* b, const mcx_storage* const* storages, int32_t n_storages,
+                                           const mcx_storage_lsm_job* h_jobs, int32_t n_jobs, double* d_moments, int64_t mom_stride,
+                                           double* d_coeff_table, int32_t* d_status, void* stream)
+{
+    if (!h || !b || !storages || !h_jobs || !d_moments || !d_status) return -1;
+    if (n_jobs <= 0) return 0;
+    const int K = b->n_basis;
+    if (K < 1 || K > 6) MCX_FAIL(h, -3, "mcx_storage_lsm_solve_batch: unsupported basis size %d", K);
+    std::vector<K6BatchSolve> solve((size_t)n_jobs);
+    std::vector<int32_t> seen((size_t)(n_storages > 0 ? n_storages : 0), 0);
+    int64_t tab = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const mcx_storage_lsm_job& q = h_jobs[j];
+        if (q.storage < 0 || q.storage >= n_storages || !storages[q.storage]) MCX_FAIL(h, -2, "mcx_storage_lsm_solve_batch: job %d: storage index out of range", j);
+        const mcx_storage* st = storages[q.storage];
+        if (st->n_basis != K || st->n_coeffs != b->n_coeffs) MCX_FAIL(h, -2, "mcx_storage_lsm_solve_batch: storage %d was created on another book", q.storage);
+        if (seen[q.storage]++) MCX_FAIL(h, -2, "mcx_storage_lsm_solve_batch: job %d: storage %d appears twice in the step", j, q.storage);
+        const int S = st->n_states;
+        if ((2 * K - 1) + S * K > mom_stride) MCX_FAIL(h, -2, "mcx_storage_lsm_solve_batch: job %d: mom_stride too small", j);
+        for (int w = 0; w < 2; ++w)
+            if (q.coeff_off[w] >= 0 && q.coeff_off[w] + (int64_t)S * K > b->n_coeffs) MCX_FAIL(h, -2, "mcx_storage_lsm_solve_batch: job %d: coefficient offset out of range", j);
+        K6BatchSolve& v = solve[j];
+        memset(&v, 0, sizeof(v));
+        v.q.shift = q.shift; v.q.scale = q.scale; v.q.x0 = q.x0; v.q.off0 = q.coeff_off[0]; v.q.off1 = q.coeff_off[1];
+        v.q.degenerate = q.degenerate; v.q.S = S; v.q.date = j;
+        v.tab_off = tab;
+        tab += (int64_t)S * K;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t solve_bytes = sizeof(K6BatchSolve) * (size_t)n_jobs;
+    void* d_fb = mcx_scratch(h, 1, solve_bytes);
+    if (!d_fb) return -100;
+    const K6BatchSolve* d_solve = (const K6BatchSolve*)mcx_upload_call_data(h, solve.data(), solve_bytes, d_fb, s);
+    if (!d_solve) return -100;
+    K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve_batch<KK>), dim3(n_jobs), dim3(1024), 0, s, d_solve, (const double*)nullptr, 0, d_moments,
+                                      mom_stride, 1, b->d_coeffs, d_coeff_table, d_status));
+    MCX_HIP(h, hipGetLastError());
+    return 0;          // stream-ordered
+}
+
+extern "C" int mcx_storage_lsm_run_batch(mcx_handle* h, mcx_book* b, const mcx_storage* const* storages, int32_t n_storages,
+                                         const mcx_storage_lsm_job* h_jobs, const int32_t* h_step_begin, int32_t n_steps,
+                                         const double* d_paths, int64_t n_paths, int64_t ld, double* d_W, int64_t ld_w, int64_t w_len,
+                                         double* h_coeffs, int32_t* h_status, int32_t flags, void* stream)
+{
+    if (!h || !b || !storages || !h_jobs || !h_step_begin || !d_paths || !d_W || !h_coeffs || !h_status) return -1;
+    if (n_steps <= 0) return 0;
+    K6Batch bt;
+    int rc = k6_batch_build(h, b, storages, n_storages, h_jobs, h_step_begin, n_steps, d_paths, n_paths, ld, d_W, ld_w, w_len, flags,
+                            "mcx_storage_lsm_run_batch", bt);
+    if (rc != 0) return rc;
+    const int n_jobs = h_step_begin[n_steps];
+    if (n_jobs <= 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t stride = bt.nm_max;
+    const size_t step_bytes = sizeof(K6StepArgs) * (size_t)n_jobs, solve_bytes = sizeof(K6BatchSolve) * (size_t)n_jobs;
+    const size_t tab_bytes = sizeof(double) * (size_t)bt.tab_doubles, st_bytes = sizeof(int32_t) * (size_t)n_jobs;
+    // slot 1: both job tables, the packed coefficient table, the status words; slot 2: partials; slot 3: the moments of a step
+    unsigned char* d_tabs = (unsigned char*)mcx_scratch(h, 1, step_bytes + solve_bytes + tab_bytes + st_bytes);
+    double* d_part = (double*)mcx_scratch(h, 2, sizeof(double) * bt.part_doubles);
+    double* d_mom = (double*)mcx_scratch(h, 3, sizeof(double) * (size_t)bt.widest * stride);
+    if (!d_tabs || !d_part || !d_mom) return -100;
+    k6_batch_place(bt, d_part);
+    const K6StepArgs* d_step = (const K6StepArgs*)d_tabs;
+    const K6BatchSolve* d_solve = (const K6BatchSolve*)(d_tabs + step_bytes);
+    double* d_tab = (double*)(d_tabs + step_bytes + solve_bytes);
+    int32_t* d_st = (int32_t*)(d_tabs + step_bytes + solve_bytes + tab_bytes);
+    // uploaded once, before the first launch (the host vectors die with this call, which ends in a synchronisation)
+    MCX_HIP(h, hipMemcpyAsync(d_tabs, bt.step.data(), step_bytes, hipMemcpyHostToDevice, s));
+    MCX_HIP(h, hipMemcpyAsync(d_tabs + step_bytes, bt.solve.data(), solve_bytes, hipMemcpyHostToDevice, s));
+    const bool multi = h->comm && h->comm_ranks > 1;
+    for (int t = 0; t < n_steps && rc == 0; ++t) {
+        const int j0 = h_step_begin[t], j1 = h_step_begin[t + 1];
+        if (j1 <= j0) continue;
+        rc = k6_batch_step(h, b, bt, d_step, d_solve, j0, j1, d_part, d_mom, stride, multi ? 0 : 1, d_tab, d_st, s);
+        if (rc != 0 || !multi) continue;
+        rc = mcx_allreduce_f64(h, d_mom, (int64_t)(j1 - j0) * stride, stream);          // ONE collective per step, stream-ordered
+        if (rc != 0) break;
+        const int K = b->n_basis;
+        K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve_batch<KK>), dim3(j1 - j0), dim3(1024), 0, s, d_solve + j0, (const double*)nullptr, 0,
+                                          d_mom, stride, 1, b->d_coeffs, d_tab, d_st));
+        if (hipGetLastError() != hipSuccess) { h->err = "mcx_storage_lsm_run_batch: launch failed"; rc = -100; }
+    }
+    if (rc == 0 && (hipMemcpyAsync(h_coeffs, d_tab, tab_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                    hipMemcpyAsync(h_status, d_st, st_bytes, hipMemcpyDeviceToHost, s) != hipSuccess)) { h->err = "mcx_storage_lsm_run_batch: copy failed"; rc = -100; }
+    if (hipStreamSynchronize(s) != hipSuccess && rc == 0) { h->err = "mcx_storage_lsm_run_batch: synchronise failed"; rc = -100; }
     return rc;
 }
 

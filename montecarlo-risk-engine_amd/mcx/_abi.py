@@ -126,3 +126,9 @@ STORAGE_LSM_DATE_DTYPE = np.dtype([("roll_date", "<i4"), ("num_atom", "<i4"), ("
 STORAGE_OP_DTYPE = np.dtype([("kind", "<i4"), ("index", "<i4"), ("num_atom", "<i4"), ("x_atom", "<i4"), ("coeff_off", "<i8")])
 assert STORAGE_LSM_DATE_DTYPE.itemsize == 56 and STORAGE_OP_DTYPE.itemsize == 24
 STORAGE_OP_ACTION, STORAGE_OP_EXPOSURE = 0, 1
+# mcx_storage_lsm_job: one (storage, date) pair of the product-batched backward induction (mcx_storage_lsm_step_batch,
+# mcx_storage_lsm_solve_batch, mcx_storage_lsm_run_batch)
+STORAGE_LSM_JOB_DTYPE = np.dtype([("storage", "<i4"), ("roll_date", "<i4"), ("num_atom", "<i4"), ("x_atom", "<i4"), ("degenerate", "<i4"),
+                                  ("reserved", "<i4"), ("coeff_off", "<i8", (2,)), ("w_old", "<i8"), ("w_new", "<i8"),
+                                  ("shift", "<f8"), ("scale", "<f8"), ("x0", "<f8")])
+assert STORAGE_LSM_JOB_DTYPE.itemsize == 80

@@ -27,6 +27,7 @@ _EXPORTS = [
     "mcx_box_muller", "mcx_tangent_european", "mcx_fused_create", "mcx_fused_destroy", "mcx_fused_num_records", "mcx_fused_run", "mcx_fused_eval_paths", "mcx_fused_run_device", "mcx_fused_eval_paths_device", "mcx_fused_set_timing", "mcx_fused_kernel_times", "mcx_fused_describe",
     "mcx_value_poly_fit", "mcx_book_collapse_values", "mcx_book_value_poly_info", "mcx_rows_minmax",
     "mcx_storage_create", "mcx_storage_destroy", "mcx_storage_lsm_step", "mcx_storage_lsm_run", "mcx_storage_eval",
+    "mcx_storage_lsm_step_batch", "mcx_storage_lsm_solve_batch", "mcx_storage_lsm_run_batch",
     "mcx_tangent_storage_lsm_step", "mcx_tangent_storage_eval", "mcx_tangent_paths_s2f",
     "mcx_reduce_vector", "mcx_reduce_profiles", "mcx_reduce_cva", "mcx_unsecured", "mcx_select_hist", "mcx_select_hist_dev", "mcx_select_narrow", "mcx_select_bracket", "mcx_select_hist_rows",
 ]
@@ -61,6 +62,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_storage_lsm_step.argtypes = [vp, vp, vp, i32, i32, i32, f64, f64, vp, i64, i64, vp, vp, i64, vp, i32, vp]
     lib.mcx_storage_lsm_run.argtypes = [vp, vp, vp, vp, i32, vp, i64, i64, vp, i64, vp, vp, i32, vp]
     lib.mcx_storage_eval.argtypes = [vp, vp, vp, vp, i32, vp, i64, i64, vp, vp, i64, vp]
+    lib.mcx_storage_lsm_step_batch.argtypes = [vp, vp, vp, i32, vp, i32, vp, i64, i64, vp, i64, i64, vp, i64, i32, vp]
+    lib.mcx_storage_lsm_solve_batch.argtypes = [vp, vp, vp, i32, vp, i32, vp, i64, vp, vp, vp]
+    lib.mcx_storage_lsm_run_batch.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i64, i64, vp, i64, i64, vp, vp, i32, vp]
     lib.mcx_tangent_storage_lsm_step.argtypes = [vp, vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp, i32, vp]
     lib.mcx_tangent_storage_eval.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i64, vp]
     lib.mcx_tangent_paths_s2f.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
@@ -641,6 +645,57 @@ class HipBackend:
             self.h, book.ptr, storage.ptr, _abi.ptr(dates), len(dates), paths.data_ptr(), n, _ld(paths), W.data_ptr(), W.shape[2],
             _abi.ptr(coeffs), _abi.ptr(status), int(flags), self._stream()), "mcx_storage_lsm_run")
         return coeffs, status
+
+    @staticmethod
+    def _storage_array(storages):
+        return (C.c_void_p * len(storages))(*[st.ptr.value for st in storages])
+
+    def storage_lsm_step_batch(self, book, storages, jobs: np.ndarray, paths: torch.Tensor, W: torch.Tensor, ld_w: int,
+                               mom_stride: int, flags: int = 0) -> torch.Tensor:
+        """one step of the product-batched induction (mcx_storage_lsm_step_batch): jobs = STORAGE_LSM_JOB_DTYPE, at most one per
+        storage, W the flat cache tensor the jobs' w_old / w_new point into -> moments [n_jobs][mom_stride] (device, stream-ordered)"""
+        jobs = np.ascontiguousarray(jobs, dtype=_abi.STORAGE_LSM_JOB_DTYPE)
+        assert W.dim() == 1 and W.is_contiguous()
+        moments = self.empty(len(jobs), int(mom_stride))
+        arr = self._storage_array(storages)
+        self._check(self.lib.mcx_storage_lsm_step_batch(
+            self.h, book.ptr, arr, len(storages), _abi.ptr(jobs), len(jobs), paths.data_ptr(), paths.shape[2], _ld(paths),
+            W.data_ptr(), int(ld_w), W.numel(), moments.data_ptr(), int(mom_stride), int(flags), self._stream()),
+            "mcx_storage_lsm_step_batch")
+        return moments
+
+    def storage_lsm_solve_batch(self, book, storages, jobs: np.ndarray, moments: torch.Tensor, table: torch.Tensor, status: torch.Tensor):
+        """the solves of one batched step from (all-reduced) moments [n_jobs][mom_stride] (mcx_storage_lsm_solve_batch): table =
+        float64 device tensor, packed [S_j][K] blocks of these jobs; status = int32 device tensor [n_jobs]; stream-ordered"""
+        jobs = np.ascontiguousarray(jobs, dtype=_abi.STORAGE_LSM_JOB_DTYPE)
+        K = book.plan.n_basis
+        assert moments.dim() == 2 and moments.shape[0] == len(jobs) and moments.is_contiguous()
+        assert table.dtype == torch.float64 and table.numel() == sum(storages[int(j)].n_states for j in jobs["storage"]) * K
+        assert status.dtype == torch.int32 and status.numel() == len(jobs)
+        arr = self._storage_array(storages)
+        self._check(self.lib.mcx_storage_lsm_solve_batch(
+            self.h, book.ptr, arr, len(storages), _abi.ptr(jobs), len(jobs), moments.data_ptr(), moments.shape[1],
+            table.data_ptr(), status.data_ptr(), self._stream()), "mcx_storage_lsm_solve_batch")
+
+    def storage_lsm_run_batch(self, book, storages, jobs: np.ndarray, step_begin: np.ndarray, paths: torch.Tensor, W: torch.Tensor,
+                              ld_w: int, flags: int = 0):
+        """the backward inductions of many storages in one call (mcx_storage_lsm_run_batch): step t = jobs[step_begin[t]:
+        step_begin[t+1]], W zeroed -> (packed coefficients: job j's [S_j][K] block at sum_{i<j} S_i K, status [n_jobs])"""
+        jobs = np.ascontiguousarray(jobs, dtype=_abi.STORAGE_LSM_JOB_DTYPE)
+        sb = np.ascontiguousarray(step_begin, dtype=np.int32)
+        assert len(sb) >= 1 and int(sb[-1]) == len(jobs) and W.dim() == 1 and W.is_contiguous()
+        K = book.plan.n_basis
+        S_of = np.array([st.n_states for st in storages], dtype=np.int64)
+        idx = jobs["storage"]
+        n_tab = int(S_of[idx[(idx >= 0) & (idx < len(storages))]].sum()) * K      # (a bad index is the library's to report)
+        coeffs = np.zeros(max(n_tab, 1))
+        status = np.zeros(max(len(jobs), 1), dtype=np.int32)
+        arr = self._storage_array(storages)
+        self._check(self.lib.mcx_storage_lsm_run_batch(
+            self.h, book.ptr, arr, len(storages), _abi.ptr(jobs), _abi.ptr(sb), len(sb) - 1, paths.data_ptr(), paths.shape[2], _ld(paths),
+            W.data_ptr(), int(ld_w), W.numel(), _abi.ptr(coeffs), _abi.ptr(status), int(flags), self._stream()),
+            "mcx_storage_lsm_run_batch")
+        return coeffs[:n_tab], status[:len(jobs)]
 
     def storage_eval(self, book, storage, ops: np.ndarray, paths: torch.Tensor, cfs, expo):
         """the main-simulation walk of one storage, ADDED into cfs [ns][n] / expo [ns][rows][n] (mcx_storage_eval)"""

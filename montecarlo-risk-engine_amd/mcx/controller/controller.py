@@ -50,6 +50,59 @@ def _key_to_double(keys: np.ndarray) -> np.ndarray:
     return bits.view(np.float64)
 
 
+def storage_lsm_dates(S: int, K: int, sched, atoms, x_range, reg_base: int, expo_base: int) -> np.ndarray:
+    """the backward induction of ONE storage as STORAGE_LSM_DATE_DTYPE records in induction order: per schedule entry
+    (t_reg, r0, r1, prod_idx, expo_idx) the rolled action date (-1: none), the regression atoms, the conditioning of the monomial
+    basis from the range of the explanatory variable, and the one or two blocks of the book's coefficient array the date's
+    [S][K] solution goes to.  Every action date is a regression date, so a step rolls at most ONE action date."""
+    dates = np.zeros(len(sched), dtype=_abi.STORAGE_LSM_DATE_DTYPE)
+    for j, ((t_reg, r0, r1, prod_idx, expo_idx), (num, x)) in enumerate(zip(sched, atoms)):
+        if r1 - r0 > 1:
+            raise RuntimeError("internal: a storage step rolls at most one action date")
+        xmin, xmax = x_range[x]
+        degenerate = not (xmax > xmin)
+        d = dates[j]
+        d["roll_date"], d["num_atom"], d["x_atom"], d["degenerate"] = (r0 if r1 > r0 else -1), num, x, int(degenerate)
+        d["shift"] = 0.5 * (xmin + xmax) if not degenerate else xmin
+        d["scale"] = 2.0 / (xmax - xmin) if not degenerate else 1.0
+        d["x0"] = xmin
+        d["coeff_off"][0] = -1 if prod_idx is None else reg_base + prod_idx * S * K
+        d["coeff_off"][1] = -1 if expo_idx is None else expo_base + expo_idx * S * K
+    return dates
+
+
+def storage_lsm_job_table(dates_of, S_of, ld_w: int):
+    """The job table of the product-batched storage induction (mcx_storage_lsm_run_batch), a plain function of the storages'
+    date tables (storage_lsm_dates): step r holds, in product order, the r-th date of every storage whose schedule is longer than
+    r, so the table is max_j L_j steps long.  Cache layout: storage j owns [2][S_j][ld_w] doubles of one flat buffer, behind the
+    blocks of the storages before it; a job reads half `w_old` and, when it rolls, writes the other half `w_new`, and the halves
+    change roles after every step that rolls (as mcx_storage_lsm_run alternates its two buffers).
+    -> (jobs STORAGE_LSM_JOB_DTYPE, step_begin int32 [n_steps + 1], job_of: per storage the indices of its jobs in schedule
+    order, w_len: doubles of the cache buffer)"""
+    n = len(dates_of)
+    L = np.array([len(d) for d in dates_of], dtype=np.int64)
+    S_arr = np.asarray(S_of, dtype=np.int64)
+    n_steps = int(L.max()) if n else 0
+    active = np.arange(n_steps)[None, :] < L[:, None]                              # [storage][step]
+    within = np.cumsum(active, axis=0) - active                                    # active storages before j in step r
+    step_begin = np.concatenate([[0], np.cumsum(active.sum(axis=0))]).astype(np.int32)
+    base = 2 * ld_w * np.concatenate([[0], np.cumsum(S_arr)])
+    jobs = np.zeros(int(step_begin[-1]), dtype=_abi.STORAGE_LSM_JOB_DTYPE)
+    job_of = []
+    for j, d in enumerate(dates_of):
+        dest = step_begin[:L[j]].astype(np.int64) + within[j, :L[j]]
+        job_of.append(dest)
+        rolls = d["roll_date"] >= 0
+        cur = (np.cumsum(rolls) - rolls) % 2                                       # the half that holds the cache before the step
+        blk = S_arr[j] * ld_w
+        jobs["storage"][dest] = j
+        for f in ("roll_date", "num_atom", "x_atom", "degenerate", "coeff_off", "shift", "scale", "x0"):
+            jobs[f][dest] = d[f]
+        jobs["w_old"][dest] = base[j] + cur * blk
+        jobs["w_new"][dest] = base[j] + (1 - cur) * blk
+    return jobs, step_begin, job_of, int(base[-1])
+
+
 class SimulationController:
     @single_threaded_host()
     def __init__(self, netting_sets: Sequence[NettingSet], model: Model, risk_metrics: RiskMetrics,
@@ -107,6 +160,8 @@ class SimulationController:
         self.main_plan = "auto"
         self.materialize = False     # also write paths / cashflows / exposures in the fused pass (inspection, tests)
         self.batch_lsm = True        # product-batched LSM pre-simulation (one launch per backward step of the whole book)
+        self.batch_storage_lsm = True        # the same for gas storages: two or more of them share the launches of a step
+        self.storage_lsm_route = None        # "batch" / "single": the route the last storage pre-simulation took
         self.forward_mode = True     # differentiate=True: dual-number pass where it exists, bump-and-revalue otherwise
         # The reference compiles nothing: every run_simulation() sees the current state of its products / metrics.  Re-using the
         # compiled descriptors and the uploaded book of the previous run is an opt-in for callers that re-run an UNCHANGED
@@ -556,8 +611,14 @@ class SimulationController:
             lo, hi = g[:, :, 0].min(axis=0), g[:, :, 1].max(axis=0)
             x_range = {x: (lo[i], hi[i]) for i, x in enumerate(x_ids)}
         lsm_flags = (_abi.LSM_MFMA if self.use_mfma else 0) | (_abi.LSM_F32_CACHE if self.reference_float32_cf_cache else 0)
-        for p_i, p, sched, atoms in storage_jobs:
-            self._storage_regression(shard, p_i, p, sched, atoms, x_range, paths, n_local, K, lsm_flags)
+        if storage_jobs:
+            if self.batch_storage_lsm and len(storage_jobs) >= 2 and hasattr(be, "storage_lsm_run_batch"):
+                self.storage_lsm_route = "batch"
+                self._storage_regression_batched(shard, storage_jobs, x_range, paths, n_local, K, lsm_flags)
+            else:
+                self.storage_lsm_route = "single"
+                for p_i, p, sched, atoms in storage_jobs:
+                    self._storage_regression(shard, p_i, p, sched, atoms, x_range, paths, n_local, K, lsm_flags)
         if not jobs:
             return
         if self.batch_lsm and not self.use_mfma and len(jobs) >= 4:       # (one or two products: the per-product loop has less fixed cost per step)
@@ -599,30 +660,19 @@ class SimulationController:
                                                                            self.product_to_netting_set_idx[p_i])
         return hit
 
-    def _storage_regression(self, shard: Shard, p_i, p, sched, atoms, x_range, paths, n_local: int, K: int, lsm_flags: int):
+    def _storage_regression(self, shard: Shard, p_i, p, sched, atoms, x_range, paths, n_local: int, K: int, lsm_flags: int,
+                            on_device: bool = True):
         """backward induction of one storage (controller.py:294-383 with the storage's compute_normalized_cashflows).  Every
         action date is a regression date, so a step rolls at most ONE action date, from the integer grid states.  One rank: the
-        whole induction in one library call; several ranks (or a singular system on the device): per date step -> all-reduce ->
-        host solve."""
+        whole induction in one library call; several ranks (or a singular system on the device, or on_device=False: the batched
+        route repeating a storage whose device solve reported one): per date step -> all-reduce -> host solve."""
         be = self.backend
         S = p.get_num_states()
         st = self._storage_handle(p_i)
-        dates = np.zeros(len(sched), dtype=_abi.STORAGE_LSM_DATE_DTYPE)
-        for j, ((t_reg, r0, r1, prod_idx, expo_idx), (num, x)) in enumerate(zip(sched, atoms)):
-            if r1 - r0 > 1:
-                raise RuntimeError("internal: a storage step rolls at most one action date")
-            xmin, xmax = x_range[x]
-            degenerate = not (xmax > xmin)
-            d = dates[j]
-            d["roll_date"], d["num_atom"], d["x_atom"], d["degenerate"] = (r0 if r1 > r0 else -1), num, x, int(degenerate)
-            d["shift"] = 0.5 * (xmin + xmax) if not degenerate else xmin
-            d["scale"] = 2.0 / (xmax - xmin) if not degenerate else 1.0
-            d["x0"] = xmin
-            d["coeff_off"][0] = -1 if prod_idx is None else self._reg_coeff_base[p_i] + prod_idx * S * K
-            d["coeff_off"][1] = -1 if expo_idx is None else self._expo_coeff_base[p_i] + expo_idx * S * K
+        dates = storage_lsm_dates(S, K, sched, atoms, x_range, self._reg_coeff_base[p_i], self._expo_coeff_base[p_i])
         W = be.zeros(2, S, n_local)
         coeffs = None
-        if shard.world == 1:
+        if shard.world == 1 and on_device:
             coeffs, status = be.storage_lsm_run(self.book, st, dates, paths, W, flags=lsm_flags)
             if status.any():
                 coeffs = None
@@ -646,6 +696,49 @@ class SimulationController:
                 p.regression_coeffs[prod_idx] = torch.from_numpy(coeffs[j].copy())
             if expo_idx is not None:
                 self.regression_coeffs[p_i][expo_idx] = torch.from_numpy(coeffs[j].copy())
+
+    def _storage_regression_batched(self, shard: Shard, storage_jobs, x_range, paths, n_local: int, K: int, lsm_flags: int):
+        """The backward inductions of ALL storages at once (csrc/k6_storage.hip k6_step_batch / k6_finish_solve_batch): storages
+        are independent, so step r of every schedule runs in one launch and the chain is max_j L_j steps long, not sum_j L_j.
+        One rank: one library call (mcx_storage_lsm_run_batch).  Several ranks: per step mcx_storage_lsm_step_batch, the moments of
+        all its jobs across the ranks in ONE all-reduce, mcx_storage_lsm_solve_batch on the device.  Per (storage, date) the
+        arithmetic is that of _storage_regression's device route; a storage whose device solve reports a singular system is
+        repeated alone through the host-solve loop."""
+        be = self.backend
+        S_of = [p.get_num_states() for _, p, _, _ in storage_jobs]
+        handles = [self._storage_handle(p_i) for p_i, _, _, _ in storage_jobs]
+        dates_of = [storage_lsm_dates(S, K, sched, atoms, x_range, self._reg_coeff_base[p_i], self._expo_coeff_base[p_i])
+                    for S, (p_i, p, sched, atoms) in zip(S_of, storage_jobs)]
+        ld_w = max(n_local, 1)
+        jobs, step_begin, job_of, w_len = storage_lsm_job_table(dates_of, S_of, ld_w)
+        tab_begin = np.concatenate([[0], np.cumsum(np.asarray(S_of, dtype=np.int64)[jobs["storage"]] * K)])
+        W = be.zeros(max(w_len, 1))
+        if shard.world == 1:
+            table, status = be.storage_lsm_run_batch(self.book, handles, jobs, step_begin, paths, W, ld_w, flags=lsm_flags)
+        else:
+            stride = (2 * K - 1) + K * max(S_of)                  # one zero-padded row per job: one all-reduce per step
+            table_d = be.zeros(int(tab_begin[-1]))
+            status_d = be.zeros(len(jobs), dtype=torch.int32)
+            for t_ in range(len(step_begin) - 1):
+                j0, j1 = int(step_begin[t_]), int(step_begin[t_ + 1])
+                mom = be.storage_lsm_step_batch(self.book, handles, jobs[j0:j1], paths, W, ld_w, stride, flags=lsm_flags)
+                shard.all_reduce_(mom)
+                be.storage_lsm_solve_batch(self.book, handles, jobs[j0:j1], mom, table_d[int(tab_begin[j0]):int(tab_begin[j1])],
+                                           status_d[j0:j1])
+            table, status = table_d.cpu().numpy(), status_d.cpu().numpy()
+        for j, (p_i, p, sched, atoms) in enumerate(storage_jobs):
+            if status[job_of[j]].any():
+                self.storage_lsm_singular_retries = getattr(self, "storage_lsm_singular_retries", 0) + 1
+                self._storage_regression(shard, p_i, p, sched, atoms, x_range, paths, n_local, K, lsm_flags, on_device=False)
+                continue
+            SK = S_of[j] * K
+            for r, (t_reg, r0, r1, prod_idx, expo_idx) in enumerate(sched):
+                b0 = int(tab_begin[job_of[j][r]])
+                c = table[b0:b0 + SK].reshape(S_of[j], K)
+                if prod_idx is not None:
+                    p.regression_coeffs[prod_idx] = torch.from_numpy(c.copy())
+                if expo_idx is not None:
+                    self.regression_coeffs[p_i][expo_idx] = torch.from_numpy(c.copy())
 
     def _storage_ops(self, p_i: int) -> np.ndarray:
         """the walk of the realised state through the main simulation (controller.py:399-461): action dates up to and including

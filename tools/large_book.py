@@ -168,7 +168,8 @@ def main():
         out = dict(book=args.book, products=len(products), counts=counts, storages=args.storages, paths=args.paths, exposure_points=args.exposure_points,
                    timeline_size=int(sc.simulation_timeline.numel()), construct_s=t1 - t0, run_s=t2 - t1,
                    products_per_second=len(products) / (t2 - t1), timings=sc.timings, prepare=getattr(sc, 'prepare_timings', None),
-                   lsm_singular_retries=getattr(sc, 'lsm_singular_retries', 0))
+                   lsm_singular_retries=getattr(sc, 'lsm_singular_retries', 0), storage_lsm_route=getattr(sc, 'storage_lsm_route', None),
+                   storage_lsm_singular_retries=getattr(sc, 'storage_lsm_singular_retries', 0))
         name = ns.get_name()
         if args.book == "ee":
             epe, pfe = np.asarray(res.get_results(name, mets[0].get_name())), np.asarray(res.get_results(name, mets[1].get_name()))
