@@ -2,11 +2,12 @@
 //
 // The reference sorts all N exposures per date (`torch.sort`, metrics/pfe_metric.py:61-66) to read x_(ceil(qN)-1) and its
 // two neighbours.  Here each pass histograms one digit of the order-preserving uint64 image of the doubles; the host
-// walks the digits (6 passes of 11/11/11/11/11/9 bits), narrowing up to three rank prefixes per date at once.  Histograms
-// are integer counters: exact, order-independent and all-reducible across GPUs (no path data leaves a GPU).
+// walks the digits (6 passes of 11/11/11/11/11/9 bits), narrowing up to K5_MAX_SEL = 4 rank prefixes per date at once (the
+// PFE metric uses three).  Histograms are integer counters: exact, order-independent and all-reducible across GPUs (no path
+// data leaves a GPU).
 //
-// Per block: an LDS histogram [n_sel][2^bits] of u32 (<= 24 KB), wave-coalesced 512-B row reads, LDS integer atomics,
-// then one global u64 atomic per non-empty bin.
+// Per block: an LDS histogram [n_sel][2^bits] of u32 (dynamic LDS: 24 KiB for three selections of an 11-bit digit, 32 KiB for
+// four), wave-coalesced 512-B row reads, LDS integer atomics, then one global u64 atomic per non-empty bin.
 #include "mcx_internal.h"
 
 namespace {
