@@ -651,11 +651,10 @@ static int lsm_step_launch(mcx_handle* h, const mcx_book* b, int32_t product, in
     if (n_paths <= 0) { MCX_HIP(h, hipMemsetAsync(d_moments, 0, sizeof(double) * NM, s)); return 0; }
     const int grid = mcx_grid_for(n_paths, MCX_BLOCK, 4 * h->n_cu);
     if ((size_t)grid * NM * sizeof(double) > h->ws_bytes) MCX_FAIL(h, -2, "%s: workspace too small", who);
-    auto flat = [&](int id) { DevAtom o; const mcx_atom& q = b->h_atoms[id]; o.t_idx = q.t_idx; o.col = q.col; o.a = q.a; o.d = q.d; o.b = q.b; o.c0 = q.c0; o.c1 = q.c1; return o; };
     K3Args a;
     a.etab = nullptr;
     a.terms = b->d_terms; a.events = b->d_events + pr.cf_begin; a.atoms = b->d_atoms; a.coeffs = b->d_coeffs; a.paths = d_paths;
-    a.W = d_W; a.partials = h->d_ws; a.num = flat(num_atom); a.x = flat(x_atom); a.shift = shift; a.scale = scale;
+    a.W = d_W; a.partials = h->d_ws; a.num = mcx_flat_atom(b->h_atoms[num_atom]); a.x = mcx_flat_atom(b->h_atoms[x_atom]); a.shift = shift; a.scale = scale;
     a.n = n_paths; a.ld = ld; a.ld_w = ld_w; a.roll_begin = roll_begin; a.roll_end = roll_end; a.n_basis = K; a.n_state = b->n_state;
     a.f32_cache = (flags & MCX_LSM_F32_CACHE) ? 1 : 0; a.bridge = b->d_bridge;
     a.ex_mode = b->ex_mode; a.ex_bits = b->d_ex_bits; a.ex_ld = b->ex_ld; a.ev_base = pr.cf_begin;
@@ -766,7 +765,6 @@ static int lsm_step_batch_impl(mcx_handle* h, const mcx_book* b, const mcx_lsm_j
         if (d_moments) MCX_HIP(h, hipMemsetAsync(d_moments, 0, sizeof(double) * (size_t)n_jobs * NM, s));
         return 0;
     }
-    auto flat = [&](int id) { DevAtom o; const mcx_atom& q = b->h_atoms[id]; o.t_idx = q.t_idx; o.col = q.col; o.a = q.a; o.d = q.d; o.b = q.b; o.c0 = q.c0; o.c1 = q.c1; return o; };
     std::vector<K3Job> jobs((size_t)n_jobs);
     for (int j = 0; j < n_jobs; ++j) {
         const mcx_lsm_job& q = h_jobs[j];
@@ -778,7 +776,7 @@ static int lsm_step_batch_impl(mcx_handle* h, const mcx_book* b, const mcx_lsm_j
         if (q.w_offset < 0 || q.w_offset + (int64_t)S * ld_w > w_len) MCX_FAIL(h, -2, "mcx_lsm_step_batch: job %d cache block outside d_W", j);
         K3Job& o = jobs[j];
         o.ev_off = pr.cf_begin; o.roll_begin = q.roll_begin; o.roll_end = q.roll_end; o.pad = 0; o.w_off = q.w_offset;
-        o.shift = q.shift; o.scale = q.scale; o.num = flat(q.num_atom); o.x = flat(q.x_atom);
+        o.shift = q.shift; o.scale = q.scale; o.num = mcx_flat_atom(b->h_atoms[q.num_atom]); o.x = mcx_flat_atom(b->h_atoms[q.x_atom]);
     }
     // few paths per product are the norm for big books: one block per 256 paths, capped
     int bpj = mcx_grid_for(n_paths, MCX_BLOCK, 64);
@@ -937,7 +935,6 @@ extern "C" int mcx_lsm_run_batch(mcx_handle* h, mcx_book* b, const mcx_lsm_job* 
         if (NM > nm_max) nm_max = NM;
         if (chunk > widest) widest = chunk;
     }
-    auto flat = [&](int id) { DevAtom o; const mcx_atom& q = b->h_atoms[id]; o.t_idx = q.t_idx; o.col = q.col; o.a = q.a; o.d = q.d; o.b = q.b; o.c0 = q.c0; o.c1 = q.c1; return o; };
     std::vector<K3Job> jobs((size_t)n_jobs);
     std::vector<K3SolveJob> solves((size_t)n_jobs);
     for (int t = 0; t < n_steps; ++t) {
@@ -952,7 +949,7 @@ extern "C" int mcx_lsm_run_batch(mcx_handle* h, mcx_book* b, const mcx_lsm_job* 
             if (q.w_offset < 0 || q.w_offset + (int64_t)S * ld_w > w_len) MCX_FAIL(h, -2, "mcx_lsm_run_batch: job %d cache block outside d_W", j);
             K3Job& o = jobs[j];
             o.ev_off = pr.cf_begin; o.roll_begin = q.roll_begin; o.roll_end = q.roll_end; o.pad = 0; o.w_off = q.w_offset;
-            o.shift = q.shift; o.scale = q.scale; o.num = flat(q.num_atom); o.x = flat(q.x_atom);
+            o.shift = q.shift; o.scale = q.scale; o.num = mcx_flat_atom(b->h_atoms[q.num_atom]); o.x = mcx_flat_atom(b->h_atoms[q.x_atom]);
             const mcx_lsm_solve_job& v = h_solve[j];
             for (int w = 0; w < 2; ++w)
                 if (v.coeff_off[w] >= 0 && v.coeff_off[w] + (int64_t)S * K > b->n_coeffs) MCX_FAIL(h, -2, "mcx_lsm_run_batch: job %d coefficient offset out of range", j);

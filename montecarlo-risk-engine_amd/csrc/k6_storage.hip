@@ -17,23 +17,13 @@
 //                    exposure rows; the date record and its [S][K] coefficient block are staged in LDS once per block and date.
 // Exact ties between candidates are the rule (a full store: inject == hold): every candidate goes through ONE inline function,
 // so tied candidates are bit-identical, and the first of [inject, hold, withdraw] wins as torch.argmax does.
-#include "mcx_internal.h"
+// The per-path arithmetic up to the candidates, the date record and its host checks live in k6_common.h, which kt_storage.hip
+// (the tangent images of k6_step and k6_eval) shares.
+#include "k6_common.h"
 
 #include <stdlib.h>
 
 #include <algorithm>
-
-#define K6_MAX_S MCX_STORAGE_MAX_STATES
-#define K6_MAX_KNOTS MCX_STORAGE_MAX_KNOTS
-
-struct K6Date {                 // device image of mcx_storage_date, atoms flattened
-    double vmin, step, nvmin, nvmax, nscale, period, c_inj, c_wd;
-    double inj_x[K6_MAX_KNOTS], inj_r[K6_MAX_KNOTS], wd_x[K6_MAX_KNOTS], wd_r[K6_MAX_KNOTS];
-    DevAtom num, x;
-    int64_t coeff_off;
-    int32_t n_inj, n_wd, is_last, pad;
-};
-static_assert(sizeof(K6Date) % 8 == 0, "copied to LDS in dwords");
 
 struct mcx_storage {
     int n_states, n_dates, netting_set, n_basis;
@@ -44,44 +34,6 @@ struct mcx_storage {
 };
 
 namespace {
-
-template <int K>
-__device__ __forceinline__ double k6_poly(const double* __restrict__ c, double x)
-{
-    double v = 0.0, xp = 1.0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) { v = fma(c[k], xp, v); xp *= x; }
-    return v;
-}
-// the same with a wave-uniform coefficient row (scalar loads)
-template <int K>
-__device__ __forceinline__ double k6_poly_uniform(const double* __restrict__ c, double x)
-{
-    double v = 0.0, xp = 1.0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) { v = fma(ldk(c + k), xp, v); xp *= x; }
-    return v;
-}
-
-// piecewise-linear rate at volume v (storage_helpers.py interpolate_rate_tensor): segment = the last knot below v, clamped to
-// the first / last segment; weight 0 where the segment's knots coincide under torch.isclose; flat outside the knots.  The knots
-// are wave-uniform, v is per lane: selects, no dynamic indexing.
-__device__ __forceinline__ double k6_rate(const double* __restrict__ xs, const double* __restrict__ rs, int n, double v)
-{
-    if (n == 1) return rs[0];
-    double x0 = xs[0], x1 = xs[1], y0 = rs[0], y1 = rs[1];
-    for (int j = 1; j < n - 1; ++j) {
-        const bool m = xs[j] < v;
-        x0 = m ? xs[j] : x0; x1 = m ? xs[j + 1] : x1;
-        y0 = m ? rs[j] : y0; y1 = m ? rs[j + 1] : y1;
-    }
-    const bool close = fabs(x0 - x1) <= 1e-8 + 1e-5 * fabs(x1);
-    const double w = close ? 0.0 : (v - x0) / (x1 - x0);
-    double r = y0 + w * (y1 - y0);
-    r = v <= xs[0] ? rs[0] : r;
-    r = v >= xs[n - 1] ? rs[n - 1] : r;
-    return r;
-}
 
 // ---- backward step ---------------------------------------------------------------------------------------------------
 struct K6StepArgs {                        // kernel argument of k6_step; one record of k6_step_batch's job table
@@ -98,27 +50,6 @@ struct K6StepArgs {                        // kernel argument of k6_step; one re
     int32_t S, n_state, roll, is_last, f32_cache;
 };
 static_assert(sizeof(K6StepArgs) % 4 == 0, "read with ldk_struct");
-
-// one candidate of an integer start state: (next state, dv) wave-uniform, the price per lane.  -> cash, value, cached tail
-template <int K>
-__device__ __forceinline__ void k6_step_candidate(const K6StepArgs& a, double ns, double dv, double price, double spot, int64_t i,
-                                                  double& cash, double& value, double& tail)
-{
-    const double b = fmin(fmax(ns, 0.0), (double)(a.S - 1));
-    const double fl = floor(b), w = b - fl;
-    const int lo = (int)fl, hi = (int)ceil(b);
-    double cont = 0.0;
-    if (!a.is_last) {
-        const double g_lo = k6_poly_uniform<K>(a.coeffs + lo * K, spot);
-        const double g_hi = hi != lo ? k6_poly_uniform<K>(a.coeffs + hi * K, spot) : g_lo;
-        cont = g_lo + w * (g_hi - g_lo);
-    }
-    const double w_lo = a.W_old[(int64_t)lo * a.ld_w + i];
-    const double w_hi = hi != lo ? a.W_old[(int64_t)hi * a.ld_w + i] : w_lo;
-    tail = w_lo + w * (w_hi - w_lo);
-    cash = -dv * price;
-    value = cash + cont;
-}
 
 // the backward step of ONE storage for the block's tiles (blockIdx.x of gridDim.x): shared by k6_step and k6_step_batch, so the
 // per-path arithmetic, the wave_sum order and the FMA contraction of the two kernels are the same program text
@@ -152,10 +83,11 @@ __device__ __forceinline__ void k6_step_body(const K6StepArgs a)          // (by
             if (a.roll) {
                 const double* __restrict__ t = a.trans + s * 6;
                 const double ns0 = ldk(t + 0), dv0 = ldk(t + 1), ns1 = ldk(t + 2), dv1 = ldk(t + 3), ns2 = ldk(t + 4), dv2 = ldk(t + 5);
-                double c0, v0, t0, c1, v1, t1, c2, v2, t2;
-                k6_step_candidate<K>(a, ns0, dv0, p_inj, spot, i, c0, v0, t0);                          // inject
-                k6_step_candidate<K>(a, ns1, dv1, dv1 >= 0.0 ? p_inj : p_wd, spot, i, c1, v1, t1);      // hold
-                k6_step_candidate<K>(a, ns2, dv2, p_wd, spot, i, c2, v2, t2);                          // withdraw
+                double c0, v0, t0, c1, v1, t1, c2, v2, t2, f;
+                int lo, hi;                                                // (where the tail was read: the tangent kernel's)
+                k6_step_candidate<K>(a.coeffs, a.W_old, a.ld_w, a.S, a.is_last, ns0, dv0, p_inj, spot, i, c0, v0, t0, lo, hi, f);                      // inject
+                k6_step_candidate<K>(a.coeffs, a.W_old, a.ld_w, a.S, a.is_last, ns1, dv1, dv1 >= 0.0 ? p_inj : p_wd, spot, i, c1, v1, t1, lo, hi, f);  // hold
+                k6_step_candidate<K>(a.coeffs, a.W_old, a.ld_w, a.S, a.is_last, ns2, dv2, p_wd, spot, i, c2, v2, t2, lo, hi, f);                      // withdraw
                 double cb = c0, vb = v0, tb = t0;                          // the first maximum wins (torch.argmax)
                 if (v1 > vb) { cb = c1; vb = v1; tb = t1; }
                 if (v2 > vb) { cb = c2; vb = v2; tb = t2; }
@@ -355,27 +287,6 @@ struct K6EvalArgs {
     int32_t n_ops, S, n_state, pad;
 };
 
-// polynomial grid of the staged coefficient block interpolated at a per-lane state
-template <int K>
-__device__ __forceinline__ double k6_lerp_grid(const double* __restrict__ sc, int S, double state, double x)
-{
-    const double b = fmin(fmax(state, 0.0), (double)(S - 1));
-    const double fl = floor(b), w = b - fl;
-    const int lo = (int)fl, hi = (int)ceil(b);
-    const double g_lo = k6_poly<K>(sc + lo * K, x), g_hi = k6_poly<K>(sc + hi * K, x);
-    return g_lo + w * (g_hi - g_lo);
-}
-
-// one candidate of the realised state: next volume nv from volume v at `price`
-template <int K>
-__device__ __forceinline__ void k6_eval_candidate(const K6Date& d, const double* __restrict__ sc, int S, double nv, double v, double price,
-                                                  double spot, double& ns, double& cash, double& value)
-{
-    ns = d.nscale == 0.0 ? 0.0 : (nv - d.nvmin) * d.nscale;
-    cash = -(nv - v) * price;
-    value = cash + (d.is_last ? 0.0 : k6_lerp_grid<K>(sc, S, ns, spot));
-}
-
 template <int K>
 __global__ __launch_bounds__(MCX_BLOCK) void k6_eval(const K6EvalArgs a)
 {
@@ -402,19 +313,11 @@ __global__ __launch_bounds__(MCX_BLOCK) void k6_eval(const K6EvalArgs a)
         __syncthreads();
         if (o.kind == 0) {
             const double spot = dev_atom(sd.x, a.paths, D, a.ld, i), num = dev_atom(sd.num, a.paths, D, a.ld, i);
-            const double v = sd.vmin + state * sd.step;
-            const double r_inj = k6_rate(sd.inj_x, sd.inj_r, sd.n_inj, v), r_wd = k6_rate(sd.wd_x, sd.wd_r, sd.n_wd, v);
-            const double nv0 = fmin(v + r_inj * sd.period, sd.nvmax);
-            const double nv1 = fmin(fmax(v, sd.nvmin), sd.nvmax);
-            const double nv2 = fmax(v - r_wd * sd.period, sd.nvmin);
-            const double p_inj = spot + sd.c_inj, p_wd = spot - sd.c_wd;
-            double s0, c0, v0, s1, c1, v1, s2, c2, v2;
-            k6_eval_candidate<K>(sd, sc, a.S, nv0, v, p_inj, spot, s0, c0, v0);                              // inject
-            k6_eval_candidate<K>(sd, sc, a.S, nv1, v, (nv1 - v) >= 0.0 ? p_inj : p_wd, spot, s1, c1, v1);    // hold
-            k6_eval_candidate<K>(sd, sc, a.S, nv2, v, p_wd, spot, s2, c2, v2);                              // withdraw
-            double sb = s0, cb = c0, vb = v0;                           // the first maximum wins (torch.argmax)
-            if (v1 > vb) { sb = s1; cb = c1; vb = v1; }
-            if (v2 > vb) { sb = s2; cb = c2; vb = v2; }
+            K6Cand c0, c1, c2;                                          // inject, hold, withdraw
+            k6_eval_candidates<K>(sd, sc, a.S, state, spot, c0, c1, c2);
+            double sb = c0.ns, cb = c0.cash, vb = c0.value;             // the first maximum wins (torch.argmax)
+            if (c1.value > vb) { sb = c1.ns; cb = c1.cash; vb = c1.value; }
+            if (c2.value > vb) { sb = c2.ns; cb = c2.cash; vb = c2.value; }
             state = sb;
             cf += cb / num;
         } else {
@@ -427,22 +330,37 @@ __global__ __launch_bounds__(MCX_BLOCK) void k6_eval(const K6EvalArgs a)
     if (live && a.cfs) a.cfs[i] += cf;
 }
 
-#define K6_DISPATCH(K, CALL)                                          \
-    switch (K) {                                                      \
-    case 1: { constexpr int KK = 1; CALL; } break;                    \
-    case 2: { constexpr int KK = 2; CALL; } break;                    \
-    case 3: { constexpr int KK = 3; CALL; } break;                    \
-    case 4: { constexpr int KK = 4; CALL; } break;                    \
-    case 5: { constexpr int KK = 5; CALL; } break;                    \
-    case 6: { constexpr int KK = 6; CALL; } break;                    \
-    default: break;                                                   \
-    }
-
-DevAtom k6_flat(const mcx_atom& q)
+// the K6StepArgs of one (storage, date) pair, `partials` left to the caller.  roll_date < 0: no roll (W_new unused)
+K6StepArgs k6_fill_step(const mcx_book* b, const mcx_storage* st, int32_t roll_date, int32_t num_atom, int32_t x_atom, double shift,
+                        double scale, const double* d_paths, int64_t n_paths, int64_t ld, const double* d_W_old, double* d_W_new,
+                        int64_t ld_w, int32_t flags)
 {
-    DevAtom o;
-    o.t_idx = q.t_idx; o.col = q.col; o.a = q.a; o.d = q.d; o.b = q.b; o.c0 = q.c0; o.c1 = q.c1;
-    return o;
+    K6StepArgs a;
+    memset(&a, 0, sizeof(a));
+    const int S = st->n_states;
+    a.paths = d_paths; a.W_old = d_W_old; a.W_new = d_W_new;
+    a.num = mcx_flat_atom(b->h_atoms[num_atom]); a.x = mcx_flat_atom(b->h_atoms[x_atom]);
+    a.shift = shift; a.scale = scale; a.n = n_paths; a.ld = ld; a.ld_w = ld_w; a.S = S; a.n_state = b->n_state;
+    a.f32_cache = (flags & MCX_LSM_F32_CACHE) ? 1 : 0;
+    a.roll = roll_date >= 0;
+    a.coeffs = b->d_coeffs; a.trans = st->d_trans; a.rnum = a.num; a.rx = a.x; a.c_inj = a.c_wd = 0.0; a.is_last = 1;
+    if (a.roll) {
+        const K6Date& d = st->h_dates[roll_date];
+        a.coeffs = b->d_coeffs + d.coeff_off; a.trans = st->d_trans + (size_t)roll_date * S * 6;
+        a.rnum = d.num; a.rx = d.x; a.c_inj = d.c_inj; a.c_wd = d.c_wd; a.is_last = d.is_last;
+    }
+    return a;
+}
+
+// the K6Solve of a date of mcx_storage_lsm_run or of a job (the two records name these fields alike); date: index of its status word
+template <class Q>
+K6Solve k6_fill_solve(const Q& q, int S, int date)
+{
+    K6Solve v;
+    memset(&v, 0, sizeof(v));
+    v.shift = q.shift; v.scale = q.scale; v.x0 = q.x0; v.off0 = q.coeff_off[0]; v.off1 = q.coeff_off[1];
+    v.degenerate = q.degenerate; v.S = S; v.date = date;
+    return v;
 }
 
 // step of one date on the stream: per-block partials in h->d_ws, *grid_out blocks (0: no paths)
@@ -460,19 +378,9 @@ int k6_step_launch(mcx_handle* h, const mcx_book* b, const mcx_storage* st, int3
     if (n_paths <= 0) return 0;
     const int grid = mcx_grid_for(n_paths, MCX_BLOCK, 4 * h->n_cu);
     if ((size_t)grid * NM * sizeof(double) > h->ws_bytes) MCX_FAIL(h, -2, "%s: workspace too small", who);
-    K6StepArgs a;
-    a.paths = d_paths; a.W_old = d_W_old; a.W_new = d_W_new; a.partials = h->d_ws;
-    a.num = k6_flat(b->h_atoms[num_atom]); a.x = k6_flat(b->h_atoms[x_atom]);
-    a.shift = shift; a.scale = scale; a.n = n_paths; a.ld = ld; a.ld_w = ld_w; a.S = S; a.n_state = b->n_state;
-    a.f32_cache = (flags & MCX_LSM_F32_CACHE) ? 1 : 0;
-    a.roll = roll_date >= 0;
-    a.coeffs = b->d_coeffs; a.trans = st->d_trans; a.rnum = a.num; a.rx = a.x; a.c_inj = a.c_wd = 0.0; a.is_last = 1;
-    if (a.roll) {
-        const K6Date& d = st->h_dates[roll_date];
-        a.coeffs = b->d_coeffs + d.coeff_off; a.trans = st->d_trans + (size_t)roll_date * S * 6;
-        a.rnum = d.num; a.rx = d.x; a.c_inj = d.c_inj; a.c_wd = d.c_wd; a.is_last = d.is_last;
-    }
-    K6_DISPATCH(K, hipLaunchKernelGGL((k6_step<KK>), dim3(grid), dim3(MCX_BLOCK), 0, s, a));
+    K6StepArgs a = k6_fill_step(b, st, roll_date, num_atom, x_atom, shift, scale, d_paths, n_paths, ld, d_W_old, d_W_new, ld_w, flags);
+    a.partials = h->d_ws;
+    K6_DISPATCH(K, 6, hipLaunchKernelGGL((k6_step<KK>), dim3(grid), dim3(MCX_BLOCK), 0, s, a));
     MCX_HIP(h, hipGetLastError());
     *grid_out = grid;
     return 0;
@@ -482,28 +390,13 @@ int k6_step_launch(mcx_handle* h, const mcx_book* b, const mcx_storage* st, int3
 
 extern "C" int mcx_storage_create(mcx_handle* h, const mcx_book* b, const mcx_storage_desc* d, mcx_storage** out)
 {
-    if (!h || !b || !d || !out || !d->dates || !d->trans) return -1;
+    if (!h || !b || !d || !out) return -1;
+    if (int rc = k6_check_desc(h, b, d, "mcx_storage_create")) return rc;
     const int S = d->n_states, K = b->n_basis;
-    if (S < 2 || S > MCX_STORAGE_MAX_STATES) MCX_FAIL(h, -2, "mcx_storage_create: n_states %d outside [2, %d]", S, MCX_STORAGE_MAX_STATES);
-    if (d->n_dates < 1) MCX_FAIL(h, -2, "mcx_storage_create: no action dates");
-    if (d->netting_set < 0 || d->netting_set >= b->n_netting_sets) MCX_FAIL(h, -2, "mcx_storage_create: netting set out of range");
     std::vector<K6Date> dates((size_t)d->n_dates);
     for (int j = 0; j < d->n_dates; ++j) {
-        const mcx_storage_date& q = d->dates[j];
-        if (q.n_inj < 1 || q.n_inj > MCX_STORAGE_MAX_KNOTS || q.n_wd < 1 || q.n_wd > MCX_STORAGE_MAX_KNOTS)
-            MCX_FAIL(h, -3, "mcx_storage_create: date %d: knot count outside [1, %d]", j, MCX_STORAGE_MAX_KNOTS);
-        if (q.num_atom < 0 || q.num_atom >= b->n_atoms || q.x_atom < 0 || q.x_atom >= b->n_atoms)
-            MCX_FAIL(h, -3, "mcx_storage_create: date %d: atom out of range", j);
-        if (q.coeff_off < 0 || q.coeff_off + (int64_t)S * K > b->n_coeffs)
-            MCX_FAIL(h, -3, "mcx_storage_create: date %d: coefficient block out of range", j);
-        K6Date& o = dates[j];
-        memset(&o, 0, sizeof(o));
-        o.vmin = q.vmin; o.step = q.step; o.nvmin = q.next_vmin; o.nvmax = q.next_vmax; o.nscale = q.next_scale;
-        o.period = q.period; o.c_inj = q.c_inj; o.c_wd = q.c_wd;
-        memcpy(o.inj_x, q.inj_x, sizeof(o.inj_x)); memcpy(o.inj_r, q.inj_r, sizeof(o.inj_r));
-        memcpy(o.wd_x, q.wd_x, sizeof(o.wd_x)); memcpy(o.wd_r, q.wd_r, sizeof(o.wd_r));
-        o.num = k6_flat(b->h_atoms[q.num_atom]); o.x = k6_flat(b->h_atoms[q.x_atom]);
-        o.coeff_off = q.coeff_off; o.n_inj = q.n_inj; o.n_wd = q.n_wd; o.is_last = q.is_last ? 1 : 0;
+        if (int rc = k6_check_date(h, b, d, j, "mcx_storage_create")) return rc;
+        k6_fill_date(b, d->dates[j], dates[j]);
     }
     MCX_HIP(h, hipSetDevice(h->device));
     mcx_storage* st = new mcx_storage();
@@ -544,7 +437,7 @@ extern "C" int mcx_storage_lsm_step(mcx_handle* h, const mcx_book* b, const mcx_
     K6Solve sv;
     memset(&sv, 0, sizeof(sv));
     sv.S = st->n_states;
-    K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve<KK>), dim3(1), dim3(1024), 0, s, h->d_ws, grid, d_moments, 0, sv,
+    K6_DISPATCH(K, 6, hipLaunchKernelGGL((k6_finish_solve<KK>), dim3(1), dim3(1024), 0, s, h->d_ws, grid, d_moments, 0, sv,
                                       (double*)nullptr, (double*)nullptr, (int32_t*)nullptr));
     MCX_HIP(h, hipGetLastError());
     return 0;
@@ -579,18 +472,16 @@ extern "C" int mcx_storage_lsm_run(mcx_handle* h, mcx_book* b, const mcx_storage
                             flags, s, "mcx_storage_lsm_run", &grid);
         if (rc != 0) break;
         if (q.roll_date >= 0) cur = 1 - cur;
-        K6Solve sv;
-        sv.shift = q.shift; sv.scale = q.scale; sv.x0 = q.x0; sv.off0 = q.coeff_off[0]; sv.off1 = q.coeff_off[1];
-        sv.degenerate = q.degenerate; sv.S = S; sv.date = d; sv.pad = 0;
+        const K6Solve sv = k6_fill_solve(q, S, d);
         if (grid == 0 && hipMemsetAsync(d_mom, 0, sizeof(double) * NM, s) != hipSuccess) { h->err = "mcx_storage_lsm_run: memset failed"; rc = -100; break; }
         if (multi || grid == 0) {
-            if (grid > 0) K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve<KK>), dim3(1), dim3(1024), 0, s, h->d_ws, grid, d_mom, 0, sv,
+            if (grid > 0) K6_DISPATCH(K, 6, hipLaunchKernelGGL((k6_finish_solve<KK>), dim3(1), dim3(1024), 0, s, h->d_ws, grid, d_mom, 0, sv,
                                                            b->d_coeffs, d_tab, d_st));
             if (multi) { rc = mcx_allreduce_f64(h, d_mom, NM, stream); if (rc != 0) break; }     // stream-ordered
-            K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve<KK>), dim3(1), dim3(1024), 0, s, (const double*)nullptr, 0, d_mom, 1, sv,
+            K6_DISPATCH(K, 6, hipLaunchKernelGGL((k6_finish_solve<KK>), dim3(1), dim3(1024), 0, s, (const double*)nullptr, 0, d_mom, 1, sv,
                                               b->d_coeffs, d_tab, d_st));
         } else {
-            K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve<KK>), dim3(1), dim3(1024), 0, s, h->d_ws, grid, d_mom, 1, sv,
+            K6_DISPATCH(K, 6, hipLaunchKernelGGL((k6_finish_solve<KK>), dim3(1), dim3(1024), 0, s, h->d_ws, grid, d_mom, 1, sv,
                                               b->d_coeffs, d_tab, d_st));
         }
         if (hipGetLastError() != hipSuccess) { h->err = "mcx_storage_lsm_run: launch failed"; rc = -100; }
@@ -628,6 +519,26 @@ struct K6Batch {
     int widest = 0, nm_max = 0, tiles = 0; // jobs of the widest step; largest moment count; tiles per job
 };
 
+// what every batched entry point checks of job j before it reads the job's storage: the storage index, same book, at most once
+// per step, coefficient offsets.  seen: [n_storages], the step each storage was last seen in (-2 at the start); step: of the job
+// in the caller's table, -1 where the call is one step (which it cannot number)
+int k6_check_job(mcx_handle* h, const mcx_book* b, const mcx_storage* const* storages, int32_t n_storages, const mcx_storage_lsm_job& q,
+                 int j, int step, std::vector<int32_t>& seen, const char* who)
+{
+    if (q.storage < 0 || q.storage >= n_storages || !storages[q.storage]) MCX_FAIL(h, -2, "%s: job %d: storage index out of range", who, j);
+    const mcx_storage* st = storages[q.storage];
+    if (st->n_basis != b->n_basis || st->n_coeffs != b->n_coeffs) MCX_FAIL(h, -2, "%s: storage %d was created on another book", who, q.storage);
+    if (seen[q.storage] == step) {
+        if (step < 0) MCX_FAIL(h, -2, "%s: job %d: storage %d appears twice in the step", who, j, q.storage);
+        MCX_FAIL(h, -2, "%s: job %d: storage %d appears twice in step %d", who, j, q.storage, step);
+    }
+    seen[q.storage] = step;
+    for (int w = 0; w < 2; ++w)
+        if (q.coeff_off[w] >= 0 && q.coeff_off[w] + (int64_t)st->n_states * b->n_basis > b->n_coeffs)
+            MCX_FAIL(h, -2, "%s: job %d: coefficient offset out of range", who, j);
+    return 0;
+}
+
 // every host-side check of a job table (nothing is launched before all of them pass) and its device image
 int k6_batch_build(mcx_handle* h, const mcx_book* b, const mcx_storage* const* storages, int32_t n_storages,
                    const mcx_storage_lsm_job* h_jobs, const int32_t* h_step_begin, int32_t n_steps, const double* d_paths,
@@ -649,22 +560,18 @@ int k6_batch_build(mcx_handle* h, const mcx_book* b, const mcx_storage* const* s
     const size_t cap = k6_partial_cap() / sizeof(double);
     out.step.resize((size_t)n_jobs); out.solve.resize((size_t)n_jobs);
     out.launch_begin.assign(1, 0);
-    std::vector<int32_t> seen((size_t)n_storages, -1);
+    std::vector<int32_t> seen((size_t)n_storages, -2);
     for (int t = 0; t < n_steps; ++t) {
         size_t used = 0;
         if (h_step_begin[t + 1] - h_step_begin[t] > out.widest) out.widest = h_step_begin[t + 1] - h_step_begin[t];
         for (int j = h_step_begin[t]; j < h_step_begin[t + 1]; ++j) {
             const mcx_storage_lsm_job& q = h_jobs[j];
-            if (q.storage < 0 || q.storage >= n_storages) MCX_FAIL(h, -2, "%s: job %d: storage index out of range", who, j);
-            if (seen[q.storage] == t) MCX_FAIL(h, -2, "%s: job %d: storage %d appears twice in step %d", who, j, q.storage, t);
-            seen[q.storage] = t;
+            if (int rc = k6_check_job(h, b, storages, n_storages, q, j, t, seen, who)) return rc;
             const mcx_storage* st = storages[q.storage];
             const int S = st->n_states, NM = (2 * K - 1) + S * K;
             const bool roll = q.roll_date >= 0;
             if (q.roll_date >= st->n_dates) MCX_FAIL(h, -2, "%s: job %d: roll date out of range", who, j);
             if (q.num_atom < 0 || q.num_atom >= b->n_atoms || q.x_atom < 0 || q.x_atom >= b->n_atoms) MCX_FAIL(h, -2, "%s: job %d: atom out of range", who, j);
-            for (int w = 0; w < 2; ++w)
-                if (q.coeff_off[w] >= 0 && q.coeff_off[w] + (int64_t)S * K > b->n_coeffs) MCX_FAIL(h, -2, "%s: job %d: coefficient offset out of range", who, j);
             const int64_t w_last = w_len - (int64_t)S * ld_w;
             if (q.w_old < 0 || q.w_old > w_last) MCX_FAIL(h, -2, "%s: job %d: w_old outside d_W", who, j);
             if (roll && (q.w_new < 0 || q.w_new > w_last)) MCX_FAIL(h, -2, "%s: job %d: w_new outside d_W", who, j);
@@ -672,23 +579,11 @@ int k6_batch_build(mcx_handle* h, const mcx_book* b, const mcx_storage* const* s
             // a new launch where the partials would pass the cap (or gridDim.y its limit); a launch holds at least one job
             const size_t need = (size_t)out.tiles * NM;
             if (j > out.launch_begin.back() && (used + need > cap || j - out.launch_begin.back() >= K6_MAX_LAUNCH_JOBS)) { out.launch_begin.push_back(j); used = 0; }
-            K6StepArgs& a = out.step[j];
-            memset(&a, 0, sizeof(a));
-            a.paths = d_paths; a.W_old = d_W + q.w_old; a.W_new = roll ? d_W + q.w_new : nullptr;
-            a.num = k6_flat(b->h_atoms[q.num_atom]); a.x = k6_flat(b->h_atoms[q.x_atom]);
-            a.shift = q.shift; a.scale = q.scale; a.n = n_paths; a.ld = ld; a.ld_w = ld_w; a.S = S; a.n_state = b->n_state;
-            a.f32_cache = (flags & MCX_LSM_F32_CACHE) ? 1 : 0;
-            a.roll = roll;
-            a.coeffs = b->d_coeffs; a.trans = st->d_trans; a.rnum = a.num; a.rx = a.x; a.c_inj = a.c_wd = 0.0; a.is_last = 1;
-            if (roll) {
-                const K6Date& d = st->h_dates[q.roll_date];
-                a.coeffs = b->d_coeffs + d.coeff_off; a.trans = st->d_trans + (size_t)q.roll_date * S * 6;
-                a.rnum = d.num; a.rx = d.x; a.c_inj = d.c_inj; a.c_wd = d.c_wd; a.is_last = d.is_last;
-            }
+            out.step[j] = k6_fill_step(b, st, q.roll_date, q.num_atom, q.x_atom, q.shift, q.scale, d_paths, n_paths, ld, d_W + q.w_old,
+                                       roll ? d_W + q.w_new : nullptr, ld_w, flags);
             K6BatchSolve& v = out.solve[j];
             memset(&v, 0, sizeof(v));
-            v.q.shift = q.shift; v.q.scale = q.scale; v.q.x0 = q.x0; v.q.off0 = q.coeff_off[0]; v.q.off1 = q.coeff_off[1];
-            v.q.degenerate = q.degenerate; v.q.S = S; v.q.date = j;
+            v.q = k6_fill_solve(q, S, j);
             v.part_off = (int64_t)used; v.tab_off = out.tab_doubles; v.n_blocks = out.tiles;
             used += need;
             out.tab_doubles += (int64_t)S * K;
@@ -714,7 +609,7 @@ int k6_batch_step(mcx_handle* h, const mcx_book* b, const K6Batch& bt, const K6S
     if (j1 <= j0) return 0;
     if (bt.tiles == 0) {
         MCX_HIP(h, hipMemsetAsync(d_mom, 0, sizeof(double) * (size_t)(j1 - j0) * mom_stride, s));
-        if (do_solve) K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve_batch<KK>), dim3(j1 - j0), dim3(1024), 0, s, d_solve + j0, d_part, 0, d_mom,
+        if (do_solve) K6_DISPATCH(K, 6, hipLaunchKernelGGL((k6_finish_solve_batch<KK>), dim3(j1 - j0), dim3(1024), 0, s, d_solve + j0, d_part, 0, d_mom,
                                                          mom_stride, 1, b->d_coeffs, d_tab, d_st));
         MCX_HIP(h, hipGetLastError());
         return 0;
@@ -722,8 +617,8 @@ int k6_batch_step(mcx_handle* h, const mcx_book* b, const K6Batch& bt, const K6S
     size_t l = std::upper_bound(bt.launch_begin.begin(), bt.launch_begin.end(), (int32_t)j0) - bt.launch_begin.begin() - 1;
     for (; l + 1 < bt.launch_begin.size() && bt.launch_begin[l] < j1; ++l) {
         const int a0 = bt.launch_begin[l], nj = bt.launch_begin[l + 1] - a0;
-        K6_DISPATCH(K, hipLaunchKernelGGL((k6_step_batch<KK>), dim3(bt.tiles, nj), dim3(MCX_BLOCK), 0, s, d_step + a0));
-        K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve_batch<KK>), dim3(nj), dim3(1024), 0, s, d_solve + a0, d_part, 1,
+        K6_DISPATCH(K, 6, hipLaunchKernelGGL((k6_step_batch<KK>), dim3(bt.tiles, nj), dim3(MCX_BLOCK), 0, s, d_step + a0));
+        K6_DISPATCH(K, 6, hipLaunchKernelGGL((k6_finish_solve_batch<KK>), dim3(nj), dim3(1024), 0, s, d_solve + a0, d_part, 1,
                                           d_mom + (size_t)(a0 - j0) * mom_stride, mom_stride, do_solve, b->d_coeffs, d_tab, d_st));
         MCX_HIP(h, hipGetLastError());
     }
@@ -766,22 +661,16 @@ extern "C" int mcx_storage_lsm_solve_batch(mcx_handle* h, mcx_book* b, const mcx
     const int K = b->n_basis;
     if (K < 1 || K > 6) MCX_FAIL(h, -3, "mcx_storage_lsm_solve_batch: unsupported basis size %d", K);
     std::vector<K6BatchSolve> solve((size_t)n_jobs);
-    std::vector<int32_t> seen((size_t)(n_storages > 0 ? n_storages : 0), 0);
+    std::vector<int32_t> seen((size_t)(n_storages > 0 ? n_storages : 0), -2);
     int64_t tab = 0;
     for (int j = 0; j < n_jobs; ++j) {
         const mcx_storage_lsm_job& q = h_jobs[j];
-        if (q.storage < 0 || q.storage >= n_storages || !storages[q.storage]) MCX_FAIL(h, -2, "mcx_storage_lsm_solve_batch: job %d: storage index out of range", j);
-        const mcx_storage* st = storages[q.storage];
-        if (st->n_basis != K || st->n_coeffs != b->n_coeffs) MCX_FAIL(h, -2, "mcx_storage_lsm_solve_batch: storage %d was created on another book", q.storage);
-        if (seen[q.storage]++) MCX_FAIL(h, -2, "mcx_storage_lsm_solve_batch: job %d: storage %d appears twice in the step", j, q.storage);
-        const int S = st->n_states;
+        if (int rc = k6_check_job(h, b, storages, n_storages, q, j, -1, seen, "mcx_storage_lsm_solve_batch")) return rc;
+        const int S = storages[q.storage]->n_states;
         if ((2 * K - 1) + S * K > mom_stride) MCX_FAIL(h, -2, "mcx_storage_lsm_solve_batch: job %d: mom_stride too small", j);
-        for (int w = 0; w < 2; ++w)
-            if (q.coeff_off[w] >= 0 && q.coeff_off[w] + (int64_t)S * K > b->n_coeffs) MCX_FAIL(h, -2, "mcx_storage_lsm_solve_batch: job %d: coefficient offset out of range", j);
         K6BatchSolve& v = solve[j];
         memset(&v, 0, sizeof(v));
-        v.q.shift = q.shift; v.q.scale = q.scale; v.q.x0 = q.x0; v.q.off0 = q.coeff_off[0]; v.q.off1 = q.coeff_off[1];
-        v.q.degenerate = q.degenerate; v.q.S = S; v.q.date = j;
+        v.q = k6_fill_solve(q, S, j);
         v.tab_off = tab;
         tab += (int64_t)S * K;
     }
@@ -791,7 +680,7 @@ extern "C" int mcx_storage_lsm_solve_batch(mcx_handle* h, mcx_book* b, const mcx
     if (!d_fb) return -100;
     const K6BatchSolve* d_solve = (const K6BatchSolve*)mcx_upload_call_data(h, solve.data(), solve_bytes, d_fb, s);
     if (!d_solve) return -100;
-    K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve_batch<KK>), dim3(n_jobs), dim3(1024), 0, s, d_solve, (const double*)nullptr, 0, d_moments,
+    K6_DISPATCH(K, 6, hipLaunchKernelGGL((k6_finish_solve_batch<KK>), dim3(n_jobs), dim3(1024), 0, s, d_solve, (const double*)nullptr, 0, d_moments,
                                       mom_stride, 1, b->d_coeffs, d_coeff_table, d_status));
     MCX_HIP(h, hipGetLastError());
     return 0;          // stream-ordered
@@ -836,7 +725,7 @@ extern "C" int mcx_storage_lsm_run_batch(mcx_handle* h, mcx_book* b, const mcx_s
         rc = mcx_allreduce_f64(h, d_mom, (int64_t)(j1 - j0) * stride, stream);          // ONE collective per step, stream-ordered
         if (rc != 0) break;
         const int K = b->n_basis;
-        K6_DISPATCH(K, hipLaunchKernelGGL((k6_finish_solve_batch<KK>), dim3(j1 - j0), dim3(1024), 0, s, d_solve + j0, (const double*)nullptr, 0,
+        K6_DISPATCH(K, 6, hipLaunchKernelGGL((k6_finish_solve_batch<KK>), dim3(j1 - j0), dim3(1024), 0, s, d_solve + j0, (const double*)nullptr, 0,
                                           d_mom, stride, 1, b->d_coeffs, d_tab, d_st));
         if (hipGetLastError() != hipSuccess) { h->err = "mcx_storage_lsm_run_batch: launch failed"; rc = -100; }
     }
@@ -876,7 +765,7 @@ extern "C" int mcx_storage_eval(mcx_handle* h, const mcx_book* b, const mcx_stor
     a.expo = d_expo ? d_expo + (size_t)st->netting_set * b->n_expo_rows * ld_out : nullptr;
     a.n = n_paths; a.ld = ld; a.ld_out = ld_out; a.n_ops = n_ops; a.S = S; a.n_state = b->n_state; a.pad = 0;
     const int grid = (int)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK);
-    K6_DISPATCH(K, hipLaunchKernelGGL((k6_eval<KK>), dim3(grid), dim3(MCX_BLOCK), 0, s, a));
+    K6_DISPATCH(K, 6, hipLaunchKernelGGL((k6_eval<KK>), dim3(grid), dim3(MCX_BLOCK), 0, s, a));
     MCX_HIP(h, hipGetLastError());
     return 0;          // stream-ordered
 }

@@ -672,13 +672,6 @@ int upload_ids(mcx_handle* h, const mcx_book* b, DevBuf& ev_ids, DevBuf& term_at
     return 0;
 }
 
-DevAtom flat_atom(const mcx_book* b, int id)
-{
-    DevAtom o; const mcx_atom& q = b->h_atoms[id];
-    o.t_idx = q.t_idx; o.col = q.col; o.a = q.a; o.d = q.d; o.b = q.b; o.c0 = q.c0; o.c1 = q.c1;
-    return o;
-}
-
 }  // namespace
 
 extern "C" int mcx_tangent_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
@@ -752,7 +745,7 @@ extern "C" int mcx_tangent_lsm(mcx_handle* h, const mcx_book* b, int32_t product
     memset(&a, 0, sizeof(a));
     fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b);
     a.ev_ids = (const KTEventIds*)ev_ids.p; a.term_atom = (const int32_t*)term_atom.p;
-    a.num = flat_atom(b, num_atom); a.x = flat_atom(b, x_atom); a.num_id = num_atom; a.x_id = x_atom; a.shift = shift; a.scale = scale;
+    a.num = mcx_flat_atom(b->h_atoms[num_atom]); a.x = mcx_flat_atom(b->h_atoms[x_atom]); a.num_id = num_atom; a.x_id = x_atom; a.shift = shift; a.scale = scale;
     a.partials = h->d_ws; a.ev_first = pr.cf_begin + first_event; a.ev_end = pr.cf_end;
     switch (K) {
     case 1: hipLaunchKernelGGL((kt_lsm<1>), dim3(grid), dim3(MCX_BLOCK), 0, s, a); break;
@@ -806,7 +799,7 @@ extern "C" int mcx_tangent_lsm_step(mcx_handle* h, const mcx_book* b, int32_t pr
     fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b);
     a.ev_ids = (const KTEventIds*)ev_ids.p; a.term_atom = (const int32_t*)term_atom.p; a.coeffs = b->d_coeffs;
     a.W = d_W; a.dW = d_dW; a.ld_w = ld_w; a.w_stride = (int64_t)S * ld_w;
-    a.num = flat_atom(b, num_atom); a.x = flat_atom(b, x_atom); a.num_id = num_atom; a.x_id = x_atom; a.shift = shift; a.scale = scale;
+    a.num = mcx_flat_atom(b->h_atoms[num_atom]); a.x = mcx_flat_atom(b->h_atoms[x_atom]); a.num_id = num_atom; a.x_id = x_atom; a.shift = shift; a.scale = scale;
     a.partials = h->d_ws; a.roll_begin = pr.cf_begin + roll_begin; a.roll_end = pr.cf_begin + roll_end;
     bool launched = true;
 #define MCX_KTS(KK, SS) hipLaunchKernelGGL((kt_lsm_step<KK, SS>), dim3(grid), dim3(MCX_BLOCK), 0, s, a)

@@ -9,9 +9,10 @@
 // equations (host: G c = r => dc = G^-1 (dr - dG c)) into the coefficient tangents and from there into the exposure rows
 // lerp_grid(c, state, x) / num with c, x, num dual and the state and its weights primal.
 //
-// Every PRIMAL value is formed by the expressions of k6_storage.hip (same operations in the same order, -ffp-contract=on contracts
-// them alike), so image 0 equals the primal kernels' results and every decision is the base run's; the tangents are formed next to
-// it by hand and never feed a decision.  Decisions use the coefficients the caller passes (the base run's).
+// Every PRIMAL value is formed by the functions k6_storage.hip forms it with (k6_common.h: the polynomial, the rate, the step
+// candidate, the three candidates of an action date, one definition each), so image 0 equals the primal kernels' results by
+// construction and every decision is the base run's; this file holds only what is dual.  The tangents are formed next to the
+// primal values by hand and never feed a decision.  Decisions use the coefficients the caller passes (the base run's).
 //   kts_step   one backward date.  One path per lane, the transition table and the coefficient rows are wave-uniform scalar loads.
 //              The (1+NP)(2K-1) Gram sums stay in per-lane registers over the grid-stride loop and are reduced once at the end;
 //              the (1+NP) S K right-hand-side moments cannot (640 at S = 32, K = 4): each is reduced over the wave as soon as it is
@@ -21,14 +22,11 @@
 //   kts_paths  Schwartz two-factor, EULER and ANALYTICAL: both step maps are linear in (x, y); the Cholesky factors depend on the
 //              parameters (rho; under ANALYTICAL also kappa and the volatilities) and arrive with their tangents.
 #include "mcx_dual.h"
+#include "k6_common.h"
 
 namespace {
 
 constexpr int NP = MCX_TANGENT_NP;
-#define KTS_MAX_S MCX_STORAGE_MAX_STATES
-#define KTS_MAX_KNOTS MCX_STORAGE_MAX_KNOTS
-
-struct KTSAtom { DevAtom a; int32_t id, pad; };
 
 // primal value exactly as dev_atom forms it, tangents by the chain rule: v = a + d x + b exp(c0 + c1 x)
 struct KTSBook {
@@ -61,41 +59,6 @@ __device__ __forceinline__ void kts_atom(const KTSBook& b, const DevAtom& a, int
     }
 }
 
-template <int K>
-__device__ __forceinline__ double kts_poly(const double* __restrict__ c, double x)
-{
-    double v = 0.0, xp = 1.0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) { v = fma(c[k], xp, v); xp *= x; }
-    return v;
-}
-template <int K>
-__device__ __forceinline__ double kts_poly_uniform(const double* __restrict__ c, double x)
-{
-    double v = 0.0, xp = 1.0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) { v = fma(ldk(c + k), xp, v); xp *= x; }
-    return v;
-}
-
-// k6_rate: the piecewise-linear rate at volume v (volumes carry no parameter dependence)
-__device__ __forceinline__ double kts_rate(const double* __restrict__ xs, const double* __restrict__ rs, int n, double v)
-{
-    if (n == 1) return rs[0];
-    double x0 = xs[0], x1 = xs[1], y0 = rs[0], y1 = rs[1];
-    for (int j = 1; j < n - 1; ++j) {
-        const bool m = xs[j] < v;
-        x0 = m ? xs[j] : x0; x1 = m ? xs[j + 1] : x1;
-        y0 = m ? rs[j] : y0; y1 = m ? rs[j + 1] : y1;
-    }
-    const bool close = fabs(x0 - x1) <= 1e-8 + 1e-5 * fabs(x1);
-    const double w = close ? 0.0 : (v - x0) / (x1 - x0);
-    double r = y0 + w * (y1 - y0);
-    r = v <= xs[0] ? rs[0] : r;
-    r = v >= xs[n - 1] ? rs[n - 1] : r;
-    return r;
-}
-
 // ---- backward step -----------------------------------------------------------------------------------------------------------
 struct KTSStepArgs {
     KTSBook b;
@@ -112,32 +75,10 @@ struct KTSStepArgs {
     int32_t S, roll, is_last, f32_cache;
 };
 
-// one candidate of an integer start state (k6_step_candidate) -> cash, value, cached tail and where the tail was read
-template <int K>
-__device__ __forceinline__ void kts_step_candidate(const KTSStepArgs& a, double ns, double dv, double price, double spot, int64_t i,
-                                                   double& cash, double& value, double& tail, int& lo, int& hi, double& w)
-{
-    const double b = fmin(fmax(ns, 0.0), (double)(a.S - 1));
-    const double fl = floor(b);
-    w = b - fl;
-    lo = (int)fl; hi = (int)ceil(b);
-    double cont = 0.0;
-    if (!a.is_last) {
-        const double g_lo = kts_poly_uniform<K>(a.coeffs + lo * K, spot);
-        const double g_hi = hi != lo ? kts_poly_uniform<K>(a.coeffs + hi * K, spot) : g_lo;
-        cont = g_lo + w * (g_hi - g_lo);
-    }
-    const double w_lo = a.W_old[(int64_t)lo * a.ld_w + i];
-    const double w_hi = hi != lo ? a.W_old[(int64_t)hi * a.ld_w + i] : w_lo;
-    tail = w_lo + w * (w_hi - w_lo);
-    cash = -dv * price;
-    value = cash + cont;
-}
-
 template <int K>
 __global__ __launch_bounds__(MCX_BLOCK) void kts_step(const KTSStepArgs a)
 {
-    constexpr int NB = 2 * K - 1, ROW = NB + KTS_MAX_S * K;
+    constexpr int NB = 2 * K - 1, ROW = NB + K6_MAX_S * K;
     __shared__ double rows[4][1 + NP][ROW];
     const int NM = NB + a.S * K;
     const int lane = threadIdx.x & (MCX_WAVE - 1), wv = threadIdx.x >> 6;
@@ -186,9 +127,9 @@ __global__ __launch_bounds__(MCX_BLOCK) void kts_step(const KTSStepArgs a)
                 const double ns0 = ldk(t + 0), dv0 = ldk(t + 1), ns1 = ldk(t + 2), dv1 = ldk(t + 3), ns2 = ldk(t + 4), dv2 = ldk(t + 5);
                 double c0, v0, t0, c1, v1, t1, c2, v2, t2, f0, f1, f2;
                 int lo0, hi0, lo1, hi1, lo2, hi2;
-                kts_step_candidate<K>(a, ns0, dv0, p_inj, spot, i, c0, v0, t0, lo0, hi0, f0);                          // inject
-                kts_step_candidate<K>(a, ns1, dv1, dv1 >= 0.0 ? p_inj : p_wd, spot, i, c1, v1, t1, lo1, hi1, f1);      // hold
-                kts_step_candidate<K>(a, ns2, dv2, p_wd, spot, i, c2, v2, t2, lo2, hi2, f2);                          // withdraw
+                k6_step_candidate<K>(a.coeffs, a.W_old, a.ld_w, a.S, a.is_last, ns0, dv0, p_inj, spot, i, c0, v0, t0, lo0, hi0, f0);                      // inject
+                k6_step_candidate<K>(a.coeffs, a.W_old, a.ld_w, a.S, a.is_last, ns1, dv1, dv1 >= 0.0 ? p_inj : p_wd, spot, i, c1, v1, t1, lo1, hi1, f1);  // hold
+                k6_step_candidate<K>(a.coeffs, a.W_old, a.ld_w, a.S, a.is_last, ns2, dv2, p_wd, spot, i, c2, v2, t2, lo2, hi2, f2);                      // withdraw
                 const bool m1 = v1 > v0;                                   // the first maximum wins (torch.argmax)
                 const double vb1 = m1 ? v1 : v0;
                 const bool m2 = v2 > vb1;
@@ -261,15 +202,6 @@ __global__ void kts_sum_partials(const double* __restrict__ partials, int count,
 }
 
 // ---- main simulation ---------------------------------------------------------------------------------------------------------
-struct KTSDate {                // device image of mcx_storage_date with the atoms flattened AND their ids (derivative rows)
-    double vmin, step, nvmin, nvmax, nscale, period, c_inj, c_wd;
-    double inj_x[KTS_MAX_KNOTS], inj_r[KTS_MAX_KNOTS], wd_x[KTS_MAX_KNOTS], wd_r[KTS_MAX_KNOTS];
-    KTSAtom num, x;
-    int64_t coeff_off;
-    int32_t n_inj, n_wd, is_last, pad;
-};
-static_assert(sizeof(KTSDate) % 8 == 0, "copied to LDS in dwords");
-
 struct KTSEvalArgs {
     KTSBook b;
     const KTSDate* __restrict__ dates;
@@ -282,25 +214,6 @@ struct KTSEvalArgs {
     int64_t n, ld_out, cf_stride, ex_stride;
     int32_t n_ops, S;
 };
-
-template <int K>
-__device__ __forceinline__ double kts_lerp_grid(const double* __restrict__ sc, int S, double state, double x)
-{
-    const double b = fmin(fmax(state, 0.0), (double)(S - 1));
-    const double fl = floor(b), w = b - fl;
-    const int lo = (int)fl, hi = (int)ceil(b);
-    const double g_lo = kts_poly<K>(sc + lo * K, x), g_hi = kts_poly<K>(sc + hi * K, x);
-    return g_lo + w * (g_hi - g_lo);
-}
-
-template <int K>
-__device__ __forceinline__ void kts_eval_candidate(const KTSDate& d, const double* __restrict__ sc, int S, double nv, double v, double price,
-                                                   double spot, double& ns, double& cash, double& value)
-{
-    ns = d.nscale == 0.0 ? 0.0 : (nv - d.nvmin) * d.nscale;
-    cash = -(nv - v) * price;
-    value = cash + (d.is_last ? 0.0 : kts_lerp_grid<K>(sc, S, ns, spot));
-}
 
 // tangent of the polynomial row c (dual) at x (dual): sum_k dc_k x^k + (sum_k k c_k x^(k-1)) dx
 template <int K>
@@ -324,8 +237,8 @@ template <int K>
 __global__ __launch_bounds__(MCX_BLOCK) void kts_eval(const KTSEvalArgs a)
 {
     __shared__ KTSDate sd;
-    __shared__ double sc[KTS_MAX_S * K];
-    __shared__ double sdc[KTS_MAX_S * K * NP];
+    __shared__ double sc[K6_MAX_S * K];
+    __shared__ double sdc[K6_MAX_S * K * NP];
     const int64_t i_raw = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x;
     const bool live = i_raw < a.n;
     const int64_t i = live ? i_raw : a.n - 1;
@@ -353,21 +266,13 @@ __global__ __launch_bounds__(MCX_BLOCK) void kts_eval(const KTSEvalArgs a)
             double spot, num, dspot[NP], dnum[NP];
             kts_atom(a.b, sd.x.a, sd.x.id, i, spot, dspot);
             kts_atom(a.b, sd.num.a, sd.num.id, i, num, dnum);
-            const double v = sd.vmin + state * sd.step;
-            const double r_inj = kts_rate(sd.inj_x, sd.inj_r, sd.n_inj, v), r_wd = kts_rate(sd.wd_x, sd.wd_r, sd.n_wd, v);
-            const double nv0 = fmin(v + r_inj * sd.period, sd.nvmax);
-            const double nv1 = fmin(fmax(v, sd.nvmin), sd.nvmax);
-            const double nv2 = fmax(v - r_wd * sd.period, sd.nvmin);
-            const double p_inj = spot + sd.c_inj, p_wd = spot - sd.c_wd;
-            double s0, c0, v0, s1, c1, v1, s2, c2, v2;
-            kts_eval_candidate<K>(sd, sc, a.S, nv0, v, p_inj, spot, s0, c0, v0);                              // inject
-            kts_eval_candidate<K>(sd, sc, a.S, nv1, v, (nv1 - v) >= 0.0 ? p_inj : p_wd, spot, s1, c1, v1);    // hold
-            kts_eval_candidate<K>(sd, sc, a.S, nv2, v, p_wd, spot, s2, c2, v2);                              // withdraw
-            const bool m1 = v1 > v0;                                    // the first maximum wins (torch.argmax)
-            const double vb1 = m1 ? v1 : v0;
-            const bool m2 = v2 > vb1;
-            const double cb = m2 ? c2 : (m1 ? c1 : c0), nvb = m2 ? nv2 : (m1 ? nv1 : nv0);
-            state = m2 ? s2 : (m1 ? s1 : s0);
+            K6Cand c0, c1, c2;                                          // inject, hold, withdraw
+            const double v = k6_eval_candidates<K>(sd, sc, a.S, state, spot, c0, c1, c2);
+            const bool m1 = c1.value > c0.value;                        // the first maximum wins (torch.argmax); selects: no scratch
+            const double vb1 = m1 ? c1.value : c0.value;
+            const bool m2 = c2.value > vb1;
+            const double cb = m2 ? c2.cash : (m1 ? c1.cash : c0.cash), nvb = m2 ? c2.nv : (m1 ? c1.nv : c0.nv);
+            state = m2 ? c2.ns : (m1 ? c1.ns : c0.ns);
             const double cn = cb / num, ir = 1.0 / num, mdv = -(nvb - v);
             cf += cn;
 #pragma unroll
@@ -377,7 +282,7 @@ __global__ __launch_bounds__(MCX_BLOCK) void kts_eval(const KTSEvalArgs a)
             double x, num, dx[NP], dnum[NP];
             kts_atom(a.b, ax, o.x_atom, i, x, dx);
             kts_atom(a.b, an, o.num_atom, i, num, dnum);
-            const double e = kts_lerp_grid<K>(sc, a.S, state, x) / num;
+            const double e = k6_lerp_grid<K>(sc, a.S, state, x) / num;
             const double b = fmin(fmax(state, 0.0), (double)(a.S - 1));
             const double fl = floor(b), w = b - fl;
             const int lo = (int)fl, hi = (int)ceil(b);
@@ -499,15 +404,6 @@ const void* kts_upload(mcx_handle* h, int slot, const void* src, size_t bytes, h
     return big ? mcx_upload_call_data(h, src, bytes, big, s) : nullptr;
 }
 
-KTSAtom kts_flat(const mcx_book* b, int id)
-{
-    KTSAtom o;
-    const mcx_atom& q = b->h_atoms[id];
-    o.a.t_idx = q.t_idx; o.a.col = q.col; o.a.a = q.a; o.a.d = q.d; o.a.b = q.b; o.a.c0 = q.c0; o.a.c1 = q.c1;
-    o.id = id; o.pad = 0;
-    return o;
-}
-
 void kts_fill_book(const mcx_book* b, const double* d_datoms, const double* d_paths, const double* d_dpaths, int64_t ld, int32_t n_dates,
                    KTSBook* out)
 {
@@ -515,35 +411,13 @@ void kts_fill_book(const mcx_book* b, const double* d_datoms, const double* d_pa
     out->pstride = (int64_t)n_dates * b->n_state * ld;
 }
 
+// the shared descriptor checks and the tangent kernels' own bound on the basis size
 int kts_check_desc(mcx_handle* h, const mcx_book* b, const mcx_storage_desc* d, const char* who)
 {
-    if (!d->dates || !d->trans) return -1;
-    if (d->n_states < 2 || d->n_states > MCX_STORAGE_MAX_STATES) MCX_FAIL(h, -2, "%s: n_states %d outside [2, %d]", who, d->n_states, MCX_STORAGE_MAX_STATES);
-    if (d->n_dates < 1) MCX_FAIL(h, -2, "%s: no action dates", who);
-    if (d->netting_set < 0 || d->netting_set >= b->n_netting_sets) MCX_FAIL(h, -2, "%s: netting set out of range", who);
+    if (int rc = k6_check_desc(h, b, d, who)) return rc;
     if (b->n_basis < 1 || b->n_basis > 4) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: basis size %d has no instantiation", who, b->n_basis);
     return 0;
 }
-
-int kts_check_date(mcx_handle* h, const mcx_book* b, const mcx_storage_desc* d, int j, const char* who)
-{
-    const mcx_storage_date& q = d->dates[j];
-    if (q.n_inj < 1 || q.n_inj > MCX_STORAGE_MAX_KNOTS || q.n_wd < 1 || q.n_wd > MCX_STORAGE_MAX_KNOTS)
-        MCX_FAIL(h, -3, "%s: date %d: knot count outside [1, %d]", who, j, MCX_STORAGE_MAX_KNOTS);
-    if (q.num_atom < 0 || q.num_atom >= b->n_atoms || q.x_atom < 0 || q.x_atom >= b->n_atoms) MCX_FAIL(h, -3, "%s: date %d: atom out of range", who, j);
-    if (q.coeff_off < 0 || q.coeff_off + (int64_t)d->n_states * b->n_basis > b->n_coeffs)
-        MCX_FAIL(h, -3, "%s: date %d: coefficient block out of range", who, j);
-    return 0;
-}
-
-#define KTS_DISPATCH(K, CALL)                                         \
-    switch (K) {                                                      \
-    case 1: { constexpr int KK = 1; CALL; } break;                    \
-    case 2: { constexpr int KK = 2; CALL; } break;                    \
-    case 3: { constexpr int KK = 3; CALL; } break;                    \
-    case 4: { constexpr int KK = 4; CALL; } break;                    \
-    default: break;                                                   \
-    }
 
 }  // namespace
 
@@ -557,7 +431,7 @@ extern "C" int mcx_tangent_storage_lsm_step(mcx_handle* h, const mcx_book* b, co
     if (!h || !b || !desc || !d_datoms || !d_coeffs || !d_paths || !d_dpaths || !d_W_old || !d_dW_old || !h_moments) return -1;
     if (int rc = kts_check_desc(h, b, desc, who)) return rc;
     if (roll_date >= desc->n_dates) MCX_FAIL(h, -2, "%s: roll date out of range", who);
-    if (roll_date >= 0) if (int rc = kts_check_date(h, b, desc, roll_date, who)) return rc;
+    if (roll_date >= 0) if (int rc = k6_check_date(h, b, desc, roll_date, who)) return rc;
     if (num_atom < 0 || num_atom >= b->n_atoms || x_atom < 0 || x_atom >= b->n_atoms) MCX_FAIL(h, -2, "%s: atom out of range", who);
     if (ld < n_paths || ld_w < n_paths) MCX_FAIL(h, -2, "%s: leading dimension < n_paths", who);
     if (roll_date >= 0 && (!d_W_new || !d_dW_new || d_W_new == d_W_old || d_dW_new == d_dW_old))
@@ -572,7 +446,7 @@ extern "C" int mcx_tangent_storage_lsm_step(mcx_handle* h, const mcx_book* b, co
     memset(&a, 0, sizeof(a));
     kts_fill_book(b, d_datoms, d_paths, d_dpaths, ld, n_dates, &a.b);
     a.W_old = d_W_old; a.dW_old = d_dW_old; a.W_new = d_W_new; a.dW_new = d_dW_new; a.partials = h->d_ws;
-    a.num = kts_flat(b, num_atom); a.x = kts_flat(b, x_atom); a.rnum = a.num; a.rx = a.x;
+    k6_set_atom(b, num_atom, a.num); k6_set_atom(b, x_atom, a.x); a.rnum = a.num; a.rx = a.x;
     a.shift = shift; a.scale = scale; a.n = n_paths; a.ld_w = ld_w; a.w_stride = (int64_t)S * ld_w; a.S = S;
     a.f32_cache = (flags & MCX_LSM_F32_CACHE) ? 1 : 0;
     a.roll = roll_date >= 0; a.is_last = 1; a.coeffs = d_coeffs; a.trans = nullptr;
@@ -581,9 +455,9 @@ extern "C" int mcx_tangent_storage_lsm_step(mcx_handle* h, const mcx_book* b, co
         const double* d_trans = (const double*)mcx_stage_small(h, desc->trans + (size_t)roll_date * S * 6, sizeof(double) * (size_t)S * 6, s);
         if (!d_trans) return -100;
         a.coeffs = d_coeffs + d.coeff_off; a.trans = d_trans;
-        a.rnum = kts_flat(b, d.num_atom); a.rx = kts_flat(b, d.x_atom); a.c_inj = d.c_inj; a.c_wd = d.c_wd; a.is_last = d.is_last ? 1 : 0;
+        k6_set_atom(b, d.num_atom, a.rnum); k6_set_atom(b, d.x_atom, a.rx); a.c_inj = d.c_inj; a.c_wd = d.c_wd; a.is_last = d.is_last ? 1 : 0;
     }
-    KTS_DISPATCH(K, hipLaunchKernelGGL((kts_step<KK>), dim3(grid), dim3(MCX_BLOCK), 0, s, a));
+    K6_DISPATCH(K, 4, hipLaunchKernelGGL((kts_step<KK>), dim3(grid), dim3(MCX_BLOCK), 0, s, a));
     MCX_HIP(h, hipGetLastError());
     double* d_out = h->d_ws + (size_t)grid * count;
     hipLaunchKernelGGL(kts_sum_partials, dim3((count + 63) / 64), dim3(64), 0, s, h->d_ws, count, grid, d_out);
@@ -618,16 +492,8 @@ extern "C" int mcx_tangent_storage_eval(mcx_handle* h, const mcx_book* b, const 
     }
     std::vector<KTSDate> dates((size_t)desc->n_dates);
     for (int j = 0; j < desc->n_dates; ++j) {
-        if (int rc = kts_check_date(h, b, desc, j, who)) return rc;
-        const mcx_storage_date& q = desc->dates[j];
-        KTSDate& o = dates[j];
-        memset(&o, 0, sizeof(o));
-        o.vmin = q.vmin; o.step = q.step; o.nvmin = q.next_vmin; o.nvmax = q.next_vmax; o.nscale = q.next_scale;
-        o.period = q.period; o.c_inj = q.c_inj; o.c_wd = q.c_wd;
-        memcpy(o.inj_x, q.inj_x, sizeof(o.inj_x)); memcpy(o.inj_r, q.inj_r, sizeof(o.inj_r));
-        memcpy(o.wd_x, q.wd_x, sizeof(o.wd_x)); memcpy(o.wd_r, q.wd_r, sizeof(o.wd_r));
-        o.num = kts_flat(b, q.num_atom); o.x = kts_flat(b, q.x_atom);
-        o.coeff_off = q.coeff_off; o.n_inj = q.n_inj; o.n_wd = q.n_wd; o.is_last = q.is_last ? 1 : 0;
+        if (int rc = k6_check_date(h, b, desc, j, who)) return rc;
+        k6_fill_date(b, desc->dates[j], dates[j]);
     }
     hipStream_t s = (hipStream_t)stream;
     const void* d_dates = kts_upload(h, 0, dates.data(), sizeof(KTSDate) * dates.size(), s);
@@ -643,7 +509,7 @@ extern "C" int mcx_tangent_storage_eval(mcx_handle* h, const mcx_book* b, const 
     a.cf_stride = (int64_t)b->n_netting_sets * ld_out; a.ex_stride = (int64_t)b->n_netting_sets * n_rows * ld_out;
     a.n = n_paths; a.ld_out = ld_out; a.n_ops = n_ops; a.S = S;
     const int grid = (int)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK);
-    KTS_DISPATCH(K, hipLaunchKernelGGL((kts_eval<KK>), dim3(grid), dim3(MCX_BLOCK), 0, s, a));
+    K6_DISPATCH(K, 4, hipLaunchKernelGGL((kts_eval<KK>), dim3(grid), dim3(MCX_BLOCK), 0, s, a));
     MCX_HIP(h, hipGetLastError());
     MCX_HIP(h, hipStreamSynchronize(s));
     return 0;

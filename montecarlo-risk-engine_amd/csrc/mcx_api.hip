@@ -60,13 +60,6 @@ extern "C" int mcx_device_info(mcx_handle* h, int32_t* n_cu, int64_t* hbm_bytes,
 }
 
 // ---- book ------------------------------------------------------------------------------------------------------------
-static DevAtom flat_atom(const mcx_atom& a)
-{
-    DevAtom o;
-    o.t_idx = a.t_idx; o.col = a.col; o.a = a.a; o.d = a.d; o.b = a.b; o.c0 = a.c0; o.c1 = a.c1;
-    return o;
-}
-
 extern "C" int mcx_book_create(mcx_handle* h, const mcx_book_desc* d, mcx_book** out)
 {
     if (!h || !d || !out) return -1;
@@ -127,11 +120,11 @@ extern "C" int mcx_book_create(mcx_handle* h, const mcx_book_desc* d, mcx_book**
     b->h_atoms.assign(d->atoms, d->atoms + d->n_atoms);
 
     std::vector<DevAtom> atoms(d->n_atoms > 0 ? d->n_atoms : 1);
-    for (int i = 0; i < d->n_atoms; ++i) atoms[i] = flat_atom(d->atoms[i]);
+    for (int i = 0; i < d->n_atoms; ++i) atoms[i] = mcx_flat_atom(d->atoms[i]);
     std::vector<DevTerm> terms(d->n_terms > 0 ? d->n_terms : 1);
     for (int i = 0; i < d->n_terms; ++i) {
         terms[i].w = d->terms[i].w;
-        terms[i].atom = flat_atom(d->atoms[d->terms[i].atom]);
+        terms[i].atom = mcx_flat_atom(d->atoms[d->terms[i].atom]);
         terms[i].den = d->terms[i].den;
         terms[i].pad = 0;
     }
@@ -159,8 +152,8 @@ extern "C" int mcx_book_create(mcx_handle* h, const mcx_book_desc* d, mcx_book**
             o.kind = e.kind; o.term_begin = e.term_begin; o.term_end = e.term_end; o.coeff_off = e.coeff_off; o.row = e.expo_row;
             o.strike = e.strike; o.sign = e.sign;
             for (int q = 0; q < 4; ++q) o.aux[q] = e.aux[q];
-            o.num = flat_atom(d->atoms[e.num_atom]);
-            o.x = e.x_atom >= 0 ? flat_atom(d->atoms[e.x_atom]) : none;
+            o.num = mcx_flat_atom(d->atoms[e.num_atom]);
+            o.x = e.x_atom >= 0 ? mcx_flat_atom(d->atoms[e.x_atom]) : none;
         }
         fam.fetch_or(mine);
     };

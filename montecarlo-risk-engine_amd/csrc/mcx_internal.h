@@ -63,6 +63,12 @@ struct DevAtom {            // value = a + d*x + b*exp(c0 + c1*x), x = paths[(t_
     int32_t t_idx, col;
     double a, d, b, c0, c1;
 };
+static inline DevAtom mcx_flat_atom(const mcx_atom& q)      // host: the device record of an atom of include/mcx.h
+{
+    DevAtom o;
+    o.t_idx = q.t_idx; o.col = q.col; o.a = q.a; o.d = q.d; o.b = q.b; o.c0 = q.c0; o.c1 = q.c1;
+    return o;
+}
 
 struct DevTerm {
     double w;

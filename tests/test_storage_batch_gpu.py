@@ -221,6 +221,41 @@ def test_bad_job_tables_are_refused_before_any_launch(what, hip):
     assert not W.any().item()
 
 
+@pytest.mark.parametrize("what", ["w_new == w_old", "w_old outside", "storage index out of range", "appears twice"])
+def test_bad_job_tables_are_refused_by_the_stepwise_entry_points(what, hip):
+    """the smallest book (K = 2, 257 paths): mcx_storage_lsm_step_batch refuses all four tables; mcx_storage_lsm_solve_batch, which
+    receives neither paths nor cache, the two that concern it.  After each refusal the cache (filled with a sentinel), the moments,
+    the table and the book's coefficients are what they were: nothing ran"""
+    from mcx._native import McxError
+    b = book_of(hip, 2, 257)
+    b.reset()
+    before = hip.book_get_coeffs(b.sc.book).copy()
+    table, bad = _bad_tables(b)[what]
+    t = int(np.searchsorted(b.step_begin, bad, side="right")) - 1
+    step = np.ascontiguousarray(table[b.step_begin[t]:b.step_begin[t + 1]], dtype=_abi.STORAGE_LSM_JOB_DTYPE)
+    stride = (2 * b.K - 1) + 32 * b.K
+    W = hip.zeros(b.w_len).fill_(1.5)
+    with pytest.raises(McxError) as e:
+        hip.storage_lsm_step_batch(b.sc.book, b.handles, step, b.paths, W, b.n, stride)
+    msg = hip.lib.mcx_last_error(hip.h).decode()
+    assert e.value.code == -2 and what in msg and "mcx_storage_lsm_step_batch" in msg, msg
+    hip.synchronize()
+    assert (W == 1.5).all().item() and np.array_equal(hip.book_get_coeffs(b.sc.book), before)
+    if what not in ("storage index out of range", "appears twice"):
+        return
+    # (the library directly: the wrapper sizes the table from the storage indices before it calls)
+    mom = hip.zeros(len(step), stride).fill_(2.5)
+    tab = hip.zeros(len(step) * 32 * b.K).fill_(3.5)
+    status = hip.zeros(len(step), dtype=torch.int32).fill_(7)
+    rc = hip.lib.mcx_storage_lsm_solve_batch(hip.h, b.sc.book.ptr, hip._storage_array(b.handles), len(b.handles), _abi.ptr(step), len(step),
+                                             mom.data_ptr(), stride, tab.data_ptr(), status.data_ptr(), hip._stream())
+    msg = hip.lib.mcx_last_error(hip.h).decode()
+    assert rc == -2 and what in msg and "mcx_storage_lsm_solve_batch" in msg, msg
+    hip.synchronize()
+    assert (mom == 2.5).all().item() and (tab == 3.5).all().item() and (status == 7).all().item()
+    assert (W == 1.5).all().item() and np.array_equal(hip.book_get_coeffs(b.sc.book), before)
+
+
 # ---- 6. three emulated ranks --------------------------------------------------------------------------------------------------------
 def test_three_emulated_ranks_one_collective_per_step(hip):
     """uneven split of 1,000 paths; tolerances of tests/test_storage_emulated_ranks.py (the ranks sum their moments in another
