@@ -13,6 +13,7 @@
 //     features of 64 paths are staged through LDS in a bank-conflict-free [feature][path] image (row stride 66 doubles).
 // Both read each path's state once (HBM-bound: 8*(1+S+atoms) B/path).
 #include "mcx_device.h"
+#include "lsm_solve.h"
 
 namespace {
 
@@ -177,6 +178,25 @@ __device__ __forceinline__ void k3_block_reduce(const double (&acc)[NM], double*
     if (threadIdx.x < NM) dst[threadIdx.x] = (rows[0][threadIdx.x] + rows[1][threadIdx.x]) + (rows[2][threadIdx.x] + rows[3][threadIdx.x]);
 }
 
+// path i into the lane's running sums: acc[q] += z^q (q < 2K-1), acc[(2K-1) + s K + k] += z^k Y_s.  Shared by k3_step_valu and
+// k3_step_batch (the grid-stride loop stays in the kernels: with the loop in here 88 of their 96 instantiations compiled differently)
+template <int K, int S>
+__device__ __forceinline__ void k3_accumulate(const K3Args& a, int64_t i, double (&acc)[(2 * K - 1) + S * K])
+{
+    double y[S], z;
+    k3_roll<S>(a, i, y, z);
+    double zp = 1.0;
+#pragma unroll
+    for (int k = 0; k < 2 * K - 1; ++k) {
+        acc[k] += zp;
+        if (k < K) {
+#pragma unroll
+            for (int s = 0; s < S; ++s) acc[(2 * K - 1) + s * K + k] = fma(zp, y[s], acc[(2 * K - 1) + s * K + k]);
+        }
+        zp *= z;
+    }
+}
+
 template <int K, int S>
 __global__ __launch_bounds__(MCX_BLOCK) void k3_step_valu(const K3Args a_in)
 {
@@ -189,20 +209,7 @@ __global__ __launch_bounds__(MCX_BLOCK) void k3_step_valu(const K3Args a_in)
     double acc[NM];
 #pragma unroll
     for (int q = 0; q < NM; ++q) acc[q] = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * MCX_BLOCK) {
-        double y[S], z;
-        k3_roll<S>(a, i, y, z);
-        double zp = 1.0;
-#pragma unroll
-        for (int k = 0; k < 2 * K - 1; ++k) {
-            acc[k] += zp;
-            if (k < K) {
-#pragma unroll
-                for (int s = 0; s < S; ++s) acc[(2 * K - 1) + s * K + k] = fma(zp, y[s], acc[(2 * K - 1) + s * K + k]);
-            }
-            zp *= z;
-        }
-    }
+    for (int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * MCX_BLOCK) k3_accumulate<K, S>(a, i, acc);
     k3_block_reduce<NM>(acc, a.partials + (int64_t)blockIdx.x * NM);
 }
 
@@ -293,20 +300,7 @@ __global__ __launch_bounds__(MCX_BLOCK) void k3_step_batch(K3Args a, const K3Job
     double acc[NM];
 #pragma unroll
     for (int q = 0; q < NM; ++q) acc[q] = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * MCX_BLOCK) {
-        double y[S], z;
-        k3_roll<S>(a, i, y, z);
-        double zp = 1.0;
-#pragma unroll
-        for (int k = 0; k < 2 * K - 1; ++k) {
-            acc[k] += zp;
-            if (k < K) {
-#pragma unroll
-                for (int s = 0; s < S; ++s) acc[(2 * K - 1) + s * K + k] = fma(zp, y[s], acc[(2 * K - 1) + s * K + k]);
-            }
-            zp *= z;
-        }
-    }
+    for (int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * MCX_BLOCK) k3_accumulate<K, S>(a, i, acc);
     k3_block_reduce<NM>(acc, a.partials + ((int64_t)blockIdx.y * blocks_per_job + blockIdx.x) * NM);
 }
 
@@ -396,109 +390,30 @@ __global__ void k3_minmax_finish(const double* __restrict__ partials, int n_bloc
 // ---- device-side normal-equation solve (mcx_lsm_run) ---------------------------------------------------------------------
 // One date of the backward induction: moments of the shifted / scaled basis -> least-squares coefficients in the RAW monomial
 // basis, written straight into the book's coefficient array (what the next date's roll reads) and into the result table.
-// Same algorithm as the host solver (mcx/plan.py solve_normal_equations): LU with partial pivoting of the K x K Gram matrix,
-// back-transformation z^k = scale^k (x - shift)^k, and the minimum-norm solution of the exactly rank-1 system of a date on
-// which every path shares x = x0 (the calibration date).  K <= 6, S <= 8: one lane.
-struct K3Solve {
+// The solver itself is lsm_solve (lsm_solve.h, shared with the gas storage).  K <= 6, S <= 8: one lane.
+struct K3Solve {                 // one system: of a date of mcx_lsm_run or of a job of a batched step (uploaded as a table)
     double shift, scale, x0;
     int64_t off0, off1;          // coefficient offsets in the book (-1: none)
-    int32_t degenerate, K, S, date;
+    int32_t degenerate, pad;
 };
 
-// KK / SS > 0: basis size / state count known at compile time — every loop unrolls and the K x K system lives in registers (with
-// run-time bounds the local arrays sit in scratch memory: ~11 us for a 3 x 3 solve by one thread, mostly scratch latency).
-// Pivoting by conditional row swaps with static indices: after the r-loop row c holds the largest |entry| of column c, as with
-// LAPACK's single swap; the remaining rows may be ordered differently, the solution is the same up to rounding.
+// KK / SS > 0: basis size / state count known at compile time (else the run-time K, S: local arrays in scratch memory).
+// Here only the stores: status[date], row `date` of the table (or nullptr), the book's coefficients unless singular
 template <int KK, int SS>
-__device__ __forceinline__ void k3_solve_t(const double* __restrict__ m, const K3Solve& q, double* __restrict__ coeffs, double* __restrict__ table,
-                                           int32_t* __restrict__ status)
+__device__ __forceinline__ void k3_solve_t(const double* __restrict__ m, const K3Solve& q, int K_rt, int S_rt, int date,
+                                           double* __restrict__ coeffs, double* __restrict__ table, int32_t* __restrict__ status)
 {
-    const int K = KK ? KK : q.K, S = SS ? SS : q.S;
+    const int K = KK ? KK : K_rt, S = SS ? SS : S_rt;
     constexpr int KA = KK ? KK : MCX_MAX_BASIS, SA = SS ? SS : MCX_MAX_STATES;
     double out[SA][KA];
-#pragma unroll
-    for (int s = 0; s < S; ++s)
-#pragma unroll
-        for (int k = 0; k < K; ++k) out[s][k] = 0.0;
-    const double n = m[0];
-    int st = 0;
-    if (n > 0.0 && q.degenerate) {
-        double v[KA], vv = 0.0, xp = 1.0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) { v[k] = xp; vv += xp * xp; xp *= q.x0; }
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const double mean_y = m[(2 * K - 1) + s * K] / n;
-#pragma unroll
-            for (int k = 0; k < K; ++k) out[s][k] = v[k] * (mean_y / vv);
-        }
-    } else if (n > 0.0) {
-        double G[KA][KA], B[KA][SA];
-        double gmax = 0.0;
-#pragma unroll
-        for (int j = 0; j < K; ++j)
-#pragma unroll
-            for (int k = 0; k < K; ++k) { G[j][k] = m[j + k]; gmax = fmax(gmax, fabs(G[j][k])); }
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-#pragma unroll
-            for (int s = 0; s < S; ++s) B[k][s] = m[(2 * K - 1) + s * K + k];
-#pragma unroll
-        for (int c = 0; c < K; ++c) {                                  // LU, partial pivoting
-#pragma unroll
-            for (int r = c + 1; r < K; ++r) {
-                const bool sw = fabs(G[r][c]) > fabs(G[c][c]);
-#pragma unroll
-                for (int k = 0; k < K; ++k) { const double x = G[c][k], y = G[r][k]; G[c][k] = sw ? y : x; G[r][k] = sw ? x : y; }
-#pragma unroll
-                for (int s = 0; s < S; ++s) { const double x = B[c][s], y = B[r][s]; B[c][s] = sw ? y : x; B[r][s] = sw ? x : y; }
-            }
-            if (!(fabs(G[c][c]) > 1e-14 * gmax)) st = 1;               // numerically singular: the caller re-solves on the host
-            const double piv = st ? 1.0 : G[c][c];
-#pragma unroll
-            for (int r = c + 1; r < K; ++r) {
-                const double f = G[r][c] / piv;
-#pragma unroll
-                for (int k = c + 1; k < K; ++k) G[r][k] -= f * G[c][k];
-#pragma unroll
-                for (int s = 0; s < S; ++s) B[r][s] -= f * B[c][s];
-            }
-        }
-        if (st == 0) {
-#pragma unroll
-            for (int c = K - 1; c >= 0; --c)
-#pragma unroll
-                for (int s = 0; s < S; ++s) {
-                    double acc = B[c][s];
-#pragma unroll
-                    for (int k = c + 1; k < K; ++k) acc -= G[c][k] * B[k][s];
-                    B[c][s] = acc / G[c][c];
-                }
-            // T[j][k] = coefficient of x^j in z^k = scale^k C(k, j) (-shift)^(k-j)
-            double sp = 1.0;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                double binom = 1.0;
-#pragma unroll
-                for (int j = 0; j <= k; ++j) {
-                    double ms = 1.0;
-                    for (int e = 0; e < k - j; ++e) ms *= -q.shift;
-                    const double T = sp * binom * ms;
-#pragma unroll
-                    for (int s = 0; s < S; ++s) out[s][j] += T * B[k][s];
-                    binom = binom * (double)(k - j) / (double)(j + 1);
-                }
-                sp *= q.scale;
-            }
-        }
-    }
-    status[q.date] = st;
+    const int st = lsm_solve<KA, SA>(m, K, 0, S, q.shift, q.scale, q.x0, q.degenerate, out);   // 1: the caller re-solves on the host
+    status[date] = st;
 #pragma unroll
     for (int s = 0; s < S; ++s)
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const double c = out[s][k];
-            if (table) table[((int64_t)q.date * S + s) * K + k] = c;
+            if (table) table[((int64_t)date * S + s) * K + k] = c;
             if (st == 0) {
                 if (q.off0 >= 0) coeffs[q.off0 + s * K + k] = c;
                 if (q.off1 >= 0) coeffs[q.off1 + s * K + k] = c;
@@ -506,35 +421,35 @@ __device__ __forceinline__ void k3_solve_t(const double* __restrict__ m, const K
         }
 }
 
-__device__ void k3_solve_body(const double* __restrict__ m, const K3Solve& q, double* __restrict__ coeffs, double* __restrict__ table,
-                              int32_t* __restrict__ status)
+__device__ void k3_solve_body(const double* __restrict__ m, const K3Solve& q, int K, int S, int date, double* __restrict__ coeffs,
+                              double* __restrict__ table, int32_t* __restrict__ status)
 {
-    const int key = q.K * 16 + q.S;
+    const int key = K * 16 + S;
     switch (key) {
-    case 2 * 16 + 1: k3_solve_t<2, 1>(m, q, coeffs, table, status); break;
-    case 2 * 16 + 2: k3_solve_t<2, 2>(m, q, coeffs, table, status); break;
-    case 3 * 16 + 1: k3_solve_t<3, 1>(m, q, coeffs, table, status); break;
-    case 3 * 16 + 2: k3_solve_t<3, 2>(m, q, coeffs, table, status); break;
-    case 3 * 16 + 3: k3_solve_t<3, 3>(m, q, coeffs, table, status); break;
-    case 4 * 16 + 1: k3_solve_t<4, 1>(m, q, coeffs, table, status); break;
-    case 4 * 16 + 2: k3_solve_t<4, 2>(m, q, coeffs, table, status); break;
-    default: k3_solve_t<0, 0>(m, q, coeffs, table, status); break;
+    case 2 * 16 + 1: k3_solve_t<2, 1>(m, q, K, S, date, coeffs, table, status); break;
+    case 2 * 16 + 2: k3_solve_t<2, 2>(m, q, K, S, date, coeffs, table, status); break;
+    case 3 * 16 + 1: k3_solve_t<3, 1>(m, q, K, S, date, coeffs, table, status); break;
+    case 3 * 16 + 2: k3_solve_t<3, 2>(m, q, K, S, date, coeffs, table, status); break;
+    case 3 * 16 + 3: k3_solve_t<3, 3>(m, q, K, S, date, coeffs, table, status); break;
+    case 4 * 16 + 1: k3_solve_t<4, 1>(m, q, K, S, date, coeffs, table, status); break;
+    case 4 * 16 + 2: k3_solve_t<4, 2>(m, q, K, S, date, coeffs, table, status); break;
+    default: k3_solve_t<0, 0>(m, q, K, S, date, coeffs, table, status); break;
     }
 }
 
-__global__ void k3_solve(const double* __restrict__ m, const K3Solve q, double* __restrict__ coeffs, double* __restrict__ table,
-                         int32_t* __restrict__ status)
+__global__ void k3_solve(const double* __restrict__ m, const K3Solve q, int K, int S, int date, double* __restrict__ coeffs,
+                         double* __restrict__ table, int32_t* __restrict__ status)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    k3_solve_body(m, q, coeffs, table, status);
+    k3_solve_body(m, q, K, S, date, coeffs, table, status);
 }
 
 // finish + solve in ONE launch (mcx_lsm_run on one GPU: the moments need no all-reduce between the two): wave q of a 1024-thread
 // block sums moment q over the step kernel's per-block partials (fixed order: deterministic), thread 0 solves.  Two launches per
 // regression date instead of three — 121 dates of a Bermudan are latency: ~5 us + a kernel boundary each.
 __global__ __launch_bounds__(1024) void k3_finish_solve(const double* __restrict__ partials, int nm, int n_blocks, double* __restrict__ mom_out,
-                                                        const K3Solve q, double* __restrict__ coeffs, double* __restrict__ table,
-                                                        int32_t* __restrict__ status)
+                                                        const K3Solve q, int K, int S, int date, double* __restrict__ coeffs,
+                                                        double* __restrict__ table, int32_t* __restrict__ status)
 {
     __shared__ double m[(2 * MCX_MAX_BASIS - 1) + MCX_MAX_STATES * MCX_MAX_BASIS];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -545,42 +460,61 @@ __global__ __launch_bounds__(1024) void k3_finish_solve(const double* __restrict
         if (lane == 0) { m[j] = s; mom_out[j] = s; }
     }
     __syncthreads();
-    if (threadIdx.x == 0) k3_solve_body(m, q, coeffs, table, status);
+    if (threadIdx.x == 0) k3_solve_body(m, q, K, S, date, coeffs, table, status);
 }
 
-template <int K, int S>
-void launch_k3(const K3Args& a, int grid, bool mfma, hipStream_t s)
+// launch of a kernel template on (basis size, state count): the statements with KK = K, SS = S for 1 <= K <= 6, 1 <= S <= 8
+#define K3_DISPATCH(K, S, ...) MCX_DISPATCH(SS, S, 8, MCX_DISPATCH(KK, K, 6, __VA_ARGS__))
+
+// one batched moment step: grid (blocks per job, jobs).  -1: no instantiation for (K, S)
+int k3_launch_batch(int K, int S, const K3Args& a, const K3Job* d_jobs, dim3 grid, hipStream_t s)
 {
-    if (mfma) hipLaunchKernelGGL((k3_step_mfma<K, S>), dim3(grid), dim3(MCX_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL((k3_step_valu<K, S>), dim3(grid), dim3(MCX_BLOCK), 0, s, a);
+    int rc = -1;
+    K3_DISPATCH(K, S, hipLaunchKernelGGL((k3_step_batch<KK, SS>), grid, dim3(MCX_BLOCK), 0, s, a, d_jobs, (int)grid.x); rc = 0);
+    return rc;
 }
 
-template <int S>
-int dispatch_k3(int K, const K3Args& a, int grid, bool mfma, hipStream_t s)
+// the book-wide fields of the step kernels' argument, everything else zero (the per-product fields: lsm_step_launch, or the K3Job
+// of a batched step); `partials` is left to the caller
+int k3_fill_args(mcx_handle* h, const mcx_book* b, const double* d_paths, int64_t n_paths, int64_t ld, double* d_W, int64_t ld_w,
+                 int32_t flags, const char* who, K3Args& a)
 {
-    switch (K) {
-    case 1: launch_k3<1, S>(a, grid, mfma, s); return 0;
-    case 2: launch_k3<2, S>(a, grid, mfma, s); return 0;
-    case 3: launch_k3<3, S>(a, grid, mfma, s); return 0;
-    case 4: launch_k3<4, S>(a, grid, mfma, s); return 0;
-    case 5: launch_k3<5, S>(a, grid, mfma, s); return 0;
-    case 6: launch_k3<6, S>(a, grid, mfma, s); return 0;
-    default: return -1;
-    }
+    memset(&a, 0, sizeof(a));
+    a.terms = b->d_terms; a.events = b->d_events; a.atoms = b->d_atoms; a.coeffs = b->d_coeffs; a.paths = d_paths;
+    a.W = d_W; a.n = n_paths; a.ld = ld; a.ld_w = ld_w; a.n_basis = b->n_basis; a.n_state = b->n_state;
+    a.f32_cache = (flags & MCX_LSM_F32_CACHE) ? 1 : 0; a.bridge = b->d_bridge;
+    a.ex_mode = b->ex_mode; a.ex_bits = b->d_ex_bits; a.ex_ld = b->ex_ld;
+    a.vpoly = b->d_vpoly; a.vcoef = b->d_vcoef;
+    if (a.ex_mode && a.ex_ld < n_paths) MCX_FAIL(h, -2, "%s: exercise replay buffer narrower than the path count", who);
+    return 0;
 }
 
-template <int S>
-int dispatch_k3_batch(int K, const K3Args& a, const K3Job* jobs, dim3 grid, hipStream_t s)
+// job j of a batched step of S states: every index the kernel dereferences, then its device record
+int k3_check_job(mcx_handle* h, const mcx_book* b, const mcx_lsm_job& q, int j, int S, int64_t ld_w, int64_t w_len, const char* who, K3Job& out)
 {
-    switch (K) {
-    case 1: hipLaunchKernelGGL((k3_step_batch<1, S>), grid, dim3(MCX_BLOCK), 0, s, a, jobs, (int)grid.x); return 0;
-    case 2: hipLaunchKernelGGL((k3_step_batch<2, S>), grid, dim3(MCX_BLOCK), 0, s, a, jobs, (int)grid.x); return 0;
-    case 3: hipLaunchKernelGGL((k3_step_batch<3, S>), grid, dim3(MCX_BLOCK), 0, s, a, jobs, (int)grid.x); return 0;
-    case 4: hipLaunchKernelGGL((k3_step_batch<4, S>), grid, dim3(MCX_BLOCK), 0, s, a, jobs, (int)grid.x); return 0;
-    case 5: hipLaunchKernelGGL((k3_step_batch<5, S>), grid, dim3(MCX_BLOCK), 0, s, a, jobs, (int)grid.x); return 0;
-    case 6: hipLaunchKernelGGL((k3_step_batch<6, S>), grid, dim3(MCX_BLOCK), 0, s, a, jobs, (int)grid.x); return 0;
-    default: return -1;
-    }
+    if (q.product < 0 || q.product >= b->n_products) MCX_FAIL(h, -2, "%s: job %d product out of range", who, j);
+    const DevProduct& pr = b->h_products[q.product];
+    if (pr.n_states != S) MCX_FAIL(h, -2, "%s: job %d has %d states, expected %d", who, j, pr.n_states, S);
+    if (q.roll_begin < 0 || q.roll_end < q.roll_begin || q.roll_end > pr.cf_end - pr.cf_begin) MCX_FAIL(h, -2, "%s: job %d roll window", who, j);
+    if (q.num_atom < 0 || q.num_atom >= b->n_atoms || q.x_atom < 0 || q.x_atom >= b->n_atoms) MCX_FAIL(h, -2, "%s: job %d atoms", who, j);
+    if (q.w_offset < 0 || q.w_offset + (int64_t)S * ld_w > w_len) MCX_FAIL(h, -2, "%s: job %d cache block outside d_W", who, j);
+    out.ev_off = pr.cf_begin; out.roll_begin = q.roll_begin; out.roll_end = q.roll_end; out.pad = 0; out.w_off = q.w_offset;
+    out.shift = q.shift; out.scale = q.scale; out.num = mcx_flat_atom(b->h_atoms[q.num_atom]); out.x = mcx_flat_atom(b->h_atoms[q.x_atom]);
+    return 0;
+}
+
+// the K3Solve of a date (mcx_lsm_date) or of a job (mcx_lsm_solve_job: the two records name these fields alike) of S states, its
+// coefficient blocks checked against the book; what / idx: "date 3", "job 17" of the message
+template <class Q>
+int k3_fill_solve(mcx_handle* h, const mcx_book* b, const Q& q, int S, const char* who, const char* what, int idx, K3Solve& out)
+{
+    for (int w = 0; w < 2; ++w)
+        if (q.coeff_off[w] >= 0 && q.coeff_off[w] + (int64_t)S * b->n_basis > b->n_coeffs)
+            MCX_FAIL(h, -2, "%s: %s %d coefficient offset out of range", who, what, idx);
+    memset(&out, 0, sizeof(out));
+    out.shift = q.shift; out.scale = q.scale; out.x0 = q.x0; out.off0 = q.coeff_off[0]; out.off1 = q.coeff_off[1];
+    out.degenerate = q.degenerate;
+    return 0;
 }
 
 }  // namespace
@@ -652,27 +586,14 @@ static int lsm_step_launch(mcx_handle* h, const mcx_book* b, int32_t product, in
     const int grid = mcx_grid_for(n_paths, MCX_BLOCK, 4 * h->n_cu);
     if ((size_t)grid * NM * sizeof(double) > h->ws_bytes) MCX_FAIL(h, -2, "%s: workspace too small", who);
     K3Args a;
-    a.etab = nullptr;
-    a.terms = b->d_terms; a.events = b->d_events + pr.cf_begin; a.atoms = b->d_atoms; a.coeffs = b->d_coeffs; a.paths = d_paths;
-    a.W = d_W; a.partials = h->d_ws; a.num = mcx_flat_atom(b->h_atoms[num_atom]); a.x = mcx_flat_atom(b->h_atoms[x_atom]); a.shift = shift; a.scale = scale;
-    a.n = n_paths; a.ld = ld; a.ld_w = ld_w; a.roll_begin = roll_begin; a.roll_end = roll_end; a.n_basis = K; a.n_state = b->n_state;
-    a.f32_cache = (flags & MCX_LSM_F32_CACHE) ? 1 : 0; a.bridge = b->d_bridge;
-    a.ex_mode = b->ex_mode; a.ex_bits = b->d_ex_bits; a.ex_ld = b->ex_ld; a.ev_base = pr.cf_begin;
-    a.vpoly = b->d_vpoly; a.vcoef = b->d_vcoef;
-    if (a.ex_mode && a.ex_ld < n_paths) MCX_FAIL(h, -2, "%s: exercise replay buffer narrower than the path count", who);
+    if (int rc = k3_fill_args(h, b, d_paths, n_paths, ld, d_W, ld_w, flags, who, a)) return rc;
+    a.events += pr.cf_begin; a.ev_base = pr.cf_begin; a.roll_begin = roll_begin; a.roll_end = roll_end; a.partials = h->d_ws;
+    a.num = mcx_flat_atom(b->h_atoms[num_atom]); a.x = mcx_flat_atom(b->h_atoms[x_atom]); a.shift = shift; a.scale = scale;
     const bool mfma = (flags & MCX_LSM_MFMA) != 0;
     int rc = -1;
-    switch (S) {
-    case 1: rc = dispatch_k3<1>(K, a, grid, mfma, s); break;
-    case 2: rc = dispatch_k3<2>(K, a, grid, mfma, s); break;
-    case 3: rc = dispatch_k3<3>(K, a, grid, mfma, s); break;
-    case 4: rc = dispatch_k3<4>(K, a, grid, mfma, s); break;
-    case 5: rc = dispatch_k3<5>(K, a, grid, mfma, s); break;
-    case 6: rc = dispatch_k3<6>(K, a, grid, mfma, s); break;
-    case 7: rc = dispatch_k3<7>(K, a, grid, mfma, s); break;
-    case 8: rc = dispatch_k3<8>(K, a, grid, mfma, s); break;
-    default: break;
-    }
+    K3_DISPATCH(K, S, if (mfma) hipLaunchKernelGGL((k3_step_mfma<KK, SS>), dim3(grid), dim3(MCX_BLOCK), 0, s, a);
+                      else hipLaunchKernelGGL((k3_step_valu<KK, SS>), dim3(grid), dim3(MCX_BLOCK), 0, s, a);
+                      rc = 0);
     if (rc != 0) MCX_FAIL(h, -3, "%s: unsupported (basis=%d, states=%d)", who, K, S);
     MCX_HIP(h, hipGetLastError());
     if (grid_out) { *grid_out = grid; return 0; }
@@ -696,12 +617,9 @@ extern "C" int mcx_lsm_solve(mcx_handle* h, mcx_book* b, int32_t product, const 
     if (!h || !b || !d_moments || !date || !d_table || !d_status) return -1;
     if (product < 0 || product >= b->n_products || date_index < 0) MCX_FAIL(h, -2, "mcx_lsm_solve: product / date index out of range");
     const int K = b->n_basis, S = b->h_products[product].n_states;
-    for (int w = 0; w < 2; ++w)
-        if (date->coeff_off[w] >= 0 && date->coeff_off[w] + (int64_t)S * K > b->n_coeffs) MCX_FAIL(h, -2, "mcx_lsm_solve: coefficient offset out of range");
     K3Solve sv;
-    sv.shift = date->shift; sv.scale = date->scale; sv.x0 = date->x0; sv.off0 = date->coeff_off[0]; sv.off1 = date->coeff_off[1];
-    sv.degenerate = date->degenerate; sv.K = K; sv.S = S; sv.date = date_index;
-    hipLaunchKernelGGL(k3_solve, dim3(1), dim3(64), 0, (hipStream_t)stream, d_moments, sv, b->d_coeffs, d_table, d_status);
+    if (int rc = k3_fill_solve(h, b, *date, S, "mcx_lsm_solve", "date", date_index, sv)) return rc;
+    hipLaunchKernelGGL(k3_solve, dim3(1), dim3(64), 0, (hipStream_t)stream, d_moments, sv, K, S, date_index, b->d_coeffs, d_table, d_status);
     MCX_HIP(h, hipGetLastError());
     return 0;
 }
@@ -715,10 +633,9 @@ extern "C" int mcx_lsm_run(mcx_handle* h, mcx_book* b, int32_t product, const mc
     if (product < 0 || product >= b->n_products) MCX_FAIL(h, -2, "mcx_lsm_run: product out of range");
     const int K = b->n_basis, S = b->h_products[product].n_states, NM = (2 * K - 1) + S * K;
     const size_t tab_bytes = sizeof(double) * (size_t)n_dates * S * K, st_bytes = sizeof(int32_t) * (size_t)n_dates;
+    std::vector<K3Solve> solves((size_t)n_dates);        // (every date is checked before the first launch)
     for (int d = 0; d < n_dates; ++d)
-        for (int w = 0; w < 2; ++w)
-            if (h_dates[d].coeff_off[w] >= 0 && h_dates[d].coeff_off[w] + (int64_t)S * K > b->n_coeffs)
-                MCX_FAIL(h, -2, "mcx_lsm_run: date %d coefficient offset out of range", d);
+        if (int rc = k3_fill_solve(h, b, h_dates[d], S, "mcx_lsm_run", "date", d, solves[d])) return rc;
     hipStream_t s = (hipStream_t)stream;
     // workspace of the run: [moments NM | table n_dates*S*K | status n_dates], a scratch buffer of the handle
     double* d_ws = (double*)mcx_scratch(h, 1, sizeof(double) * NM + tab_bytes + st_bytes + 64);
@@ -735,11 +652,9 @@ extern "C" int mcx_lsm_run(mcx_handle* h, mcx_book* b, int32_t product, const mc
                              d_mom, flags, s, "mcx_lsm_run", multi ? nullptr : &grid);
         if (rc != 0) break;
         if (multi) { rc = mcx_allreduce_f64(h, d_mom, NM, stream); if (rc != 0) break; }   // stream-ordered
-        K3Solve sv;
-        sv.shift = q.shift; sv.scale = q.scale; sv.x0 = q.x0; sv.off0 = q.coeff_off[0]; sv.off1 = q.coeff_off[1];
-        sv.degenerate = q.degenerate; sv.K = K; sv.S = S; sv.date = d;
-        if (!multi && grid > 0) hipLaunchKernelGGL(k3_finish_solve, dim3(1), dim3(1024), 0, s, h->d_ws, NM, grid, d_mom, sv, b->d_coeffs, d_tab, d_st);
-        else hipLaunchKernelGGL(k3_solve, dim3(1), dim3(64), 0, s, d_mom, sv, b->d_coeffs, d_tab, d_st);
+        const K3Solve& sv = solves[d];
+        if (!multi && grid > 0) hipLaunchKernelGGL(k3_finish_solve, dim3(1), dim3(1024), 0, s, h->d_ws, NM, grid, d_mom, sv, K, S, d, b->d_coeffs, d_tab, d_st);
+        else hipLaunchKernelGGL(k3_solve, dim3(1), dim3(64), 0, s, d_mom, sv, K, S, d, b->d_coeffs, d_tab, d_st);
         if (hipGetLastError() != hipSuccess) { h->err = "mcx_lsm_run: launch failed"; rc = -100; }
     }
     if (rc == 0 && (hipMemcpyAsync(h_coeffs, d_tab, tab_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -766,18 +681,8 @@ static int lsm_step_batch_impl(mcx_handle* h, const mcx_book* b, const mcx_lsm_j
         return 0;
     }
     std::vector<K3Job> jobs((size_t)n_jobs);
-    for (int j = 0; j < n_jobs; ++j) {
-        const mcx_lsm_job& q = h_jobs[j];
-        if (q.product < 0 || q.product >= b->n_products) MCX_FAIL(h, -2, "mcx_lsm_step_batch: job %d product out of range", j);
-        const DevProduct& pr = b->h_products[q.product];
-        if (pr.n_states != S) MCX_FAIL(h, -2, "mcx_lsm_step_batch: job %d has %d states, the batch %d", j, pr.n_states, S);
-        if (q.roll_begin < 0 || q.roll_end < q.roll_begin || q.roll_end > pr.cf_end - pr.cf_begin) MCX_FAIL(h, -2, "mcx_lsm_step_batch: job %d roll window", j);
-        if (q.num_atom < 0 || q.num_atom >= b->n_atoms || q.x_atom < 0 || q.x_atom >= b->n_atoms) MCX_FAIL(h, -2, "mcx_lsm_step_batch: job %d atoms", j);
-        if (q.w_offset < 0 || q.w_offset + (int64_t)S * ld_w > w_len) MCX_FAIL(h, -2, "mcx_lsm_step_batch: job %d cache block outside d_W", j);
-        K3Job& o = jobs[j];
-        o.ev_off = pr.cf_begin; o.roll_begin = q.roll_begin; o.roll_end = q.roll_end; o.pad = 0; o.w_off = q.w_offset;
-        o.shift = q.shift; o.scale = q.scale; o.num = mcx_flat_atom(b->h_atoms[q.num_atom]); o.x = mcx_flat_atom(b->h_atoms[q.x_atom]);
-    }
+    for (int j = 0; j < n_jobs; ++j)
+        if (int rc = k3_check_job(h, b, h_jobs[j], j, S, ld_w, w_len, "mcx_lsm_step_batch", jobs[j])) return rc;
     // few paths per product are the norm for big books: one block per 256 paths, capped
     int bpj = mcx_grid_for(n_paths, MCX_BLOCK, 64);
     const int max_jobs = 32768;
@@ -787,31 +692,14 @@ static int lsm_step_batch_impl(mcx_handle* h, const mcx_book* b, const mcx_lsm_j
     double* d_out = (double*)mcx_scratch(h, 3, sizeof(double) * (size_t)chunk * NM);
     if (!d_jobs || !d_part || !d_out) return -100;
     K3Args a;
-    a.etab = nullptr;
-    memset(&a, 0, sizeof(a));
-    a.terms = b->d_terms; a.events = b->d_events; a.atoms = b->d_atoms; a.coeffs = b->d_coeffs; a.paths = d_paths;
-    a.W = d_W; a.partials = d_part; a.n = n_paths; a.ld = ld; a.ld_w = ld_w; a.n_basis = K; a.n_state = b->n_state;
-    a.f32_cache = (flags & MCX_LSM_F32_CACHE) ? 1 : 0; a.bridge = b->d_bridge;
-    a.ex_mode = b->ex_mode; a.ex_bits = b->d_ex_bits; a.ex_ld = b->ex_ld; a.ev_base = 0;
-    a.vpoly = b->d_vpoly; a.vcoef = b->d_vcoef;
-    if (a.ex_mode && a.ex_ld < n_paths) MCX_FAIL(h, -2, "mcx_lsm_step_batch: exercise replay buffer narrower than the path count");
+    if (int rc = k3_fill_args(h, b, d_paths, n_paths, ld, d_W, ld_w, flags, "mcx_lsm_step_batch", a)) return rc;
+    a.partials = d_part;
     int rc = 0;
     for (int j0 = 0; j0 < n_jobs && rc == 0; j0 += chunk) {
         const int nj = n_jobs - j0 < chunk ? n_jobs - j0 : chunk;
         const K3Job* d_jobs_now = (const K3Job*)mcx_upload_call_data(h, jobs.data() + j0, sizeof(K3Job) * (size_t)nj, d_jobs, s);
         if (!d_jobs_now) return -100;
-        const dim3 grid(bpj, nj);
-        switch (S) {
-        case 1: rc = dispatch_k3_batch<1>(K, a, d_jobs_now, grid, s); break;
-        case 2: rc = dispatch_k3_batch<2>(K, a, d_jobs_now, grid, s); break;
-        case 3: rc = dispatch_k3_batch<3>(K, a, d_jobs_now, grid, s); break;
-        case 4: rc = dispatch_k3_batch<4>(K, a, d_jobs_now, grid, s); break;
-        case 5: rc = dispatch_k3_batch<5>(K, a, d_jobs_now, grid, s); break;
-        case 6: rc = dispatch_k3_batch<6>(K, a, d_jobs_now, grid, s); break;
-        case 7: rc = dispatch_k3_batch<7>(K, a, d_jobs_now, grid, s); break;
-        case 8: rc = dispatch_k3_batch<8>(K, a, d_jobs_now, grid, s); break;
-        default: rc = -1; break;
-        }
+        rc = k3_launch_batch(K, S, a, d_jobs_now, dim3(bpj, nj), s);
         if (rc != 0) break;
         double* dst = d_moments ? d_moments + (size_t)j0 * NM : d_out;
         hipLaunchKernelGGL(k3_finish_batch, dim3(nj), dim3(64), 0, s, d_part, NM, bpj, dst, NM);
@@ -842,26 +730,22 @@ extern "C" int mcx_lsm_step_batch_dev(mcx_handle* h, const mcx_book* b, const mc
 }
 
 namespace {
-struct K3SolveJob { double shift, scale, x0; int64_t off0, off1; int32_t degenerate, pad; };
 // one thread per (product, date) system of a batched step: solve + coefficient scatter on the device; a numerically singular
 // system raises the flag (its coefficients are not written: the caller repeats the induction with the host solver)
-__global__ __launch_bounds__(64) void k3_solve_batch(const double* __restrict__ moments, const K3SolveJob* __restrict__ jobs, int n_jobs,
+__global__ __launch_bounds__(64) void k3_solve_batch(const double* __restrict__ moments, const K3Solve* __restrict__ jobs, int n_jobs,
                                                      int K, int S, double* __restrict__ coeffs, int32_t* __restrict__ flag)
 {
     const int j = blockIdx.x * 64 + threadIdx.x;
     if (j >= n_jobs) return;
-    const K3SolveJob q = jobs[j];
-    K3Solve sv;
-    sv.shift = q.shift; sv.scale = q.scale; sv.x0 = q.x0; sv.off0 = q.off0; sv.off1 = q.off1;
-    sv.degenerate = q.degenerate; sv.K = K; sv.S = S; sv.date = 0;
+    const K3Solve q = jobs[j];
     int32_t st = 0;
-    k3_solve_body(moments + (int64_t)j * ((2 * K - 1) + S * K), sv, coeffs, nullptr, &st);
+    k3_solve_body(moments + (int64_t)j * ((2 * K - 1) + S * K), q, K, S, 0, coeffs, nullptr, &st);
     if (st) atomicOr(flag, 1);
 }
 // finish + solve of a batched step in ONE launch (mcx_lsm_run_batch on one GPU: no all-reduce between the two): thread j sums the
 // partial moments of job j over its blocks in the order k3_finish_batch does (bit-identical moments) and solves
 #define K3_NM_MAX ((2 * MCX_MAX_BASIS - 1) + MCX_MAX_STATES * MCX_MAX_BASIS)
-__global__ __launch_bounds__(64) void k3_finish_solve_batch(const double* __restrict__ partials, int blocks_per_job, const K3SolveJob* __restrict__ jobs,
+__global__ __launch_bounds__(64) void k3_finish_solve_batch(const double* __restrict__ partials, int blocks_per_job, const K3Solve* __restrict__ jobs,
                                                             int n_jobs, int K, int S, double* __restrict__ coeffs, int32_t* __restrict__ flag)
 {
     const int j = blockIdx.x * 64 + threadIdx.x;
@@ -873,12 +757,9 @@ __global__ __launch_bounds__(64) void k3_finish_solve_batch(const double* __rest
         for (int b = 0; b < blocks_per_job; ++b) s += partials[((int64_t)j * blocks_per_job + b) * nm + q];
         m[q] = s;
     }
-    const K3SolveJob q = jobs[j];
-    K3Solve sv;
-    sv.shift = q.shift; sv.scale = q.scale; sv.x0 = q.x0; sv.off0 = q.off0; sv.off1 = q.off1;
-    sv.degenerate = q.degenerate; sv.K = K; sv.S = S; sv.date = 0;
+    const K3Solve q = jobs[j];
     int32_t st = 0;
-    k3_solve_body(m, sv, coeffs, nullptr, &st);
+    k3_solve_body(m, q, K, S, 0, coeffs, nullptr, &st);
     if (st) atomicOr(flag, 1);
 }
 }  // namespace
@@ -890,18 +771,13 @@ extern "C" int mcx_lsm_solve_batch(mcx_handle* h, mcx_book* b, const mcx_lsm_sol
     if (n_jobs <= 0) return 0;
     const int K = b->n_basis, S = n_states;
     if (S < 1 || S > MCX_MAX_STATES) MCX_FAIL(h, -2, "mcx_lsm_solve_batch: n_states out of range");
-    std::vector<K3SolveJob> jobs((size_t)n_jobs);
-    for (int j = 0; j < n_jobs; ++j) {
-        const mcx_lsm_solve_job& q = h_jobs[j];
-        for (int w = 0; w < 2; ++w)
-            if (q.coeff_off[w] >= 0 && q.coeff_off[w] + (int64_t)S * K > b->n_coeffs) MCX_FAIL(h, -2, "mcx_lsm_solve_batch: job %d coefficient offset out of range", j);
-        K3SolveJob& o = jobs[j];
-        o.shift = q.shift; o.scale = q.scale; o.x0 = q.x0; o.off0 = q.coeff_off[0]; o.off1 = q.coeff_off[1]; o.degenerate = q.degenerate; o.pad = 0;
-    }
+    std::vector<K3Solve> jobs((size_t)n_jobs);
+    for (int j = 0; j < n_jobs; ++j)
+        if (int rc = k3_fill_solve(h, b, h_jobs[j], S, "mcx_lsm_solve_batch", "job", j, jobs[j])) return rc;
     hipStream_t s = (hipStream_t)stream;
-    K3SolveJob* d_jobs = (K3SolveJob*)mcx_scratch(h, 1, sizeof(K3SolveJob) * (size_t)n_jobs);      // (slot 1: the step's job table is consumed by then, stream order)
+    K3Solve* d_jobs = (K3Solve*)mcx_scratch(h, 1, sizeof(K3Solve) * (size_t)n_jobs);      // (slot 1: the step's job table is consumed by then, stream order)
     if (!d_jobs) return -100;
-    const K3SolveJob* d_jobs_now = (const K3SolveJob*)mcx_upload_call_data(h, jobs.data(), sizeof(K3SolveJob) * (size_t)n_jobs, d_jobs, s);
+    const K3Solve* d_jobs_now = (const K3Solve*)mcx_upload_call_data(h, jobs.data(), sizeof(K3Solve) * (size_t)n_jobs, d_jobs, s);
     if (!d_jobs_now) return -100;
     hipLaunchKernelGGL(k3_solve_batch, dim3((n_jobs + 63) / 64), dim3(64), 0, s, d_moments, d_jobs_now, n_jobs, K, S, b->d_coeffs, d_flag);
     MCX_HIP(h, hipGetLastError());
@@ -936,30 +812,17 @@ extern "C" int mcx_lsm_run_batch(mcx_handle* h, mcx_book* b, const mcx_lsm_job* 
         if (chunk > widest) widest = chunk;
     }
     std::vector<K3Job> jobs((size_t)n_jobs);
-    std::vector<K3SolveJob> solves((size_t)n_jobs);
+    std::vector<K3Solve> solves((size_t)n_jobs);
     for (int t = 0; t < n_steps; ++t) {
         const int S = h_step_states[t];
         for (int j = h_step_begin[t]; j < h_step_begin[t + 1]; ++j) {
-            const mcx_lsm_job& q = h_jobs[j];
-            if (q.product < 0 || q.product >= b->n_products) MCX_FAIL(h, -2, "mcx_lsm_run_batch: job %d product out of range", j);
-            const DevProduct& pr = b->h_products[q.product];
-            if (pr.n_states != S) MCX_FAIL(h, -2, "mcx_lsm_run_batch: job %d has %d states, its step %d", j, pr.n_states, S);
-            if (q.roll_begin < 0 || q.roll_end < q.roll_begin || q.roll_end > pr.cf_end - pr.cf_begin) MCX_FAIL(h, -2, "mcx_lsm_run_batch: job %d roll window", j);
-            if (q.num_atom < 0 || q.num_atom >= b->n_atoms || q.x_atom < 0 || q.x_atom >= b->n_atoms) MCX_FAIL(h, -2, "mcx_lsm_run_batch: job %d atoms", j);
-            if (q.w_offset < 0 || q.w_offset + (int64_t)S * ld_w > w_len) MCX_FAIL(h, -2, "mcx_lsm_run_batch: job %d cache block outside d_W", j);
-            K3Job& o = jobs[j];
-            o.ev_off = pr.cf_begin; o.roll_begin = q.roll_begin; o.roll_end = q.roll_end; o.pad = 0; o.w_off = q.w_offset;
-            o.shift = q.shift; o.scale = q.scale; o.num = mcx_flat_atom(b->h_atoms[q.num_atom]); o.x = mcx_flat_atom(b->h_atoms[q.x_atom]);
-            const mcx_lsm_solve_job& v = h_solve[j];
-            for (int w = 0; w < 2; ++w)
-                if (v.coeff_off[w] >= 0 && v.coeff_off[w] + (int64_t)S * K > b->n_coeffs) MCX_FAIL(h, -2, "mcx_lsm_run_batch: job %d coefficient offset out of range", j);
-            K3SolveJob& u = solves[j];
-            u.shift = v.shift; u.scale = v.scale; u.x0 = v.x0; u.off0 = v.coeff_off[0]; u.off1 = v.coeff_off[1]; u.degenerate = v.degenerate; u.pad = 0;
+            if (int rc = k3_check_job(h, b, h_jobs[j], j, S, ld_w, w_len, "mcx_lsm_run_batch", jobs[j])) return rc;
+            if (int rc = k3_fill_solve(h, b, h_solve[j], S, "mcx_lsm_run_batch", "job", j, solves[j])) return rc;
         }
     }
     hipStream_t s = (hipStream_t)stream;
     const int bpj = n_paths > 0 ? mcx_grid_for(n_paths, MCX_BLOCK, 64) : 1;
-    const size_t job_bytes = sizeof(K3Job) * (size_t)n_jobs, solve_bytes = sizeof(K3SolveJob) * (size_t)n_jobs;
+    const size_t job_bytes = sizeof(K3Job) * (size_t)n_jobs, solve_bytes = sizeof(K3Solve) * (size_t)n_jobs;
     unsigned char* d_tab = (unsigned char*)mcx_scratch(h, 1, job_bytes + solve_bytes);
     double* d_part = (double*)mcx_scratch(h, 2, sizeof(double) * (size_t)widest * bpj * nm_max);
     double* d_mom = (double*)mcx_scratch(h, 3, sizeof(double) * ((size_t)widest * nm_max + 1));
@@ -970,35 +833,19 @@ extern "C" int mcx_lsm_run_batch(mcx_handle* h, mcx_book* b, const mcx_lsm_job* 
     MCX_HIP(h, hipMemcpyAsync(d_tab + job_bytes, solves.data(), solve_bytes, hipMemcpyHostToDevice, s));
     MCX_HIP(h, hipMemsetAsync(d_flag, 0, sizeof(int32_t), s));
     const K3Job* d_jobs = (const K3Job*)d_tab;
-    const K3SolveJob* d_solves = (const K3SolveJob*)(d_tab + job_bytes);
+    const K3Solve* d_solves = (const K3Solve*)(d_tab + job_bytes);
     K3Args a;
-    memset(&a, 0, sizeof(a));
-    a.terms = b->d_terms; a.events = b->d_events; a.atoms = b->d_atoms; a.coeffs = b->d_coeffs; a.paths = d_paths;
-    a.W = d_W; a.partials = d_part; a.n = n_paths; a.ld = ld; a.ld_w = ld_w; a.n_basis = K; a.n_state = b->n_state;
-    a.f32_cache = (flags & MCX_LSM_F32_CACHE) ? 1 : 0; a.bridge = b->d_bridge;
-    a.ex_mode = b->ex_mode; a.ex_bits = b->d_ex_bits; a.ex_ld = b->ex_ld; a.ev_base = 0;
-    a.vpoly = b->d_vpoly; a.vcoef = b->d_vcoef;
-    if (a.ex_mode && a.ex_ld < n_paths) MCX_FAIL(h, -2, "mcx_lsm_run_batch: exercise replay buffer narrower than the path count");
+    if (int rc = k3_fill_args(h, b, d_paths, n_paths, ld, d_W, ld_w, flags, "mcx_lsm_run_batch", a)) return rc;
+    a.partials = d_part;
     const bool multi = h->comm && h->comm_ranks > 1;
     int rc = 0;
     for (int t = 0; t < n_steps && rc == 0; ++t) {
         const int S = h_step_states[t], NM = (2 * K - 1) + S * K;
         for (int j0 = h_step_begin[t]; j0 < h_step_begin[t + 1] && rc == 0; j0 += max_jobs) {
             const int nj = h_step_begin[t + 1] - j0 < max_jobs ? h_step_begin[t + 1] - j0 : max_jobs;
-            const dim3 grid(bpj, nj);
             if (n_paths <= 0) {                            // a rank without paths still takes part in the all-reduce
                 if (hipMemsetAsync(d_mom, 0, sizeof(double) * (size_t)nj * NM, s) != hipSuccess) { rc = -100; break; }
-            } else switch (S) {
-            case 1: rc = dispatch_k3_batch<1>(K, a, d_jobs + j0, grid, s); break;
-            case 2: rc = dispatch_k3_batch<2>(K, a, d_jobs + j0, grid, s); break;
-            case 3: rc = dispatch_k3_batch<3>(K, a, d_jobs + j0, grid, s); break;
-            case 4: rc = dispatch_k3_batch<4>(K, a, d_jobs + j0, grid, s); break;
-            case 5: rc = dispatch_k3_batch<5>(K, a, d_jobs + j0, grid, s); break;
-            case 6: rc = dispatch_k3_batch<6>(K, a, d_jobs + j0, grid, s); break;
-            case 7: rc = dispatch_k3_batch<7>(K, a, d_jobs + j0, grid, s); break;
-            case 8: rc = dispatch_k3_batch<8>(K, a, d_jobs + j0, grid, s); break;
-            default: rc = -1; break;
-            }
+            } else rc = k3_launch_batch(K, S, a, d_jobs + j0, dim3(bpj, nj), s);
             if (rc != 0) break;
             if (!multi && n_paths > 0) {
                 hipLaunchKernelGGL(k3_finish_solve_batch, dim3((nj + 63) / 64), dim3(64), 0, s, d_part, bpj, d_solves + j0, nj, K, S, b->d_coeffs, d_flag);

@@ -171,7 +171,4 @@ void k6_fill_date(const mcx_book* b, const mcx_storage_date& q, K6DateT<Atom>& o
 }
 
 // launch of a kernel template on the basis size: CALL with KK = K for 1 <= K <= KMAX (4 or 6), nothing otherwise
-#define K6_CASE(N, ...) case N: { constexpr int KK = N; __VA_ARGS__; } break;
-#define K6_CASES_4(...) K6_CASE(1, __VA_ARGS__) K6_CASE(2, __VA_ARGS__) K6_CASE(3, __VA_ARGS__) K6_CASE(4, __VA_ARGS__)
-#define K6_CASES_6(...) K6_CASES_4(__VA_ARGS__) K6_CASE(5, __VA_ARGS__) K6_CASE(6, __VA_ARGS__)
-#define K6_DISPATCH(K, KMAX, ...) switch (K) { K6_CASES_##KMAX(__VA_ARGS__) default: break; }
+#define K6_DISPATCH(K, KMAX, ...) MCX_DISPATCH(KK, K, KMAX, __VA_ARGS__)

@@ -9,8 +9,8 @@
 //                    One path per lane; a moment is reduced over the wave as soon as it is formed (S*K of them do not fit in
 //                    registers), lane 0 of each wave adds it to the wave's LDS row, one barrier at the end.
 //   k6_finish_solve  sums the per-block partials and solves the K x K normal equations for S right-hand sides, lane s taking
-//                    state s (same algorithm as k3_solve_t: LU with partial pivoting, back-transformation of the shifted /
-//                    scaled basis, minimum-norm solution of the exactly rank-1 system of the calibration date).
+//                    state s (lsm_solve.h, the solver k3_lsm.hip calls too: LU with partial pivoting, back-transformation of the
+//                    shifted / scaled basis, minimum-norm solution of the exactly rank-1 system of the calibration date).
 //   k6_step_batch / k6_finish_solve_batch   the same two for step r of MANY storages in one launch each (grid.y resp. grid.x = job):
 //                    the bodies of k6_step / k6_finish_solve as device functions, the job's record read with scalar loads.
 //   k6_eval          main simulation: the realised state of a path in a register, walked through the action dates and the
@@ -20,6 +20,7 @@
 // The per-path arithmetic up to the candidates, the date record and its host checks live in k6_common.h, which kt_storage.hip
 // (the tangent images of k6_step and k6_eval) shares.
 #include "k6_common.h"
+#include "lsm_solve.h"
 
 #include <stdlib.h>
 
@@ -137,82 +138,21 @@ struct K6Solve {
     int32_t degenerate, S, date, pad;
 };
 
-// right-hand side s of the K x K system in m[] (k3_solve_t for one state; every lane factorises the same Gram matrix in registers);
-// table: the system's own [S][K] block or nullptr, status: the system's own word
+// right-hand side s of the K x K system in m[]: lsm_solve (lsm_solve.h) for one state, every lane factorises the same Gram matrix in
+// registers; here only the stores.  table: the system's own [S][K] block or nullptr, status: the system's own word
 template <int K>
 __device__ __forceinline__ void k6_solve_state(const double* __restrict__ m, const K6Solve& q, int s, double* __restrict__ coeffs,
                                                double* __restrict__ table, int32_t* __restrict__ status)
 {
-    double out[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) out[k] = 0.0;
-    const double n = m[0];
-    int st = 0;
-    if (n > 0.0 && q.degenerate) {
-        double v[K], vv = 0.0, xp = 1.0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) { v[k] = xp; vv += xp * xp; xp *= q.x0; }
-        const double mean_y = m[(2 * K - 1) + s * K] / n;
-#pragma unroll
-        for (int k = 0; k < K; ++k) out[k] = v[k] * (mean_y / vv);
-    } else if (n > 0.0) {
-        double G[K][K], B[K];
-        double gmax = 0.0;
-#pragma unroll
-        for (int j = 0; j < K; ++j)
-#pragma unroll
-            for (int k = 0; k < K; ++k) { G[j][k] = m[j + k]; gmax = fmax(gmax, fabs(G[j][k])); }
-#pragma unroll
-        for (int k = 0; k < K; ++k) B[k] = m[(2 * K - 1) + s * K + k];
-#pragma unroll
-        for (int c = 0; c < K; ++c) {                                  // LU, partial pivoting by conditional row swaps
-#pragma unroll
-            for (int r = c + 1; r < K; ++r) {
-                const bool sw = fabs(G[r][c]) > fabs(G[c][c]);
-#pragma unroll
-                for (int k = 0; k < K; ++k) { const double x = G[c][k], y = G[r][k]; G[c][k] = sw ? y : x; G[r][k] = sw ? x : y; }
-                { const double x = B[c], y = B[r]; B[c] = sw ? y : x; B[r] = sw ? x : y; }
-            }
-            if (!(fabs(G[c][c]) > 1e-14 * gmax)) st = 1;               // numerically singular: reported, not written
-            const double piv = st ? 1.0 : G[c][c];
-#pragma unroll
-            for (int r = c + 1; r < K; ++r) {
-                const double f = G[r][c] / piv;
-#pragma unroll
-                for (int k = c + 1; k < K; ++k) G[r][k] -= f * G[c][k];
-                B[r] -= f * B[c];
-            }
-        }
-        if (st == 0) {
-#pragma unroll
-            for (int c = K - 1; c >= 0; --c) {
-                double acc = B[c];
-#pragma unroll
-                for (int k = c + 1; k < K; ++k) acc -= G[c][k] * B[k];
-                B[c] = acc / G[c][c];
-            }
-            double sp = 1.0;                                           // coefficient of x^j in z^k = scale^k C(k, j) (-shift)^(k-j)
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                double binom = 1.0;
-#pragma unroll
-                for (int j = 0; j <= k; ++j) {
-                    double ms = 1.0;
-                    for (int e = 0; e < k - j; ++e) ms *= -q.shift;
-                    out[j] += sp * binom * ms * B[k];
-                    binom = binom * (double)(k - j) / (double)(j + 1);
-                }
-                sp *= q.scale;
-            }
-        }
-    }
-    if (s == 0) *status = st;
+    double out[1][K];
+    const int st = lsm_solve<K, 1>(m, K, s, 1, q.shift, q.scale, q.x0, q.degenerate, out);
+    if (s == 0) *status = st;                                          // numerically singular: reported, not written
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        if (table) table[s * K + k] = out[k];
+        if (table) table[s * K + k] = out[0][k];
         if (st == 0) {
-            if (q.off0 >= 0) coeffs[q.off0 + s * K + k] = out[k];
-            if (q.off1 >= 0) coeffs[q.off1 + s * K + k] = out[k];
+            if (q.off0 >= 0) coeffs[q.off0 + s * K + k] = out[0][k];
+            if (q.off1 >= 0) coeffs[q.off1 + s * K + k] = out[0][k];
         }
     }
 }

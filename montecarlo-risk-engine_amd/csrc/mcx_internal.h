@@ -58,6 +58,14 @@ struct mcx_handle {
         if (_e != hipSuccess) MCX_FAIL(h, -100 - (int)_e, "%s failed: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
+// launch of a kernel template on a run-time size: the statements after NMAX with the constant VAR = N for 1 <= N <= NMAX
+// (4, 6 or 8), nothing otherwise.  Nests: MCX_DISPATCH(SS, S, 8, MCX_DISPATCH(KK, K, 6, ...)).
+#define MCX_CASE(VAR, N, ...) case N: { constexpr int VAR = N; __VA_ARGS__; } break;
+#define MCX_CASES_4(VAR, ...) MCX_CASE(VAR, 1, __VA_ARGS__) MCX_CASE(VAR, 2, __VA_ARGS__) MCX_CASE(VAR, 3, __VA_ARGS__) MCX_CASE(VAR, 4, __VA_ARGS__)
+#define MCX_CASES_6(VAR, ...) MCX_CASES_4(VAR, __VA_ARGS__) MCX_CASE(VAR, 5, __VA_ARGS__) MCX_CASE(VAR, 6, __VA_ARGS__)
+#define MCX_CASES_8(VAR, ...) MCX_CASES_6(VAR, __VA_ARGS__) MCX_CASE(VAR, 7, __VA_ARGS__) MCX_CASE(VAR, 8, __VA_ARGS__)
+#define MCX_DISPATCH(VAR, N, NMAX, ...) switch (N) { MCX_CASES_##NMAX(VAR, __VA_ARGS__) default: break; }
+
 // ---- flattened device records ---------------------------------------------------------------------------------------
 struct DevAtom {            // value = a + d*x + b*exp(c0 + c1*x), x = paths[(t_idx*D + col)*ld + i]
     int32_t t_idx, col;
