@@ -296,6 +296,17 @@ void mcx_book_destroy(mcx_book* book);
 int  mcx_book_set_coeffs(mcx_handle* h, mcx_book* book, int64_t offset, int64_t count, const double* h_coeffs, void* stream);
 int  mcx_eval_book(mcx_handle* h, const mcx_book* book, const double* d_paths, int64_t n_paths, int64_t ld,
                    double* d_cfs, double* d_expo, int64_t ld_out, void* stream);
+/* Route query (read-only; tests, diagnostics): what mcx_eval_book launches for n_paths paths and the output leading dimension
+ * ld_out, from the same host function that chooses the launch.  out[MCX_K2DESC_*]: the kernel (MCX_K2_SCALAR: one path per lane;
+ * MCX_K2_CHUNKED: the one-path kernel over chunks of consecutive products, whose images a second kernel adds in chunk order;
+ * MCX_K2_MULTI: several paths per lane), the paths per lane, the MCX_K2F_* event families compiled into the multi-path kernel
+ * (0 on the other routes), the number of product chunks, the products per chunk (0 unless chunked) and the blocks along the
+ * paths.  Returns the number of entries (MCX_K2DESC_COUNT); when that exceeds cap nothing is written; < 0 on error. */
+enum { MCX_K2_SCALAR = 0, MCX_K2_CHUNKED = 1, MCX_K2_MULTI = 2 };
+enum { MCX_K2F_DEN = 1, MCX_K2F_EXOTIC = 2, MCX_K2F_EXERCISE = 4, MCX_K2F_BS_EXPO = 8 };
+enum { MCX_K2DESC_KERNEL = 0, MCX_K2DESC_PPL = 1, MCX_K2DESC_FEAT = 2, MCX_K2DESC_N_CHUNKS = 3, MCX_K2DESC_CHUNK_PRODUCTS = 4,
+       MCX_K2DESC_GRID = 5, MCX_K2DESC_COUNT = 6 };
+int  mcx_eval_book_describe(mcx_handle* h, const mcx_book* book, int64_t n_paths, int64_t ld_out, int32_t* out, int32_t cap);
 /* Value polynomials.  An event whose cash value sums >= min_terms atoms of ONE state variable x of one date — a Bermudan swaption's
  * exercise value is the underlying swap priced from ~35-64 zero-bond requests per exercise date (products/bermudan_option.py:40-43,
  * 93-131; products/bond.py:42-68, 115-163) — is a smooth function f(x) = sum_j w_j (a_j + d_j x + b_j exp(c0_j + c1_j x)).

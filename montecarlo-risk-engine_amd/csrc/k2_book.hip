@@ -172,7 +172,7 @@ __global__ __launch_bounds__(MCX_BLOCK) void k2_eval_book(const K2Args a)
 // PPL x 64 paths.  Books with barrier events (per-path bridge RNG) and the product-chunked mode stay on the kernel above.
 // FEAT: the event families the book contains (host-side scan); everything else compiles out, which is what keeps the common
 // books (cashflows, plain options, polynomial exposures) at 8 resident waves per SIMD.
-enum { K2F_DEN = 1, K2F_EXOTIC = 2, K2F_EXERCISE = 4, K2F_BS_EXPO = 8, K2F_ALL = 15 };
+enum { K2F_DEN = MCX_K2F_DEN, K2F_EXOTIC = MCX_K2F_EXOTIC, K2F_EXERCISE = MCX_K2F_EXERCISE, K2F_BS_EXPO = MCX_K2F_BS_EXPO, K2F_ALL = 15 };
 template <int PPL, int FEAT>
 __global__ __launch_bounds__(MCX_BLOCK) void k2_eval_book_v(const K2Args a)
 {
@@ -396,6 +396,63 @@ __global__ __launch_bounds__(MCX_BLOCK) void k2_resolve(const DevAtom* __restric
     out[(int64_t)q * ld_out + i] = dev_atom(ldk_struct(&atoms[ldk(ids + q)]), paths, D, ld, i);
 }
 
+// ---- the launch of a book pass ----------------------------------------------------------------------------------------------
+// The one place that decides which kernel mcx_eval_book runs (it launches from this record, mcx_eval_book_describe reports it).
+#ifndef MCX_K2_PPL
+#define MCX_K2_PPL 2
+#endif
+#ifndef MCX_K2_PPL_LIGHT
+#define MCX_K2_PPL_LIGHT 4
+#endif
+struct K2Route {
+    int kernel;           // MCX_K2_SCALAR / MCX_K2_CHUNKED / MCX_K2_MULTI
+    int ppl;              // paths per lane
+    int feat;             // FEAT mask of the k2_eval_book_v instantiation (0 on the other routes)
+    int n_chunks;         // product chunks (blockIdx.y); 1 unless chunked
+    int chunk_products;   // products per chunk; 0 unless chunked
+    int grid;             // blocks along the paths
+};
+
+K2Route k2_route(const mcx_book* b, int64_t n_paths, int64_t ld_out, int n_cu)
+{
+    K2Route r = {MCX_K2_SCALAR, 1, 0, 1, 0, 0};
+    const int grid = (int)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK);
+    r.grid = grid;
+    // Few paths x many products (the reference's 5,000-product books run on ~1,000 paths): the path grid alone leaves the
+    // chip empty (4 workgroups) while every lane walks ~10^6 events.  Split the PRODUCT list over blockIdx.y instead; each
+    // chunk accumulates into its own image, a second kernel adds the images in chunk order.
+    const size_t img = (size_t)b->n_netting_sets * ((b->want_expo ? b->n_expo_rows : 0) + (b->want_cfs ? 1 : 0)) * (size_t)ld_out * sizeof(double);
+    int n_chunks = 1;
+    if (grid < 64 && b->n_products >= 64 && ld_out == n_paths && img > 0) {
+        n_chunks = std::min(std::min(1024 / grid, b->n_products / 8), (int)std::max<size_t>(1, ((size_t)512 << 20) / img));
+        if (n_chunks < 2) n_chunks = 1;
+    }
+    if (n_chunks > 1) {
+        r.kernel = MCX_K2_CHUNKED;
+        r.chunk_products = (b->n_products + n_chunks - 1) / n_chunks;
+        r.n_chunks = (b->n_products + r.chunk_products - 1) / r.chunk_products;
+        return r;
+    }
+    // Books with barrier events (per-path bridge RNG) stay on the one-path kernel; so does every run too small to fill the chip
+    // at MCX_K2_PPL paths per lane.
+    if (b->has_barrier || grid < 8 * n_cu) return r;
+    constexpr int PPL = MCX_K2_PPL, PL = MCX_K2_PPL_LIGHT;
+    const int feat = (b->has_exotic ? K2F_EXOTIC : 0) | (b->has_exercise ? K2F_EXERCISE : 0) | (b->has_bs_expo ? K2F_BS_EXPO : 0) |
+                     (b->has_den ? K2F_DEN : 0);          // (found once, at mcx_book_create)
+    // cashflow / plain-option / polynomial-exposure books are light on registers: more paths per lane, so that every
+    // wave of a million-path run is resident at once and the event chain is walked once per 256 paths
+    const bool wide = grid >= 4 * PL * n_cu && (feat == 0 || feat == K2F_DEN);
+    r.kernel = MCX_K2_MULTI;
+    r.ppl = wide ? PL : PPL;
+    r.grid = (int)((n_paths + (int64_t)MCX_BLOCK * r.ppl - 1) / ((int64_t)MCX_BLOCK * r.ppl));
+    // the instantiations: 0, DEN, DEN|EXERCISE, DEN|EXERCISE|EXOTIC, ALL (a book takes the smallest that holds its families)
+    if (feat == 0 || feat == K2F_DEN) r.feat = feat;
+    else if (!(feat & (K2F_EXOTIC | K2F_BS_EXPO))) r.feat = K2F_DEN | K2F_EXERCISE;
+    else if (!(feat & K2F_BS_EXPO)) r.feat = K2F_DEN | K2F_EXERCISE | K2F_EXOTIC;
+    else r.feat = K2F_ALL;
+    return r;
+}
+
 }  // namespace
 
 extern "C" int mcx_eval_book(mcx_handle* h, const mcx_book* b, const double* d_paths, int64_t n_paths, int64_t ld,
@@ -420,50 +477,28 @@ extern "C" int mcx_eval_book(mcx_handle* h, const mcx_book* b, const double* d_p
     a.ex_mode = b->ex_mode; a.ex_bits = b->d_ex_bits; a.ex_ld = b->ex_ld;
     a.vpoly = b->d_vpoly; a.vcoef = b->d_vcoef;
     if (a.ex_mode && a.ex_ld < n_paths) MCX_FAIL(h, -2, "mcx_eval_book: exercise replay buffer narrower than the path count");
-    const int grid = (int)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK);
-    // Few paths x many products (the reference's 5,000-product books run on ~1,000 paths): the path grid alone leaves the
-    // chip empty (4 workgroups) while every lane walks ~10^6 events.  Split the PRODUCT list over blockIdx.y instead; each
-    // chunk accumulates into its own image, a second kernel adds the images in chunk order.
-    const size_t img = (size_t)b->n_netting_sets * ((b->want_expo ? b->n_expo_rows : 0) + (b->want_cfs ? 1 : 0)) * (size_t)ld_out * sizeof(double);
-    int n_chunks = 1;
-    if (grid < 64 && b->n_products >= 64 && ld_out == n_paths && img > 0) {
-        n_chunks = std::min(std::min(1024 / grid, b->n_products / 8), (int)std::max<size_t>(1, ((size_t)512 << 20) / img));
-        if (n_chunks < 2) n_chunks = 1;
+    const K2Route r = k2_route(b, n_paths, ld_out, h->n_cu);
+    if (r.kernel == MCX_K2_MULTI) {
+        const dim3 g(r.grid), blk(MCX_BLOCK);
+        constexpr int PPL = MCX_K2_PPL, PL = MCX_K2_PPL_LIGHT;
+        if (r.ppl == PL && r.feat == 0) hipLaunchKernelGGL((k2_eval_book_v<PL, 0>), g, blk, 0, s, a);
+        else if (r.ppl == PL) hipLaunchKernelGGL((k2_eval_book_v<PL, K2F_DEN>), g, blk, 0, s, a);
+        else if (r.feat == 0) hipLaunchKernelGGL((k2_eval_book_v<PPL, 0>), g, blk, 0, s, a);
+        else if (r.feat == K2F_DEN) hipLaunchKernelGGL((k2_eval_book_v<PPL, K2F_DEN>), g, blk, 0, s, a);
+        else if (r.feat == (K2F_DEN | K2F_EXERCISE)) hipLaunchKernelGGL((k2_eval_book_v<PPL, K2F_DEN | K2F_EXERCISE>), g, blk, 0, s, a);
+        else if (r.feat == (K2F_DEN | K2F_EXERCISE | K2F_EXOTIC)) hipLaunchKernelGGL((k2_eval_book_v<PPL, K2F_DEN | K2F_EXERCISE | K2F_EXOTIC>), g, blk, 0, s, a);
+        else hipLaunchKernelGGL((k2_eval_book_v<PPL, K2F_ALL>), g, blk, 0, s, a);
+        MCX_HIP(h, hipGetLastError());
+        return 0;
     }
-    if (n_chunks == 1) {
-        const bool barrier = b->has_barrier;
-#ifndef MCX_K2_PPL
-#define MCX_K2_PPL 2
-#endif
-        constexpr int PPL = MCX_K2_PPL;
-        if (!barrier && grid >= 8 * h->n_cu) {          // enough paths to fill the chip at PPL paths per lane
-            const int gv = (int)((n_paths + (int64_t)MCX_BLOCK * PPL - 1) / ((int64_t)MCX_BLOCK * PPL));
-            const int feat = (b->has_exotic ? K2F_EXOTIC : 0) | (b->has_exercise ? K2F_EXERCISE : 0) | (b->has_bs_expo ? K2F_BS_EXPO : 0) |
-                             (b->has_den ? K2F_DEN : 0);          // (found once, at mcx_book_create)
-#ifndef MCX_K2_PPL_LIGHT
-#define MCX_K2_PPL_LIGHT 4
-#endif
-            // cashflow / plain-option / polynomial-exposure books are light on registers: more paths per lane, so that every
-            // wave of a million-path run is resident at once and the event chain is walked once per 256 paths
-            constexpr int PL = MCX_K2_PPL_LIGHT;
-            const bool wide = grid >= 4 * PL * h->n_cu;
-            const int gl = (int)((n_paths + (int64_t)MCX_BLOCK * PL - 1) / ((int64_t)MCX_BLOCK * PL));
-            if (feat == 0 && wide) hipLaunchKernelGGL((k2_eval_book_v<PL, 0>), dim3(gl), dim3(MCX_BLOCK), 0, s, a);
-            else if (feat == K2F_DEN && wide) hipLaunchKernelGGL((k2_eval_book_v<PL, K2F_DEN>), dim3(gl), dim3(MCX_BLOCK), 0, s, a);
-            else if (feat == 0) hipLaunchKernelGGL((k2_eval_book_v<PPL, 0>), dim3(gv), dim3(MCX_BLOCK), 0, s, a);
-            else if (feat == K2F_DEN) hipLaunchKernelGGL((k2_eval_book_v<PPL, K2F_DEN>), dim3(gv), dim3(MCX_BLOCK), 0, s, a);
-            else if (!(feat & (K2F_EXOTIC | K2F_BS_EXPO))) hipLaunchKernelGGL((k2_eval_book_v<PPL, K2F_DEN | K2F_EXERCISE>), dim3(gv), dim3(MCX_BLOCK), 0, s, a);
-            else if (!(feat & K2F_BS_EXPO)) hipLaunchKernelGGL((k2_eval_book_v<PPL, K2F_DEN | K2F_EXERCISE | K2F_EXOTIC>), dim3(gv), dim3(MCX_BLOCK), 0, s, a);
-            else hipLaunchKernelGGL((k2_eval_book_v<PPL, K2F_ALL>), dim3(gv), dim3(MCX_BLOCK), 0, s, a);
-            MCX_HIP(h, hipGetLastError());
-            return 0;
-        }
+    const int grid = r.grid;
+    if (r.kernel == MCX_K2_SCALAR) {
         hipLaunchKernelGGL(k2_eval_book, dim3(grid), dim3(MCX_BLOCK), 0, s, a);
         MCX_HIP(h, hipGetLastError());
         return 0;
     }
-    a.chunk_products = (b->n_products + n_chunks - 1) / n_chunks;
-    n_chunks = (b->n_products + a.chunk_products - 1) / a.chunk_products;
+    const int n_chunks = r.n_chunks;
+    a.chunk_products = r.chunk_products;
     const int64_t n_cfs = b->want_cfs ? (int64_t)b->n_netting_sets * ld_out : 0;
     const int64_t n_expo = b->want_expo ? (int64_t)b->n_netting_sets * b->n_expo_rows * ld_out : 0;
     double* d_part = (double*)mcx_scratch(h, 2, sizeof(double) * (size_t)n_chunks * (size_t)(n_cfs + n_expo));
@@ -494,4 +529,15 @@ extern "C" int mcx_resolve_atoms(mcx_handle* h, const mcx_book* b, const int32_t
                        n_paths, ld, d_out, ld_out);
     MCX_HIP(h, hipGetLastError());
     return 0;          // stream-ordered
+}
+
+extern "C" int mcx_eval_book_describe(mcx_handle* h, const mcx_book* b, int64_t n_paths, int64_t ld_out, int32_t* out, int32_t cap)
+{
+    if (!h || !b) return -1;
+    if (n_paths <= 0 || ld_out < n_paths) return -2;
+    if (cap < MCX_K2DESC_COUNT || !out) return MCX_K2DESC_COUNT;
+    const K2Route r = k2_route(b, n_paths, ld_out, h->n_cu);
+    out[MCX_K2DESC_KERNEL] = r.kernel; out[MCX_K2DESC_PPL] = r.ppl; out[MCX_K2DESC_FEAT] = r.feat;
+    out[MCX_K2DESC_N_CHUNKS] = r.n_chunks; out[MCX_K2DESC_CHUNK_PRODUCTS] = r.chunk_products; out[MCX_K2DESC_GRID] = r.grid;
+    return MCX_K2DESC_COUNT;
 }

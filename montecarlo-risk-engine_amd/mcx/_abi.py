@@ -81,6 +81,10 @@ FUSED_MAX_STATEFUL = 4
 # mcx_fused_describe (include/mcx.h): MCX_ROUTE_* and the header length MCX_FDESC_HEADER
 ROUTE_NONE, ROUTE_LEAN, ROUTE_FUSED = 0, 1, 2
 FDESC_HEADER = 16
+# mcx_eval_book_describe (include/mcx.h): MCX_K2_* kernels, MCX_K2F_* event families, MCX_K2DESC_COUNT entries
+K2_SCALAR, K2_CHUNKED, K2_MULTI = 0, 1, 2
+K2F_DEN, K2F_EXOTIC, K2F_EXERCISE, K2F_BS_EXPO = 1, 2, 4, 8
+K2DESC_COUNT = 6
 
 
 def ptr(a: np.ndarray | None) -> C.c_void_p:

@@ -21,7 +21,7 @@ _EXPORTS = [
     "mcx_abi_version", "mcx_create", "mcx_destroy", "mcx_last_error", "mcx_device_info",
     "mcx_sim_create", "mcx_sim_destroy", "mcx_generate_paths", "mcx_generate_paths_from_state", "mcx_rng_draws",
     "mcx_comm_unique_id", "mcx_comm_init", "mcx_comm_destroy", "mcx_allreduce_f64", "mcx_allgather_f64",
-    "mcx_book_create", "mcx_book_destroy", "mcx_book_set_coeffs", "mcx_eval_book", "mcx_resolve_atoms",
+    "mcx_book_create", "mcx_book_destroy", "mcx_book_set_coeffs", "mcx_eval_book", "mcx_eval_book_describe", "mcx_resolve_atoms",
     "mcx_lsm_stats", "mcx_lsm_step", "mcx_lsm_run", "mcx_lsm_solve", "mcx_lsm_step_batch", "mcx_lsm_step_batch_dev", "mcx_lsm_solve_batch", "mcx_lsm_run_batch", "mcx_book_get_coeffs", "mcx_book_set_coeffs_batch", "mcx_book_set_bridge_rng", "mcx_book_set_exercise_replay",
     "mcx_fused_is_straight_line", "mcx_tangent_paths", "mcx_tangent_lsm", "mcx_tangent_lsm_step", "mcx_tangent_eval", "mcx_tangent_cva", "mcx_tangent_profiles", "mcx_tangent_pick",
     "mcx_box_muller", "mcx_tangent_european", "mcx_fused_create", "mcx_fused_destroy", "mcx_fused_num_records", "mcx_fused_run", "mcx_fused_eval_paths", "mcx_fused_run_device", "mcx_fused_eval_paths_device", "mcx_fused_set_timing", "mcx_fused_kernel_times", "mcx_fused_describe",
@@ -71,6 +71,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_fused_num_records.argtypes = [C.c_void_p]
     lib.mcx_fused_is_straight_line.argtypes = [C.c_void_p]
     lib.mcx_fused_describe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+    lib.mcx_eval_book_describe.argtypes = [vp, vp, i64, i64, vp, i32]
     if lib.mcx_abi_version() != _abi.ABI_VERSION:
         raise RuntimeError("libmcx_hip.so ABI version mismatch")
     return lib
@@ -284,6 +285,18 @@ class HipBackend:
             _vp(cfs.data_ptr() if cfs is not None else 0), _vp(expo.data_ptr() if expo is not None else 0),
             C.c_int64(_ld_out(cfs, expo, n)), self._stream()), "mcx_eval_book")
         return cfs, expo
+
+    def book_describe(self, book, n_paths: int, ld_out: int | None = None) -> dict:
+        """the launch of mcx_eval_book for n_paths paths and output leading dimension ld_out (mcx_eval_book_describe): kernel
+        "scalar" / "chunked" / "multi", paths per lane `ppl`, the FEAT mask `feat` of the multi-path instantiation, `n_chunks`,
+        `chunk_products` and the path `grid`"""
+        out = np.zeros(_abi.K2DESC_COUNT, dtype=np.int32)
+        rc = self.lib.mcx_eval_book_describe(self.h, book.ptr, n_paths, n_paths if ld_out is None else ld_out, _abi.ptr(out),
+                                             _abi.K2DESC_COUNT)
+        if rc != _abi.K2DESC_COUNT:
+            raise RuntimeError(f"mcx_eval_book_describe failed ({rc})")
+        kernel = {_abi.K2_SCALAR: "scalar", _abi.K2_CHUNKED: "chunked", _abi.K2_MULTI: "multi"}[int(out[0])]
+        return dict(kernel=kernel, ppl=int(out[1]), feat=int(out[2]), n_chunks=int(out[3]), chunk_products=int(out[4]), grid=int(out[5]))
 
     def resolve_atoms(self, book, atom_ids, paths: torch.Tensor) -> torch.Tensor:
         ids = np.ascontiguousarray(atom_ids, dtype=np.int32)
