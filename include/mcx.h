@@ -424,6 +424,22 @@ int  mcx_tangent_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot,
 int  mcx_tangent_lsm(mcx_handle* h, const mcx_book* book, int32_t product, int32_t first_event, int32_t num_atom, int32_t x_atom,
                      double shift, double scale, const double* d_datoms, const double* d_paths, const double* d_dpaths,
                      int64_t n_paths, int64_t ld, int32_t n_dates, double* h_moments, void* stream);
+/* mcx_tangent_lsm for a table of (product, regression date) jobs: job j returns in h_moments [n_jobs][1+NP][(2K-1)+K] exactly what
+ * mcx_tangent_lsm returns for the same arguments, bit for bit (one device function forms the tile sums of both, every job keeps the
+ * tiling of the single call, the tiles of a job are added in ascending order).  The id tables of the book and the job table are
+ * uploaded once per call; the jobs run in launches of grid (tiles, jobs) with partial sums [job][tile][1+NP][NM] in the handle's
+ * workspace, split over several launches of WHOLE jobs where they do not fit (results do not depend on the split); one copy of all
+ * moments and ONE synchronisation at the end.  The environment variable MCX_TANGENT_BATCH_PARTIAL_BYTES (a positive integer, read at
+ * each call) lowers the bytes of partial sums one launch may use — for tests of the split; unset, nothing changes; a launch always
+ * takes at least one job.
+ * Every job is checked on the host before the first launch, as mcx_tangent_lsm checks its arguments (-2: product, first_event or an
+ * atom out of range, ld < n_paths; MCX_E_NOT_FUSABLE: a product with exercise states, an event without tangent form, an option over
+ * per-term denominators, a basis size above 4): on a failed check nothing is enqueued and h_moments is not written.
+ * n_jobs == 0: returns 0; n_paths <= 0: h_moments is zeroed. */
+typedef struct { int32_t product, first_event, num_atom, x_atom; double shift, scale; } mcx_tangent_lsm_job;
+int  mcx_tangent_lsm_batch(mcx_handle* h, const mcx_book* book, const mcx_tangent_lsm_job* h_jobs, int32_t n_jobs,
+                           const double* d_datoms, const double* d_paths, const double* d_dpaths, int64_t n_paths, int64_t ld,
+                           int32_t n_dates, double* h_moments /* [n_jobs][1+NP][(2K-1)+K] */, void* stream);
 /* the same for a product with exercise rights (Bermudan / American / FlexiCall, bermudan_option.py:93-131, flexicall.py:118-133):
  * one step of the backward induction in dual numbers.  d_W [S][ld_w] / d_dW [NP][S][ld_w] are the cashflow cache per hypothetical
  * state and its tangents (zero before the first step); the step rolls them over the product's cash events

@@ -15,6 +15,10 @@
 // Scope: EULER scheme; Black-Scholes / Vasicek / CIR++ (stochastic and deterministic) slots; cashflow, plain option and exercise
 // events, polynomial (also state-indexed) and analytic Black-Scholes exposures; thresholds and MPoR collateral in the metric
 // kernels.  Anything else keeps the common-random-number bump path.
+#include <stdlib.h>
+
+#include <algorithm>
+
 #include "mcx_dual.h"
 
 namespace {
@@ -347,18 +351,32 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_lsm_step(const KTSArgs a)
 }
 
 // ---- LSM moments with tangents ------------------------------------------------------------------------------------------
+// one (product, regression date): the flattened numeraire / explanatory atoms, their ids and the product's cash events it sums
+struct KTLJob {
+    DevAtom num, x;
+    double shift, scale;
+    int32_t ev_first, ev_end, num_id, x_id;
+};
 struct KTLArgs {
     KTBook b;
     const KTEventIds* __restrict__ ev_ids;     // [n_events]
     const int32_t* __restrict__ term_atom;     // [n_terms] atom id of every term
-    DevAtom num, x;
-    double shift, scale;
+    KTLJob job;
     double* __restrict__ partials;             // [gridDim.x][(1+NP)][NM]
-    int32_t ev_first, ev_end, num_id, x_id;
+};
+struct KTLBatchArgs {
+    KTBook b;
+    const KTEventIds* __restrict__ ev_ids;
+    const int32_t* __restrict__ term_atom;
+    const KTLJob* __restrict__ jobs;           // [gridDim.y] the jobs of this launch
+    double* __restrict__ partials;             // [gridDim.y][gridDim.x][(1+NP)][NM]
 };
 
+// tile `tile` of `n_tiles` of one job: the paths tile, tile + n_tiles, ... in blocks of MCX_BLOCK, moments to partials[tile].
+// kt_lsm and kt_lsm_batch share this body — and with it the order of every sum — so a job gives the same bits through either.
 template <int K>
-__global__ __launch_bounds__(MCX_BLOCK) void kt_lsm(const KTLArgs a)
+__device__ __forceinline__ void kt_lsm_tile(const KTBook& b, const KTEventIds* __restrict__ ev_ids, const int32_t* __restrict__ term_atom,
+                                            const KTLJob& j, int tile, int n_tiles, double* __restrict__ partials)
 {
     constexpr int NM = (2 * K - 1) + K;
     double acc[1 + NP][NM];
@@ -366,12 +384,12 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_lsm(const KTLArgs a)
     for (int q = 0; q <= NP; ++q)
 #pragma unroll
         for (int m = 0; m < NM; ++m) acc[q][m] = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x; i < a.b.n; i += (int64_t)gridDim.x * MCX_BLOCK) {
+    for (int64_t i = (int64_t)tile * MCX_BLOCK + threadIdx.x; i < b.n; i += (int64_t)n_tiles * MCX_BLOCK) {
         DN total = dconst<NP>(0.0);
-        for (int q = a.ev_first; q < a.ev_end; ++q)                                       // controller.py:333-352 without the cache
-            total = total + kt_cash_event(a.b, ldk_struct(&a.b.events[q]), ldk_struct(&a.ev_ids[q]), a.term_atom, i);
-        const DN y = kt_atom(a.b, a.num, a.num_id, i) * total;                             // :368
-        const DN z = (kt_atom(a.b, a.x, a.x_id, i) - a.shift) * a.scale;
+        for (int q = j.ev_first; q < j.ev_end; ++q)                                       // controller.py:333-352 without the cache
+            total = total + kt_cash_event(b, ldk_struct(&b.events[q]), ldk_struct(&ev_ids[q]), term_atom, i);
+        const DN y = kt_atom(b, j.num, j.num_id, i) * total;                               // :368
+        const DN z = (kt_atom(b, j.x, j.x_id, i) - j.shift) * j.scale;
         DN zp = dconst<NP>(1.0);
 #pragma unroll
         for (int k = 0; k < 2 * K - 1; ++k) {
@@ -393,8 +411,24 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_lsm(const KTLArgs a)
 #pragma unroll
         for (int m = 0; m < NM; ++m) {
             const double r = block_sum(acc[q][m], lds);
-            if (threadIdx.x == 0) a.partials[((int64_t)blockIdx.x * (1 + NP) + q) * NM + m] = r;
+            if (threadIdx.x == 0) partials[((int64_t)tile * (1 + NP) + q) * NM + m] = r;
         }
+}
+
+template <int K>
+__global__ __launch_bounds__(MCX_BLOCK) void kt_lsm(const KTLArgs a)
+{
+    kt_lsm_tile<K>(a.b, a.ev_ids, a.term_atom, a.job, (int)blockIdx.x, (int)gridDim.x, a.partials);
+}
+
+// many jobs in one launch: grid (tiles, jobs).  The job is wave-uniform: its record arrives through scalar loads, as the events do.
+template <int K>
+__global__ __launch_bounds__(MCX_BLOCK) void kt_lsm_batch(const KTLBatchArgs a)
+{
+    constexpr int NM = (2 * K - 1) + K;
+    const KTLJob j = ldk_struct(&a.jobs[blockIdx.y]);
+    kt_lsm_tile<K>(a.b, a.ev_ids, a.term_atom, j, (int)blockIdx.x, (int)gridDim.x,
+                   a.partials + (int64_t)blockIdx.y * gridDim.x * ((1 + NP) * NM));
 }
 
 __global__ void kt_sum_partials(const double* __restrict__ partials, int count, int n_blocks, double* __restrict__ out)
@@ -404,6 +438,19 @@ __global__ void kt_sum_partials(const double* __restrict__ partials, int count, 
     double s = 0.0;
     for (int b = 0; b < n_blocks; ++b) s += partials[(int64_t)b * count + j];
     out[j] = s;
+}
+
+// kt_sum_partials for partials [n_jobs][n_tiles][count] -> out [n_jobs][count]: every (job, entry) adds its tiles in ascending order
+__global__ void kt_sum_partials_batch(const double* __restrict__ partials, int count, int n_tiles, int64_t total, double* __restrict__ out)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const int64_t job = t / count;
+    const int e = (int)(t - job * count);
+    const double* __restrict__ p = partials + job * n_tiles * count + e;
+    double s = 0.0;
+    for (int b = 0; b < n_tiles; ++b) s += p[(int64_t)b * count];
+    out[t] = s;
 }
 
 // ---- book evaluation with tangents ----------------------------------------------------------------------------------------
@@ -660,17 +707,65 @@ int fill_book(mcx_handle* h, const mcx_book* b, const double* d_datoms, const do
 }
 
 // ids of the atoms behind every event / term (the flattened device records hold copies, the derivative rows are per atom id)
+struct HostIds { std::vector<KTEventIds> ids; std::vector<int32_t> ta; };
+// enqueues the uploads: `host` stays alive until the stream has been synchronised
+int upload_ids_async(mcx_handle* h, const mcx_book* b, HostIds& host, DevBuf& ev_ids, DevBuf& term_atom, hipStream_t s)
+{
+    host.ids.resize((size_t)b->n_events);
+    for (int q = 0; q < b->n_events; ++q) { host.ids[q].num = b->h_event_num_atom[q]; host.ids[q].x = b->h_event_x_atom[q]; }
+    host.ta.resize((size_t)b->n_terms);
+    for (int j = 0; j < b->n_terms; ++j) host.ta[j] = b->h_term_atom[j];
+    MCX_HIP(h, ev_ids.upload(host.ids.data(), sizeof(KTEventIds) * host.ids.size(), s));
+    MCX_HIP(h, term_atom.upload(host.ta.data(), sizeof(int32_t) * host.ta.size(), s));
+    return 0;
+}
 int upload_ids(mcx_handle* h, const mcx_book* b, DevBuf& ev_ids, DevBuf& term_atom, hipStream_t s)
 {
-    std::vector<KTEventIds> ids((size_t)b->n_events);
-    for (int q = 0; q < b->n_events; ++q) { ids[q].num = b->h_event_num_atom[q]; ids[q].x = b->h_event_x_atom[q]; }
-    std::vector<int32_t> ta((size_t)b->n_terms);
-    for (int j = 0; j < b->n_terms; ++j) ta[j] = b->h_term_atom[j];
-    MCX_HIP(h, ev_ids.upload(ids.data(), sizeof(KTEventIds) * ids.size(), s));
-    MCX_HIP(h, term_atom.upload(ta.data(), sizeof(int32_t) * ta.size(), s));
+    HostIds host;
+    if (int rc = upload_ids_async(h, b, host, ev_ids, term_atom, s)) return rc;
     MCX_HIP(h, hipStreamSynchronize(s));
     return 0;
 }
+
+// what mcx_tangent_lsm and mcx_tangent_lsm_batch check of one (product, regression date) before anything is enqueued; fills the
+// device record of the job
+int ktl_check_job(mcx_handle* h, const mcx_book* b, int32_t product, int32_t first_event, int32_t num_atom, int32_t x_atom, double shift,
+                  double scale, const char* who, KTLJob* out)
+{
+    if (product < 0 || product >= b->n_products) MCX_FAIL(h, -2, "%s: product out of range", who);
+    const DevProduct& pr = b->h_products[product];
+    if (pr.n_states != 1) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: stateless products only", who);
+    const int n_cf = pr.cf_end - pr.cf_begin;
+    if (first_event < 0 || first_event > n_cf) MCX_FAIL(h, -2, "%s: first_event out of range", who);
+    for (int q = pr.cf_begin; q < pr.cf_end; ++q) {
+        const DevEvent& e = b->h_events[q];
+        if (!(e.kind == MCX_EV_CASHFLOW || (e.kind == MCX_EV_OPTION && e.aux[0] == 0.0)))
+            MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: event %d (kind %d, mode %g) has no tangent form", who, q, e.kind, e.aux[0]);
+        if (e.kind == MCX_EV_OPTION)
+            for (int j = e.term_begin; j < e.term_end; ++j)
+                if (b->h_terms[j].den >= 0) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: option over per-term denominators", who);
+    }
+    if (num_atom < 0 || num_atom >= b->n_atoms || x_atom < 0 || x_atom >= b->n_atoms) MCX_FAIL(h, -2, "%s: atom out of range", who);
+    memset(out, 0, sizeof(*out));
+    out->num = mcx_flat_atom(b->h_atoms[num_atom]); out->x = mcx_flat_atom(b->h_atoms[x_atom]); out->num_id = num_atom; out->x_id = x_atom;
+    out->shift = shift; out->scale = scale; out->ev_first = pr.cf_begin + first_event; out->ev_end = pr.cf_end;
+    return 0;
+}
+
+// upper bound (bytes) of the partial sums of one kt_lsm_batch launch: the handle's workspace, or less where
+// MCX_TANGENT_BATCH_PARTIAL_BYTES says so (include/mcx.h; unset or unparsable: the workspace).  A launch always takes at least one job.
+size_t ktl_partial_cap(const mcx_handle* h)
+{
+    size_t cap = h->ws_bytes;
+    const char* e = getenv("MCX_TANGENT_BATCH_PARTIAL_BYTES");
+    if (e && *e) {
+        char* end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        if (end != e && *end == 0 && v > 0 && (size_t)v < cap) cap = (size_t)v;
+    }
+    return cap;
+}
+constexpr int KTL_MAX_LAUNCH_JOBS = 32768;     // gridDim.y
 
 }  // namespace
 
@@ -718,20 +813,9 @@ extern "C" int mcx_tangent_lsm(mcx_handle* h, const mcx_book* b, int32_t product
                                int64_t n_paths, int64_t ld, int32_t n_dates, double* h_moments, void* stream)
 {
     if (!h || !b || !d_datoms || !d_paths || !d_dpaths || !h_moments) return -1;
-    if (product < 0 || product >= b->n_products) MCX_FAIL(h, -2, "mcx_tangent_lsm: product out of range");
-    const DevProduct& pr = b->h_products[product];
-    if (pr.n_states != 1) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_lsm: stateless products only");
-    const int n_cf = pr.cf_end - pr.cf_begin;
-    if (first_event < 0 || first_event > n_cf) MCX_FAIL(h, -2, "mcx_tangent_lsm: first_event out of range");
-    for (int q = pr.cf_begin; q < pr.cf_end; ++q) {
-        const DevEvent& e = b->h_events[q];
-        if (!(e.kind == MCX_EV_CASHFLOW || (e.kind == MCX_EV_OPTION && e.aux[0] == 0.0)))
-            MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_lsm: event %d (kind %d, mode %g) has no tangent form", q, e.kind, e.aux[0]);
-        if (e.kind == MCX_EV_OPTION)
-            for (int j = e.term_begin; j < e.term_end; ++j)
-                if (b->h_terms[j].den >= 0) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_lsm: option over per-term denominators");
-    }
-    if (num_atom < 0 || num_atom >= b->n_atoms || x_atom < 0 || x_atom >= b->n_atoms) MCX_FAIL(h, -2, "mcx_tangent_lsm: atom out of range");
+    KTLArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = ktl_check_job(h, b, product, first_event, num_atom, x_atom, shift, scale, "mcx_tangent_lsm", &a.job)) return rc;
     const int K = b->n_basis, NM = (2 * K - 1) + K;
     if (n_paths <= 0) { memset(h_moments, 0, sizeof(double) * (size_t)(1 + NP) * NM); return 0; }
     hipStream_t s = (hipStream_t)stream;
@@ -741,12 +825,9 @@ extern "C" int mcx_tangent_lsm(mcx_handle* h, const mcx_book* b, int32_t product
     const int count = (1 + NP) * NM;
     if ((size_t)(grid + 1) * count * sizeof(double) > h->ws_bytes || (size_t)count * sizeof(double) > h->pinned_bytes)
         MCX_FAIL(h, -2, "mcx_tangent_lsm: workspace too small");
-    KTLArgs a;
-    memset(&a, 0, sizeof(a));
     fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b);
     a.ev_ids = (const KTEventIds*)ev_ids.p; a.term_atom = (const int32_t*)term_atom.p;
-    a.num = mcx_flat_atom(b->h_atoms[num_atom]); a.x = mcx_flat_atom(b->h_atoms[x_atom]); a.num_id = num_atom; a.x_id = x_atom; a.shift = shift; a.scale = scale;
-    a.partials = h->d_ws; a.ev_first = pr.cf_begin + first_event; a.ev_end = pr.cf_end;
+    a.partials = h->d_ws;
     switch (K) {
     case 1: hipLaunchKernelGGL((kt_lsm<1>), dim3(grid), dim3(MCX_BLOCK), 0, s, a); break;
     case 2: hipLaunchKernelGGL((kt_lsm<2>), dim3(grid), dim3(MCX_BLOCK), 0, s, a); break;
@@ -761,6 +842,68 @@ extern "C" int mcx_tangent_lsm(mcx_handle* h, const mcx_book* b, int32_t product
     MCX_HIP(h, hipMemcpyAsync(h->h_pinned, d_out, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, s));
     MCX_HIP(h, hipStreamSynchronize(s));
     memcpy(h_moments, h->h_pinned, sizeof(double) * (size_t)count);
+    return 0;
+}
+
+// every job of the table in launches of grid (tiles, jobs): the id tables, the job table and the result block exist once per call;
+// partials [job][tile][1+NP][NM] in the workspace, as many whole jobs per launch as fit; ONE synchronisation, at the end
+extern "C" int mcx_tangent_lsm_batch(mcx_handle* h, const mcx_book* b, const mcx_tangent_lsm_job* h_jobs, int32_t n_jobs,
+                                     const double* d_datoms, const double* d_paths, const double* d_dpaths, int64_t n_paths, int64_t ld,
+                                     int32_t n_dates, double* h_moments, void* stream)
+{
+    if (!h || !b || n_jobs < 0) return -1;
+    if (n_jobs == 0) return 0;
+    if (!h_jobs || !d_datoms || !d_paths || !d_dpaths || !h_moments) return -1;
+    if (ld < n_paths) MCX_FAIL(h, -2, "mcx_tangent_lsm_batch: ld < n_paths");
+    const int K = b->n_basis, NM = (2 * K - 1) + K, count = (1 + NP) * NM;
+    std::vector<KTLJob> jobs((size_t)n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+        const mcx_tangent_lsm_job& q = h_jobs[j];
+        if (int rc = ktl_check_job(h, b, q.product, q.first_event, q.num_atom, q.x_atom, q.shift, q.scale, "mcx_tangent_lsm_batch", &jobs[j])) {
+            h->err = "job " + std::to_string(j) + ": " + h->err;
+            return rc;
+        }
+    }
+    if (K < 1 || K > 4) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_lsm_batch: basis size %d has no instantiation", K);
+    const size_t out_bytes = sizeof(double) * (size_t)n_jobs * count;
+    if (n_paths <= 0) { memset(h_moments, 0, out_bytes); return 0; }
+    const int tiles = mcx_grid_for(n_paths, MCX_BLOCK, 2 * h->n_cu);       // of every job, whatever the split (mcx_tangent_lsm's)
+    const size_t job_bytes = sizeof(double) * (size_t)tiles * count;
+    if (job_bytes > h->ws_bytes) MCX_FAIL(h, -2, "mcx_tangent_lsm_batch: workspace too small");
+    size_t per_launch = ktl_partial_cap(h) / job_bytes;
+    if (per_launch < 1) per_launch = 1;
+    if (per_launch > (size_t)KTL_MAX_LAUNCH_JOBS) per_launch = KTL_MAX_LAUNCH_JOBS;
+    hipStream_t s = (hipStream_t)stream;
+    HostIds host_ids;
+    DevBuf ev_ids, term_atom, d_jobs, d_out;
+    if (int rc = upload_ids_async(h, b, host_ids, ev_ids, term_atom, s)) return rc;
+    MCX_HIP(h, d_jobs.upload(jobs.data(), sizeof(KTLJob) * jobs.size(), s));
+    MCX_HIP(h, hipMalloc(&d_out.p, out_bytes));
+    KTLBatchArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b);
+    a.ev_ids = (const KTEventIds*)ev_ids.p; a.term_atom = (const int32_t*)term_atom.p; a.partials = h->d_ws;
+    hipError_t err = hipSuccess;
+    for (size_t j0 = 0; j0 < (size_t)n_jobs && err == hipSuccess; j0 += per_launch) {
+        const size_t nj = std::min(per_launch, (size_t)n_jobs - j0);
+        a.jobs = (const KTLJob*)d_jobs.p + j0;
+        const dim3 grid((unsigned)tiles, (unsigned)nj);
+        switch (K) {
+        case 1: hipLaunchKernelGGL((kt_lsm_batch<1>), grid, dim3(MCX_BLOCK), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((kt_lsm_batch<2>), grid, dim3(MCX_BLOCK), 0, s, a); break;
+        case 3: hipLaunchKernelGGL((kt_lsm_batch<3>), grid, dim3(MCX_BLOCK), 0, s, a); break;
+        default: hipLaunchKernelGGL((kt_lsm_batch<4>), grid, dim3(MCX_BLOCK), 0, s, a); break;
+        }
+        const int64_t total = (int64_t)nj * count;
+        hipLaunchKernelGGL(kt_sum_partials_batch, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h->d_ws, count, tiles, total,
+                           (double*)d_out.p + j0 * count);
+        err = hipGetLastError();
+    }
+    // the stream is drained before the scoped buffers go, also after a failed launch; h_moments is written by the one copy only
+    if (err == hipSuccess) err = hipMemcpyAsync(h_moments, d_out.p, out_bytes, hipMemcpyDeviceToHost, s);
+    const hipError_t sync = hipStreamSynchronize(s);
+    MCX_HIP(h, err);
+    MCX_HIP(h, sync);
     return 0;
 }
 

@@ -109,6 +109,10 @@ LSM_SOLVE_JOB_DTYPE = np.dtype([("shift", np.float64), ("scale", np.float64), ("
 assert LSM_SOLVE_JOB_DTYPE.itemsize == 48
 
 TANGENT_NP = 4          # MCX_TANGENT_NP: model parameters per forward-mode pass (csrc/kt_book.hip)
+# mcx_tangent_lsm_job: one (stateless product, regression date) pair of mcx_tangent_lsm_batch
+TANGENT_LSM_JOB_DTYPE = np.dtype([("product", "<i4"), ("first_event", "<i4"), ("num_atom", "<i4"), ("x_atom", "<i4"),
+                                  ("shift", "<f8"), ("scale", "<f8")])
+assert TANGENT_LSM_JOB_DTYPE.itemsize == 32
 
 # gas storage (include/mcx.h "K6"): mcx_storage_date, mcx_storage_desc, mcx_storage_lsm_date, mcx_storage_op
 STORAGE_DATE_DTYPE = np.dtype([("vmin", "<f8"), ("step", "<f8"), ("next_vmin", "<f8"), ("next_vmax", "<f8"), ("next_scale", "<f8"),

@@ -23,7 +23,7 @@ _EXPORTS = [
     "mcx_comm_unique_id", "mcx_comm_init", "mcx_comm_destroy", "mcx_allreduce_f64", "mcx_allgather_f64",
     "mcx_book_create", "mcx_book_destroy", "mcx_book_set_coeffs", "mcx_eval_book", "mcx_eval_book_describe", "mcx_resolve_atoms",
     "mcx_lsm_stats", "mcx_lsm_step", "mcx_lsm_run", "mcx_lsm_solve", "mcx_lsm_step_batch", "mcx_lsm_step_batch_dev", "mcx_lsm_solve_batch", "mcx_lsm_run_batch", "mcx_book_get_coeffs", "mcx_book_set_coeffs_batch", "mcx_book_set_bridge_rng", "mcx_book_set_exercise_replay",
-    "mcx_fused_is_straight_line", "mcx_tangent_paths", "mcx_tangent_lsm", "mcx_tangent_lsm_step", "mcx_tangent_eval", "mcx_tangent_cva", "mcx_tangent_profiles", "mcx_tangent_pick",
+    "mcx_fused_is_straight_line", "mcx_tangent_paths", "mcx_tangent_lsm", "mcx_tangent_lsm_batch", "mcx_tangent_lsm_step", "mcx_tangent_eval", "mcx_tangent_cva", "mcx_tangent_profiles", "mcx_tangent_pick",
     "mcx_box_muller", "mcx_tangent_european", "mcx_fused_create", "mcx_fused_destroy", "mcx_fused_num_records", "mcx_fused_run", "mcx_fused_eval_paths", "mcx_fused_run_device", "mcx_fused_eval_paths_device", "mcx_fused_set_timing", "mcx_fused_kernel_times", "mcx_fused_describe",
     "mcx_value_poly_fit", "mcx_book_collapse_values", "mcx_book_value_poly_info", "mcx_rows_minmax",
     "mcx_storage_create", "mcx_storage_destroy", "mcx_storage_lsm_step", "mcx_storage_lsm_run", "mcx_storage_eval",
@@ -67,6 +67,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_storage_lsm_run_batch.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i64, i64, vp, i64, i64, vp, vp, i32, vp]
     lib.mcx_tangent_storage_lsm_step.argtypes = [vp, vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp, i32, vp]
     lib.mcx_tangent_storage_eval.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i64, vp]
+    lib.mcx_tangent_lsm_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, i64, i64, i32, vp, vp]
     lib.mcx_tangent_paths_s2f.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_fused_num_records.argtypes = [C.c_void_p]
     lib.mcx_fused_is_straight_line.argtypes = [C.c_void_p]
@@ -422,14 +423,36 @@ class HipBackend:
         return paths, dpaths
 
     def tangent_lsm(self, book, product: int, first_event: int, num_atom: int, x_atom: int, shift: float, scale: float,
-                    datoms: torch.Tensor, paths: torch.Tensor, dpaths: torch.Tensor) -> np.ndarray:
+                    datoms: torch.Tensor, paths: torch.Tensor, dpaths: torch.Tensor, n_paths: int | None = None) -> np.ndarray:
+        """n_paths: the paths of the [T][D][ld] tensors that count (default: all ld of them)"""
         K = book.plan.n_basis
         out = np.zeros((1 + _abi.TANGENT_NP, (2 * K - 1) + K))
-        n = paths.shape[2]
+        ld = paths.shape[2]
+        n = ld if n_paths is None else int(n_paths)
+        assert paths.is_contiguous() and dpaths.is_contiguous() and dpaths.shape == (_abi.TANGENT_NP,) + tuple(paths.shape) and n <= ld
         self._check(self.lib.mcx_tangent_lsm(
             self.h, book.ptr, C.c_int32(product), C.c_int32(first_event), C.c_int32(num_atom), C.c_int32(x_atom),
             C.c_double(shift), C.c_double(scale), _vp(datoms.data_ptr()), _vp(paths.data_ptr()), _vp(dpaths.data_ptr()),
-            C.c_int64(n), C.c_int64(n), C.c_int32(paths.shape[0]), _abi.ptr(out), self._stream()), "mcx_tangent_lsm")
+            C.c_int64(n), C.c_int64(ld), C.c_int32(paths.shape[0]), _abi.ptr(out), self._stream()), "mcx_tangent_lsm")
+        return out
+
+    def tangent_lsm_batch(self, book, jobs: np.ndarray, datoms: torch.Tensor, paths: torch.Tensor, dpaths: torch.Tensor,
+                          n_paths: int | None = None, out: np.ndarray | None = None) -> np.ndarray:
+        """tangent_lsm for a table of jobs (_abi.TANGENT_LSM_JOB_DTYPE) in one library call (mcx_tangent_lsm_batch): moments
+        [n_jobs][1+NP][(2K-1)+K], job j bit for bit what tangent_lsm returns for it.  out: filled in place when given (a failed
+        call leaves it as it was)"""
+        K = book.plan.n_basis
+        jobs = np.ascontiguousarray(jobs, dtype=_abi.TANGENT_LSM_JOB_DTYPE)
+        shape = (len(jobs), 1 + _abi.TANGENT_NP, (2 * K - 1) + K)
+        if out is None:
+            out = np.zeros(shape)
+        ld = paths.shape[2]
+        n = ld if n_paths is None else int(n_paths)
+        assert out.shape == shape and out.dtype == np.float64 and out.flags.c_contiguous
+        assert paths.is_contiguous() and dpaths.is_contiguous() and dpaths.shape == (_abi.TANGENT_NP,) + tuple(paths.shape) and n <= ld
+        self._check(self.lib.mcx_tangent_lsm_batch(
+            self.h, book.ptr, _abi.ptr(jobs), C.c_int32(len(jobs)), _vp(datoms.data_ptr()), _vp(paths.data_ptr()), _vp(dpaths.data_ptr()),
+            C.c_int64(n), C.c_int64(ld), C.c_int32(paths.shape[0]), _abi.ptr(out), self._stream()), "mcx_tangent_lsm_batch")
         return out
 
     def tangent_lsm_step(self, book, product: int, roll_begin: int, roll_end: int, num_atom: int, x_atom: int, shift: float,

@@ -294,6 +294,50 @@ def _solve_dual_states(mom: np.ndarray, K: int, S: int, shift: float, scale: flo
     return c, dc
 
 
+def _regression_centering(x_range, x):
+    """(shift, scale, degenerate) of the explanatory atom x: z = (x - shift) * scale maps its range over all ranks to [-1, 1]"""
+    xmin, xmax = x_range[x]
+    degenerate = not (xmax > xmin)
+    shift = 0.5 * (xmin + xmax) if not degenerate else xmin
+    scale = 2.0 / (xmax - xmin) if not degenerate else 1.0
+    return shift, scale, degenerate
+
+
+def stateless_lsm_jobs(plan, x_range, expo_coeff_base, K: int):
+    """the (product, regression date) pairs of the products WITHOUT exercise states of one forward-mode pass, in the order the
+    per-job loop of run_with_tangent_book visits them.  plan: [(product index, product, regression schedule, [(num atom, x atom)])];
+    x_range: {x atom: (min, max)}.  Returns the job table (_abi.TANGENT_LSM_JOB_DTYPE: what mcx_tangent_lsm takes per job) and,
+    per job, (offset of its K coefficients, degenerate) for _solve_dual.  Products with states (exercise rights, storages) are
+    skipped: their backward induction is sequential per product.  Pure host arithmetic."""
+    rows, keep = [], []
+    for p_i, p, sched, atoms in plan:
+        if p.get_num_states() > 1:
+            continue
+        pdates = np.asarray([float(t) for t in p.product_timeline])
+        for (t_reg, _r0, _r1, _prod_idx, expo_idx), (num, x) in zip(sched, atoms):
+            if expo_idx is None:
+                continue
+            shift, scale, degenerate = _regression_centering(x_range, x)
+            first = int(np.searchsorted(pdates, t_reg, side="right"))      # cashflows strictly after t_reg (controller.py:323)
+            rows.append((p_i, first, num, x, shift, scale))
+            keep.append((expo_coeff_base[p_i] + expo_idx * K, degenerate))
+    return np.array(rows, dtype=_abi.TANGENT_LSM_JOB_DTYPE), keep
+
+
+def _batch_tangent_lsm(sc) -> bool:
+    """which route the regression of the stateless products takes (SimulationController.batch_tangent_lsm): one
+    mcx_tangent_lsm_batch call per parameter chunk, or one mcx_tangent_lsm call per (product, date)"""
+    flag = getattr(sc, "batch_tangent_lsm", None)
+    if flag is False:
+        return False
+    able = hasattr(sc.backend, "tangent_lsm_batch")
+    if flag is None and len(sc.products) <= 64:
+        return False
+    if not able:            # the per-job route stops at 64 products: ~3 synchronous round trips per (product, date, chunk)
+        raise _NoTangentForm("products")
+    return True
+
+
 def run_with_tangent_book(sc):
     """d PV / d theta and d CVA / d theta in forward mode through pre-simulation, regression and main simulation."""
     import copy
@@ -310,8 +354,7 @@ def run_with_tangent_book(sc):
     if any(m.metric_type not in (MetricType.PV, MetricType.CVA, MetricType.EPE, MetricType.ENE, MetricType.CE, MetricType.EEPE,
                                  MetricType.PFE) or not m._native for m in rm.metrics):
         raise _NoTangentForm("metric")
-    if len(sc.products) > 64:
-        raise _NoTangentForm("products")
+    batched = _batch_tangent_lsm(sc)
     if any(p.get_num_states() > 1 for p in sc.products) and not hasattr(sc.backend, "tangent_lsm_step"):
         raise _NoTangentForm("exercise products")
     if any(sc._can_skip_monte_carlo_for_product(p) for p in sc.products):
@@ -389,6 +432,7 @@ def run_with_tangent_book(sc):
 
     storages = getattr(base, "_storage_meta", {})
     lsm_flags = _abi.LSM_F32_CACHE if base.reference_float32_cf_cache else 0
+    n_batched = 0
 
     for c0 in range(0, P, NP):
         sel = list(range(c0, min(c0 + NP, P)))
@@ -461,6 +505,8 @@ def run_with_tangent_book(sc):
                         dcoeffs[o:o + S * K] = dc.reshape(NP, S * K).T
                     del W, dW
                     continue
+                if batched:
+                    continue
                 pdates = np.asarray([float(t) for t in p.product_timeline])
                 for (t_reg, _r0, _r1, _prod_idx, expo_idx), (num, x) in zip(sched, atoms):
                     if expo_idx is None:
@@ -474,6 +520,16 @@ def run_with_tangent_book(sc):
                     c, dc = _solve_dual(mom, K, shift, scale, degenerate, NP)
                     o = base._expo_coeff_base[p_i] + expo_idx * K
                     coeffs[o:o + K], dcoeffs[o:o + K] = c, dc.T
+            if batched:
+                # the stateless products' (product, date) pairs: one library call and one collective for the whole moment block;
+                # their coefficient slots are disjoint from those of the products with states, which the loop above has served
+                table, keep = stateless_lsm_jobs(plan, x_range, base._expo_coeff_base, K)
+                if len(table):
+                    moments = shard.all_reduce_np(be.tangent_lsm_batch(book, table, datoms, paths_pre, dpaths_pre))
+                    for job, mom, (o, degenerate) in zip(table, moments, keep):
+                        c, dc = _solve_dual(mom, K, float(job["shift"]), float(job["scale"]), degenerate, NP)
+                        coeffs[o:o + K], dcoeffs[o:o + K] = c, dc.T
+                    n_batched += len(table)
             del paths_pre, dpaths_pre
         be.synchronize()
         t2 = time.perf_counter()
@@ -539,7 +595,8 @@ def run_with_tangent_book(sc):
         t_main += time.perf_counter() - t2
     sc.sim_plan, sc.last_state = base.sim_plan, base.last_state
     sc.timings = dict(total=time.perf_counter() - t0, tangent=True, forward_mode_passes=(P + NP - 1) // NP,
-                      base_run_and_descriptor_derivatives=t_desc, presim_and_regression=t_pre, main=t_main)
+                      base_run_and_descriptor_derivatives=t_desc, presim_and_regression=t_pre, main=t_main,
+                      batched_lsm_jobs=n_batched)
     g = [[[tuple(ev) for ev in grads[ns_i][m_i]] for m_i in range(n_metrics)] for ns_i in range(n_ns)]
     return sc._package([[[tuple(v) for v in evals] for evals in per_metric] for per_metric in res0.results], g, [])
 

@@ -161,6 +161,10 @@ class SimulationController:
         self.materialize = False     # also write paths / cashflows / exposures in the fused pass (inspection, tests)
         self.batch_lsm = True        # product-batched LSM pre-simulation (one launch per backward step of the whole book)
         self.batch_storage_lsm = True        # the same for gas storages: two or more of them share the launches of a step
+        # differentiate=True, regression of the products without exercise states in forward mode: None = one mcx_tangent_lsm_batch
+        # call per parameter chunk for a book of more than 64 products, one mcx_tangent_lsm call per (product, date) below;
+        # True / False = the batched / the per-job route at any size (mcx/aad.py run_with_tangent_book)
+        self.batch_tangent_lsm = None
         self.storage_lsm_route = None        # "batch" / "single": the route the last storage pre-simulation took
         self.forward_mode = True     # differentiate=True: dual-number pass where it exists, bump-and-revalue otherwise
         # The reference compiles nothing: every run_simulation() sees the current state of its products / metrics.  Re-using the
