@@ -370,6 +370,7 @@ struct mcx_fused {
     int chunk_cap, npf, max_chunk;      // max_chunk: bytes of the largest interpreted chunk (0: none)
     int lean;                  // every date has a FastDate record kf_lean.hip can run (valid != 0)
     FastDateCva* d_cva;        // [n_dates] when every date runs in the cva-date kernel of kf_lean.hip, else nullptr
+    int cva_steps;             // (d_cva) sub-steps up to and including the last one that stores a date with a CVA increment
     LeanTerm* d_lterms;
     double* d_vcoef;           // this object's copy of the exercise-value polynomial coefficients (the book may rebuild its own)
     int32_t rec_pv[MCX_FUSED_MAX_NS], rec_cva[MCX_FUSED_MAX_NS];
@@ -723,6 +724,15 @@ extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_boo
             cva_only = false;          // a threshold, an EPE / ENE record or an exercise: the general program
         }
     }
+    // The dates after the last CVA increment are all-zero records: each adds +0.0 to the CVA, so the cva-date kernel need not
+    // simulate up to them.  cva_steps is the index just past the last sub-step that stores a date with an increment.
+    int cva_steps = 0;
+    for (size_t k = 0; k < sim->h_steps.size() && cva_only; ++k) {
+        const int st = sim->h_steps[k].store_idx;
+        if (st >= 0 && st < T && (fast[st].flags & (64 | 128 | 256)) == 64) cva_steps = (int)k + 1;
+    }
+    // (a book without any increment: nothing to stop at, the whole table like every other kernel)
+    f->cva_steps = cva_steps > 0 ? cva_steps : (int)sim->h_steps.size();
     // LDS budget: 4 wave slots + the record area (dynamic) must fit comfortably; with kf_fused's static tables (Box-Muller 4 KiB,
     // exponential 1 KiB) a block holds at most 65 KiB of the CU's 160 KiB
     if ((size_t)4 * f->chunk_cap + sizeof(double) * 9 * (size_t)n_rec > 60 * 1024) {
@@ -797,6 +807,7 @@ static int fused_run_impl(mcx_handle* h, const mcx_fused* f, bool simulate, uint
     mcx_fill_k1_args(f->sim, seed, path_offset, n_paths, ld > 0 ? ld : n_paths, d_paths, d_inject_z, d_inject_u, &a.k1);
     // the cva-date kernel computes the CVA records alone: no stored paths, cashflows or exposures
     a.cva_dates = (simulate && !d_inject_z && !d_paths && !d_cfs && !d_expo) ? f->d_cva : nullptr;
+    if (a.cva_dates) a.k1.n_steps = f->cva_steps;      // (mcx_launch_kf_lean restores the full count for any other kernel)
     a.prog = f->d_prog; a.fast = f->d_fast; a.lterms = f->d_lterms; a.vcoef = f->d_vcoef; a.date_off = f->d_date_off; a.chunk_cap = f->chunk_cap;
     a.date_row = f->d_date_row; a.coeffs = f->book->d_coeffs; a.cfs = d_cfs; a.expo = d_expo; a.partials = f->d_partials;
     a.ld_out = ld_out; a.n_dates = f->n_dates; a.n_basis = f->book->n_basis; a.n_ns = f->n_ns; a.n_rec = f->n_rec;

@@ -58,14 +58,164 @@ __device__ __forceinline__ void lean_date_cva(const FastDateCvaLds* __restrict__
     }
 }
 
+// ---- the draws of the cva-date instantiation (DK = 1) ---------------------------------------------------------------------------
+// draw_pairs_staged (mcx_device.h) for a launch whose grid is the kernel's whole residency and whose paths share ONE high word of the path index
+// (launch_lean_shape checks both) and whose sub-step is the same for every path of the lane: the same bits, less vector work.
+// The stages are written as there, but the backend does not keep them: the results of stage C are dead where the rare-draw
+// branch is taken, so it sinks the stage behind that branch and waits for the table reads after a few of its instructions.
+// Measured at four waves per SIMD, that order is faster than the staged one; thin launches, which the
+// staging is for, run DK = 2.
+//   * Philox: the counter is (path_lo, path_hi, step, draw) and only path_lo differs between lanes, so all of round 1 but
+//     M0 * path_lo, the product M0 * (hi(M1 step) ^ path_hi ^ k0) of round 2 and the key folds of rounds 2 and 3 are wave-uniform:
+//     written on scalars, they run on the SALU (a VOP3 reads one SGPR: two scalars are xor-ed before they meet a vector);
+//   * the second uniform's remainder from integers, see cva_draw_pairs;
+//   * one rare-draw test per lane.
+template <int PPL>
+__device__ __forceinline__ void philox4x32_10_cva(const uint32_t (&path_lo)[PPL], uint32_t path_hi, uint32_t step, uint32_t draw, uint64_t seed,
+                                                  uint32_t (&o0)[PPL], uint32_t (&o1)[PPL], uint32_t (&o2)[PPL], uint32_t (&o3)[PPL])
+{
+    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    uint32_t c0[PPL], c1[PPL], c2[PPL], c3[PPL];
+    // round 1: c0 and c1 come out scalar, c2 and c3 per lane
+    const uint64_t s1 = (uint64_t)M1 * step;
+    const uint32_t hk = path_hi ^ k0;
+    const uint32_t a0 = (uint32_t)(s1 >> 32) ^ hk, a1 = (uint32_t)s1;
+    const uint32_t dk = draw ^ k1;
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) {
+        const uint64_t p0 = (uint64_t)M0 * path_lo[q];
+        c2[q] = (uint32_t)(p0 >> 32) ^ dk;
+        c3[q] = (uint32_t)p0;
+    }
+    k0 += W0; k1 += W1;
+    // round 2: M0 * c0 is a scalar product and c3 comes out scalar; the round keys are folded into the per-lane words, which do
+    // not depend on the sub-step (the keys then need no register of their own inside a run of sub-steps)
+    const uint64_t s0 = (uint64_t)M0 * a0;
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) {
+        const uint64_t p1 = (uint64_t)M1 * c2[q];
+        c0[q] = ((uint32_t)(p1 >> 32) ^ k0) ^ a1;
+        c2[q] = (c3[q] ^ k1) ^ (uint32_t)(s0 >> 32);
+        c1[q] = (uint32_t)p1;
+    }
+    k0 += W0; k1 += W1;
+    // round 3: the last scalar word (c3) and its key
+    const uint32_t x3 = (uint32_t)s0 ^ k1;
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) {
+        const uint64_t p0 = (uint64_t)M0 * c0[q];
+        const uint64_t p1 = (uint64_t)M1 * c2[q];
+        c0[q] = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1[q], k0, 0x96);
+        c2[q] = (uint32_t)(p0 >> 32) ^ x3;
+        c1[q] = (uint32_t)p1; c3[q] = (uint32_t)p0;
+    }
+    k0 += W0; k1 += W1;
+#pragma unroll
+    for (int r = 3; r < 10; ++r) {                                      // rounds 4-10: philox4x32_10_n
+#pragma unroll
+        for (int q = 0; q < PPL; ++q) {
+            const uint64_t p0 = (uint64_t)M0 * c0[q];
+            const uint64_t p1 = (uint64_t)M1 * c2[q];
+            const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1[q], k0, 0x96);
+            const uint32_t n2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3[q], k1, 0x96);
+            c1[q] = (uint32_t)p1; c3[q] = (uint32_t)p0; c0[q] = n0; c2[q] = n2;
+        }
+        k0 += W0; k1 += W1;
+    }
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) { o0[q] = c0[q]; o1[q] = c1[q]; o2[q] = c2[q]; o3[q] = c3[q]; }
+}
+
+// Constants of the integer-built remainder, kept in VGPRs across a run of sub-steps like the additive ones of mcx_bm_vconst
+// (mcx_math.h): the kernel has vector registers to spare and none of the scalar ones
+struct CvaDrawConst {
+    double off52;          // 2^52 - 1/2
+    double trig_scale;     // 2 pi 2^-53
+};
+__device__ __forceinline__ CvaDrawConst cva_draw_const_make()
+{
+    CvaDrawConst c;
+    c.off52 = mcx_opaque_v(0x1.0p52 - 0.5); c.trig_scale = mcx_opaque_v(6.28318530717958647692 * 0x1.0p-53);
+    return c;
+}
+
+// The second uniform's remainder ur = (n' + 1/2) 2^-53, n' = (w3 & mask) 2^21 + (w2 >> 11) < 2^(53 - BMB), enters the angle only as
+// d = fma(ur, 2 pi, trig_off).  The words (0x43300000 | n' >> 32, n' & 0xffffffff) are the double 2^52 + n'; subtracting 2^52 - 1/2 is
+// exact (n' + 1/2 has at most 54 - BMB bits), and (n' + 1/2) (2 pi 2^-53) is the same real product as ur (2 pi): one rounding in the
+// fma, the same d.  Three integer operations and an addition replace a shift, two conversions and two fmas.
+template <int PPL, int BMB>
+__device__ __forceinline__ bool cva_draw_pairs(uint64_t seed, const uint32_t (&path_lo)[PPL], uint32_t path_hi, uint32_t step, uint32_t draw,
+                                               double (&z0)[PPL], double (&z1)[PPL], const double* __restrict__ tab,
+                                               const mcx_bm_coef& C, const mcx_bm_vconst& vc, const CvaDrawConst& dc)
+{
+    static_assert(BMB >= 1 && BMB <= 20, "the funnel shift of the high word is by 11 + BMB < 32 bits");
+    constexpr int N = 1 << BMB, LOG_TERMS = mcx_bm_shape<BMB>::LOG_TERMS;
+    uint32_t w0[PPL], w1[PPL], w2[PPL], w3[PPL];
+    philox4x32_10_cva<PPL>(path_lo, path_hi, step, draw, seed, w0, w1, w2, w3);
+    double m[PPL], ed[PPL], ps[PPL], pc[PPL];
+    int e[PPL];
+    mcx_d2 tc[PPL], sc[PPL];
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) {                                     // (B) cells and table reads
+        const double ua = u53(w0[q], w1[q], &vc);
+        m[q] = __builtin_amdgcn_frexp_mant(ua);
+        e[q] = __builtin_amdgcn_frexp_exp(ua);
+        const int jl = (__double2hiint(m[q]) >> (20 - BMB)) & (N - 1);
+        tc[q] = ((const mcx_d2*)tab)[jl];
+        sc[q] = ((const mcx_d2*)(tab + 2 * N))[(int)(w3[q] >> (32 - BMB))];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) {                                     // (C) no table value needed
+        const uint32_t lo = __builtin_amdgcn_alignbit(w3[q], w2[q], 11);
+        // 0x43300000 | (w3 & mask) >> 11 as one funnel shift of the constant over w3 << BMB
+        const uint32_t hi = __builtin_amdgcn_alignbit(0x43300000u >> (21 - BMB), w3[q] << BMB, 11 + BMB);
+        const double v = __hiloint2double((int)hi, (int)lo) - dc.off52;
+        const double d = fma(v, dc.trig_scale, vc.trig_off);
+        const double d2 = d * d;
+        double qs, qc;
+        if constexpr (mcx_bm_shape<BMB>::TRIG_TERMS == 3) {
+            qs = fma(fma(vc.sin_head, d2, C.c[7]), d2, C.c[6]);
+            qc = fma(fma(vc.cos_head, d2, C.c[10]), d2, C.c[9]);
+        } else {
+            qs = fma(vc.sin_head, d2, C.c[6]);
+            qc = fma(vc.cos_head, d2, C.c[9]);
+        }
+        ps[q] = fma(d * d2, qs, d);
+        pc[q] = fma(d2, qc, 1.0);
+        ed[q] = (double)e[q];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t top = 0;
+#pragma unroll
+    for (int q = 0; q < PPL; ++q) {                                     // (D) radius and rotation
+        const double s = fma(m[q], tc[q].x, 2.0);
+        double p = vc.log_head;
+#pragma unroll
+        for (int k = LOG_TERMS - 2; k >= 0; --k) p = fma(p, s, C.c[k]);
+        const double r2 = fma(ed[q], -2.0 * 6.93147180559945309417e-01, tc[q].y) + fma(s * s, p, s);
+        const double r = mcx_sqrt_gp(r2);
+        const double sn = fma(sc[q].x, pc[q], sc[q].y * ps[q]);
+        const double cs = fma(-sc[q].x, ps[q], sc[q].y * pc[q]);
+        z0[q] = r * cs;
+        z1[q] = r * sn;
+        top = w1[q] > top ? w1[q] : top;
+    }
+    // a first uniform may round to 1 only where its high word is all ones: the largest of the lane's high words is all ones exactly
+    // when one of them is (one v_max_u32 and one compare; the AND of the words would miss a lane that holds a single such word)
+    return top == 0xffffffffu;
+}
+
 #define MCX_LEAN_WAVES 4
 // SIMULATE = false: the same date programs on a paths tensor produced earlier by K1 (k1.paths is then the INPUT
 // [date][state][path]): one streaming pass, the next date's state columns in flight while this date's program runs
 // (Measured and dropped: drawing the normals of 2-5 sub-steps AHEAD as independent staged chains, for small path counts — the draws
 // depend on the counter (path, step) only.  No gain at one or two waves per SIMD: what a thin launch waits for is scalar work, see
 // launch_lean.)
-// DK (date kind) = 1: every date through lean_date_cva from the FastDateCvaLds records that follow the record area in the
-// dynamic LDS (launch_lean_shape: a.cva_dates != nullptr)
+// DK (date kind) != 0: every date through lean_date_cva from the FastDateCvaLds records that follow the record area in the
+// dynamic LDS (launch_lean_shape: a.cva_dates != nullptr).  DK = 1 draws through cva_draw_pairs: the kernel of a launch whose grid is
+// the whole residency.  DK = 2 keeps draw_pairs_staged: the kernel of a thin launch (one or two waves per SIMD), see launch_lean_shape.
 template <int NSLOT, int NZ, bool INJECT, int SIG, int PPL, bool SIMULATE, int DK = 0>
 __global__ __launch_bounds__(MCX_BLOCK, MCX_LEAN_WAVES) void kf_lean(const FusedArgs)      // read through kargs_region(), never by name
 {
@@ -77,8 +227,8 @@ __global__ __launch_bounds__(MCX_BLOCK, MCX_LEAN_WAVES) void kf_lean(const Fused
     const int n_rec = a0.n_rec;
     const int64_t n = a0.k1.n;
     for (int q = threadIdx.x; q < 9 * n_rec; q += MCX_BLOCK) lds[q] = 0.0;
-    FastDateCvaLds* const dlds = (FastDateCvaLds*)(lds + ((9 * n_rec + 1) & ~1));      // (DK = 1) 16-byte aligned
-    if constexpr (DK == 1) {
+    FastDateCvaLds* const dlds = (FastDateCvaLds*)(lds + ((9 * n_rec + 1) & ~1));      // (DK != 0) 16-byte aligned
+    if constexpr (DK != 0) {
         // every date's record, its regression rows gathered from the coefficient table of this run
         const FastDateCva* __restrict__ dc = a0.cva_dates;
         const double* __restrict__ cf = a0.coeffs;
@@ -150,6 +300,10 @@ __global__ __launch_bounds__(MCX_BLOCK, MCX_LEAN_WAVES) void kf_lean(const Fused
                 const uint64_t seed = k.seed;
                 const mcx_bm_coef bc = mcx_bm_coef_load(zr0);
                 const mcx_bm_vconst vc = mcx_bm_vconst_make<BMB>(bc);  // constants kept in registers across the run of sub-steps
+                // (DK = 1) the one high word of the launch's path indices, read where it is used like every other argument
+                uint32_t path_hi = 0;
+                CvaDrawConst dc = {};
+                if constexpr (DK == 1) { path_hi = ((const MCX_KONST uint32_t*)&k.path_offset)[1]; dc = cva_draw_const_make(); }
 #pragma unroll 1
                 while (st < 0 && step < n_steps) {
                     if constexpr (SIG == SIG_GENERIC) {
@@ -168,6 +322,15 @@ __global__ __launch_bounds__(MCX_BLOCK, MCX_LEAN_WAVES) void kf_lean(const Fused
                         if constexpr (INJECT) {
 #pragma unroll
                             for (int q = 0; q < PPL; ++q) sim_draw<NZ, true, SIG, BMB>(k, step, path[q], i[q], zz[q], uu[q], tab, seed, bc, &vc);
+                        } else if constexpr (DK == 1) {
+                            static_assert(NZ == 2, "one Philox block per path and sub-step");
+                            uint32_t plo[PPL];
+                            double za[PPL], zb[PPL];
+#pragma unroll
+                            for (int q = 0; q < PPL; ++q) plo[q] = (uint32_t)path[q];
+                            rare = cva_draw_pairs<PPL, BMB>(seed, plo, path_hi, (uint32_t)step, 0u, za, zb, tab, bc, vc, dc);
+#pragma unroll
+                            for (int q = 0; q < PPL; ++q) { zz[q][0] = za[q]; zz[q][1] = zb[q]; uu[q] = 0.0; }
                         } else {
                             uint32_t st_q[PPL];
 #pragma unroll
@@ -175,8 +338,15 @@ __global__ __launch_bounds__(MCX_BLOCK, MCX_LEAN_WAVES) void kf_lean(const Fused
                             rare = sim_draw_n<PPL, NZ, SIG, BMB>(k, st_q, path, zz, uu, tab, seed, bc, vc);
                         }
                         if (!INJECT && __builtin_expect(__any(rare), 0)) {
+                            if constexpr (DK == 1) {
+                                // only the low word of the path index is kept per lane
 #pragma unroll
-                            for (int q = 0; q < PPL; ++q) sim_draw<NZ, false, SIG, BMB, true>(k, step, path[q], i[q], zz[q], uu[q], tab, seed, bc, &vc);
+                                for (int q = 0; q < PPL; ++q)
+                                    sim_draw<NZ, false, SIG, BMB, true>(k, step, ((uint64_t)path_hi << 32) | (uint32_t)path[q], i[q], zz[q], uu[q], tab, seed, bc, &vc);
+                            } else {
+#pragma unroll
+                                for (int q = 0; q < PPL; ++q) sim_draw<NZ, false, SIG, BMB, true>(k, step, path[q], i[q], zz[q], uu[q], tab, seed, bc, &vc);
+                            }
                         }
 #pragma unroll
                         for (int q = 0; q < PPL; ++q) st = sim_apply_loaded<NSLOT, NZ, SIG, true>(k, sdat, reg[q], zz[q], uu[q]);   // POS: mcx_fused_create
@@ -185,7 +355,7 @@ __global__ __launch_bounds__(MCX_BLOCK, MCX_LEAN_WAVES) void kf_lean(const Fused
                 }
             }
             if (st >= 0) {
-                if constexpr (DK == 1) lean_date_cva<NSLOT, PPL>(dlds + st, reg, cva, etab);
+                if constexpr (DK != 0) lean_date_cva<NSLOT, PPL>(dlds + st, reg, cva, etab);
                 else lean_date<NSLOT, SIG, PPL, true>(st, i, live, first_tile, lds, reg, cfs, cva, est, etab);
             }
         }
@@ -245,7 +415,7 @@ __global__ __launch_bounds__(MCX_BLOCK, MCX_LEAN_WAVES) void kf_lean(const Fused
 
 // launch of one shape (paths per lane) of the kernel; returns the grid
 template <int NSLOT, int NZ, int SIG, int PPL>
-int launch_lean_shape(const FusedArgs& a, int n_cu, bool inject, bool simulate, hipStream_t s)
+int launch_lean_shape(const FusedArgs& a, int full_steps, int n_cu, bool inject, bool simulate, hipStream_t s)
 {
     const int64_t tiles = (a.k1.n + MCX_BLOCK * PPL - 1) / (MCX_BLOCK * PPL);
     const size_t lds = sizeof(double) * (size_t)((9 * a.n_rec + 1) & ~1);
@@ -282,22 +452,41 @@ int launch_lean_shape(const FusedArgs& a, int n_cu, bool inject, bool simulate, 
         auto kern = kf_lean<NSLOT, NZ, false, SIG, PPL, true>;
         const int64_t resident = residency(kern, lds);
         if constexpr (SIG == SIG_VAS_CIR_E) {
-            // the cva-date kernel, unless its date records in LDS (128 B per date) cost a block per CU
-            auto kern_cva = kf_lean<NSLOT, NZ, false, SIG, PPL, true, 1>;
-            if (a.cva_dates && residency(kern_cva, lds_cva) >= resident) {
+            // the cva-date kernel, unless its date records in LDS (128 B per date) cost a block per CU or the launch's path
+            // indices do not share one high word (the early Philox rounds of cva_draw_pairs take that word as a scalar).
+            // A launch whose grid fills the chip (four blocks per CU, four waves per SIMD) draws through cva_draw_pairs, whose
+            // scalar chain at the head of every sub-step and whose table reads the other waves of the SIMD cover: the backend sinks
+            // stage C of those draws behind the rare-draw branch, away from the reads, and at four waves that order is the faster
+            // one.  Any thinner grid (fewer tiles than resident blocks, or a tile count that sized() deals to fewer blocks) has
+            // less to cover them with and keeps the staged draws of draw_pairs_staged (DK = 2).
+            auto kern_cva = kf_lean<NSLOT, NZ, false, SIG, 2, true, 1>;         // (two paths per lane only: a full launch)
+            auto kern_cva_thin = kf_lean<NSLOT, NZ, false, SIG, PPL, true, 2>;
+            const bool one_high_word = ((a.k1.path_offset + (uint64_t)(a.k1.n - 1)) >> 32) == (a.k1.path_offset >> 32);
+            if (a.cva_dates && one_high_word) {
                 grid = sized(resident);
-                hipLaunchKernelGGL(kern_cva, dim3(grid), dim3(MCX_BLOCK), lds_cva, s, a);
-                return grid;
+                if (PPL == 2 && grid >= resident) {
+                    if (residency(kern_cva, lds_cva) >= resident) {
+                        hipLaunchKernelGGL(kern_cva, dim3(grid), dim3(MCX_BLOCK), lds_cva, s, a);
+                        return grid;
+                    }
+                } else if (residency(kern_cva_thin, lds_cva) >= resident) {
+                    hipLaunchKernelGGL(kern_cva_thin, dim3(grid), dim3(MCX_BLOCK), lds_cva, s, a);
+                    return grid;
+                }
             }
         }
         grid = sized(resident);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(MCX_BLOCK), lds, s, a);
+        // a pass prepared for the cva-date kernel stops after the last date that adds to the CVA (fused_run_impl); every other
+        // kernel runs the whole step table
+        FusedArgs g = a;
+        g.k1.n_steps = full_steps;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(MCX_BLOCK), lds, s, g);
     }
     return grid;
 }
 
 template <int NSLOT, int NZ, int SIG>
-void launch_lean(const FusedArgs& a, int n_cu, bool inject, bool simulate, hipStream_t s, int* grid_out)
+void launch_lean(const FusedArgs& a, int full_steps, int n_cu, bool inject, bool simulate, hipStream_t s, int* grid_out)
 {
     // Full shape: two paths per lane where both fit the 128-VGPR budget of 4 waves per SIMD (the generic run-time-dispatch kernels
     // of several sub-models carry every model's step code and would spill: one path per lane).  512 paths per block-tile, 4 blocks
@@ -308,8 +497,8 @@ void launch_lean(const FusedArgs& a, int n_cu, bool inject, bool simulate, hipSt
     if (simulate && !inject) {
         const char* sh = getenv("MCX_LEAN_SHAPE");
         const int code = sh ? atoi(sh) : 0;
-        if (code == 11) { *grid_out = launch_lean_shape<NSLOT, NZ, SIG, 1>(a, n_cu, inject, simulate, s); return; }
-        if (code == 21) { *grid_out = launch_lean_shape<NSLOT, NZ, SIG, 2>(a, n_cu, inject, simulate, s); return; }
+        if (code == 11) { *grid_out = launch_lean_shape<NSLOT, NZ, SIG, 1>(a, full_steps, n_cu, inject, simulate, s); return; }
+        if (code == 21) { *grid_out = launch_lean_shape<NSLOT, NZ, SIG, 2>(a, full_steps, n_cu, inject, simulate, s); return; }
     }
 #endif
     // Small path counts (one GPU's share of a strong-scaled run: 2^20 paths over 8 GPUs = 2^17 each): the full shape would put one
@@ -319,10 +508,10 @@ void launch_lean(const FusedArgs& a, int n_cu, bool inject, bool simulate, hipSt
     // 0.176 against 0.195 ms at 131,072 paths, equal at 262,144, slower from there on (the scalar work per path doubles).
     const int64_t full_tiles = (a.k1.n + MCX_BLOCK * PPL - 1) / (MCX_BLOCK * PPL);
     if (PPL == 2 && simulate && !inject && full_tiles < (int64_t)2 * n_cu) {
-        *grid_out = launch_lean_shape<NSLOT, NZ, SIG, 1>(a, n_cu, inject, simulate, s);
+        *grid_out = launch_lean_shape<NSLOT, NZ, SIG, 1>(a, full_steps, n_cu, inject, simulate, s);
         return;
     }
-    *grid_out = launch_lean_shape<NSLOT, NZ, SIG, PPL>(a, n_cu, inject, simulate, s);
+    *grid_out = launch_lean_shape<NSLOT, NZ, SIG, PPL>(a, full_steps, n_cu, inject, simulate, s);
 }
 
 }  // namespace
@@ -333,22 +522,22 @@ int mcx_launch_kf_lean(const FusedArgs& a, const mcx_sim_desc& sd, int n_cu, boo
 {
     int grid = -1;
     switch (mcx_sim_signature(sd)) {
-    case SIG_VAS_CIR_E: launch_lean<2, 2, SIG_VAS_CIR_E>(a, n_cu, inject, simulate, s, &grid); break;
+    case SIG_VAS_CIR_E: launch_lean<2, 2, SIG_VAS_CIR_E>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
 #ifndef MCX_LEAN_ONE_SIG
-    case SIG_BS_A: launch_lean<1, 1, SIG_BS_A>(a, n_cu, inject, simulate, s, &grid); break;
-    case SIG_BS_E: launch_lean<1, 1, SIG_BS_E>(a, n_cu, inject, simulate, s, &grid); break;
-    case SIG_HESTON_QE: launch_lean<1, 2, SIG_HESTON_QE>(a, n_cu, inject, simulate, s, &grid); break;
-    case SIG_HESTON_E: launch_lean<1, 2, SIG_HESTON_E>(a, n_cu, inject, simulate, s, &grid); break;
-    case SIG_VAS_E: launch_lean<1, 1, SIG_VAS_E>(a, n_cu, inject, simulate, s, &grid); break;
-    case SIG_VAS_A: launch_lean<1, 1, SIG_VAS_A>(a, n_cu, inject, simulate, s, &grid); break;
-    case SIG_BS_VAS_CIRDET_E: launch_lean<3, 3, SIG_BS_VAS_CIRDET_E>(a, n_cu, inject, simulate, s, &grid); break;
+    case SIG_BS_A: launch_lean<1, 1, SIG_BS_A>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
+    case SIG_BS_E: launch_lean<1, 1, SIG_BS_E>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
+    case SIG_HESTON_QE: launch_lean<1, 2, SIG_HESTON_QE>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
+    case SIG_HESTON_E: launch_lean<1, 2, SIG_HESTON_E>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
+    case SIG_VAS_E: launch_lean<1, 1, SIG_VAS_E>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
+    case SIG_VAS_A: launch_lean<1, 1, SIG_VAS_A>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
+    case SIG_BS_VAS_CIRDET_E: launch_lean<3, 3, SIG_BS_VAS_CIRDET_E>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
     default:
         switch (sd.n_slots * 16 + sd.n_z) {
-        case 1 * 16 + 1: launch_lean<1, 1, SIG_GENERIC>(a, n_cu, inject, simulate, s, &grid); break;
-        case 1 * 16 + 2: launch_lean<1, 2, SIG_GENERIC>(a, n_cu, inject, simulate, s, &grid); break;
-        case 2 * 16 + 2: launch_lean<2, 2, SIG_GENERIC>(a, n_cu, inject, simulate, s, &grid); break;
-        case 3 * 16 + 3: launch_lean<3, 3, SIG_GENERIC>(a, n_cu, inject, simulate, s, &grid); break;
-        case 4 * 16 + 4: launch_lean<4, 4, SIG_GENERIC>(a, n_cu, inject, simulate, s, &grid); break;
+        case 1 * 16 + 1: launch_lean<1, 1, SIG_GENERIC>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
+        case 1 * 16 + 2: launch_lean<1, 2, SIG_GENERIC>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
+        case 2 * 16 + 2: launch_lean<2, 2, SIG_GENERIC>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
+        case 3 * 16 + 3: launch_lean<3, 3, SIG_GENERIC>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
+        case 4 * 16 + 4: launch_lean<4, 4, SIG_GENERIC>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
         default: break;
         }
 #else
