@@ -4,8 +4,8 @@
 // (controller/controller.py:609-627, regression coefficients carry their graph: :370-383).  Here the derivative travels
 // forward in dual numbers, MCX_TANGENT_NP parameters per pass:
 //   kt_paths : K1 with dual state           -> paths [T][D][N] and d paths / d theta [NP][T][D][N]
-//   kt_lsm   : normal equations of one (product, regression date) with dual moments (the host differentiates the solve:
-//              G c = r  =>  dc = G^-1 (dr - dG c))
+//   kt_lsm_batch : normal equations of (product, regression date) jobs with dual moments (the host differentiates the solve:
+//              G c = r  =>  dc = G^-1 (dr - dG c)); mcx_tangent_lsm is its one-job case
 //   kt_eval  : the book's cashflow / polynomial-exposure events with dual atoms and dual coefficients
 //   kt_cva   : sum_m relu(thr(E_m)) S(0,t_m) (1 - S(t_m,t_m+1)) (1-R) per path with tangents (cva_metric.py:62-100)
 // The derivatives of every host-computed descriptor number (model parameters per slot, psi(t) tables, initial state, the
@@ -56,10 +56,7 @@ __device__ __forceinline__ void ktp_store(const KTPArgs& a, int t, int64_t i, co
         const int c = k.slots[s].state_off;
         const int nd = k.slots[s].kind == MCX_MODEL_BS ? 1 : 2;
         for (int e = 0; e < nd; ++e) {
-            const int64_t off = ((int64_t)t * D + c + e) * k.ld + i;
-            k.paths[off] = reg[2 * s + e].v;
-#pragma unroll
-            for (int q = 0; q < NP; ++q) a.dpaths[q * a.pstride + off] = reg[2 * s + e].d[q];
+            dstore(k.paths, a.dpaths, a.pstride, ((int64_t)t * D + c + e) * k.ld + i, reg[2 * s + e]);
         }
     }
 }
@@ -158,6 +155,8 @@ struct KTBook {
     const DevTerm* __restrict__ terms;
     const DevEvent* __restrict__ events;
     const DevAtom* __restrict__ atoms;
+    const DevEventIds* __restrict__ ev_ids;   // DevEvent and DevTerm carry COPIES of their atoms: the ids behind them find the
+    const int32_t* __restrict__ term_atom;    // derivative rows ([n_events], [n_terms]; the book's, mcx_book_tangent_ids)
     const double* __restrict__ datoms;   // [n_atoms][5][NP]: d(a, d, b, c0, c1) / d theta
     const double* __restrict__ paths;
     const double* __restrict__ dpaths;
@@ -169,38 +168,35 @@ __device__ __forceinline__ DN kt_atom(const KTBook& b, const DevAtom& a, int ato
 {
     const double* __restrict__ da = b.datoms + (int64_t)atom_id * 5 * NP;
     DN x = dconst<NP>(0.0);
-    if (a.col >= 0) {
-        const int64_t off = ((int64_t)a.t_idx * b.n_state + a.col) * b.ld + i;
-        x.v = b.paths[off];
-#pragma unroll
-        for (int q = 0; q < NP; ++q) x.d[q] = b.dpaths[q * b.pstride + off];
-    }
+    if (a.col >= 0) x = dload<NP>(b.paths, b.dpaths, b.pstride, ((int64_t)a.t_idx * b.n_state + a.col) * b.ld + i);
     DN v = ld_dual(a.a, da) + ld_dual(a.d, da + NP) * x;
     if (a.b != 0.0) v = v + ld_dual(a.b, da + 2 * NP) * dexp(ld_dual(a.c0, da + 3 * NP) + ld_dual(a.c1, da + 4 * NP) * x);
     return v;
 }
 
-// DevEvent carries COPIES of its numeraire / explanatory atoms; the tangent kernels need their ids to find the derivative rows
-struct KTEventIds { int32_t num, x; };
-
-// normalised dual cashflow of one stateless cash event (CASHFLOW or plain OPTION)
-__device__ __forceinline__ DN kt_cash_event(const KTBook& b, const DevEvent& e, const KTEventIds& id, const int32_t* __restrict__ term_atom, int64_t i)
+// sum of an event's weighted dual terms; the terms over a denominator of their own (mcx_term.den, the unequal-tenor swap quirk) go
+// to `own`.  Only CASHFLOW events have such terms: the host refuses them under OPTION and EXERCISE events (kt_tangent_form)
+__device__ __forceinline__ DN kt_term_sum(const KTBook& b, const DevEvent& e, int64_t i, DN& own)
 {
-    const DN num = kt_atom(b, e.num, id.num, i);
-    DN val = dconst<NP>(0.0), own = dconst<NP>(0.0);
+    DN val = dconst<NP>(0.0);
+    own = dconst<NP>(0.0);
     for (int j = e.term_begin; j < e.term_end; ++j) {
         const DevTerm tm = ldk_struct(&b.terms[j]);
-        const DN v = kt_atom(b, tm.atom, ldk(term_atom + j), i) * tm.w;
+        const DN v = kt_atom(b, tm.atom, ldk(b.term_atom + j), i) * tm.w;
         if (tm.den < 0) val = val + v;
-        else own = own + v / kt_atom(b, ldk_struct(&b.atoms[tm.den]), tm.den, i);      // the unequal-tenor swap quirk (mcx_term.den)
+        else own = own + v / kt_atom(b, ldk_struct(&b.atoms[tm.den]), tm.den, i);
     }
+    return val;
+}
+
+// normalised dual cashflow of one stateless cash event (CASHFLOW or plain OPTION)
+__device__ __forceinline__ DN kt_cash_event(const KTBook& b, const DevEvent& e, const DevEventIds& id, int64_t i)
+{
+    const DN num = kt_atom(b, e.num, id.num, i);
+    DN own;
+    const DN val = kt_term_sum(b, e, i, own);
     if (e.kind == MCX_EV_CASHFLOW) return val / num + own;
-    const DN x = (val - e.strike) * e.sign;                         // torch.maximum(x, 0): gradient 1 for x > 0, 1/2 at the tie
-    const double w = x.v > 0.0 ? 1.0 : (x.v == 0.0 ? 0.5 : 0.0);
-    DN pay;
-    pay.v = fmax(x.v, 0.0);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) pay.d[q] = w * x.d[q];
+    const DN pay = dmax0((val - e.strike) * e.sign);
     return pay / num;
 }
 
@@ -211,22 +207,13 @@ __device__ __forceinline__ DN kt_cash_event(const KTBook& b, const DevEvent& e, 
 // State-independent pieces of one MCX_EV_EXERCISE event for path i: the dual immediate value already divided by the numeraire and
 // the primal explanatory variable of the continuation polynomial.
 struct KTExercise { DN pay; double imm, x; };
-__device__ __forceinline__ KTExercise kt_exercise_value(const KTBook& b, const DevEvent& e, const KTEventIds& id, const int32_t* __restrict__ term_atom,
-                                                         int64_t i)
+__device__ __forceinline__ KTExercise kt_exercise_value(const KTBook& b, const DevEvent& e, const DevEventIds& id, int64_t i)
 {
     KTExercise r;
     const DN num = kt_atom(b, e.num, id.num, i);
-    DN val = dconst<NP>(0.0);
-    for (int j = e.term_begin; j < e.term_end; ++j) {
-        const DevTerm tm = ldk_struct(&b.terms[j]);
-        val = val + kt_atom(b, tm.atom, ldk(term_atom + j), i) * tm.w;
-    }
-    const DN xs = (val - e.strike) * e.sign;                         // torch.maximum(x, 0): gradient 1 for x > 0, 1/2 at the tie
-    const double w = xs.v > 0.0 ? 1.0 : (xs.v == 0.0 ? 0.5 : 0.0);
-    DN imm;
-    imm.v = fmax(xs.v, 0.0);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) imm.d[q] = w * xs.d[q];
+    DN own;
+    const DN val = kt_term_sum(b, e, i, own);
+    const DN imm = dmax0((val - e.strike) * e.sign);
     r.pay = imm / num;
     r.imm = imm.v;
     r.x = e.coeff_off >= 0 ? kt_atom(b, e.x, id.x, i).v : 0.0;
@@ -251,13 +238,49 @@ __device__ __forceinline__ bool kt_exercises(const DevEvent& e, const double* __
     return ex;
 }
 
+// ---- LSM moments with tangents ------------------------------------------------------------------------------------------
+// moments of a regression date over S hypothetical states, [1+NP][(2K-1) + S K] per lane in registers: the powers z^0 .. z^(2K-2)
+// of the normalised explanatory variable (Gram matrix), then z^k (num w[s]) for k < K (right-hand side of state s)
+template <int K, int S>
+__device__ __forceinline__ void kt_moments_add(double (&acc)[1 + NP][(2 * K - 1) + S * K], const DN& z, const DN& num, const DN (&w)[S])
+{
+    DN zp = dconst<NP>(1.0);
+#pragma unroll
+    for (int k = 0; k < 2 * K - 1; ++k) {
+        acc[0][k] += zp.v;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) acc[1 + q][k] += zp.d[q];
+        if (k < K) {
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                const DN zy = zp * (num * w[s]);
+                acc[0][(2 * K - 1) + s * K + k] += zy.v;
+#pragma unroll
+                for (int q = 0; q < NP; ++q) acc[1 + q][(2 * K - 1) + s * K + k] += zy.d[q];
+            }
+        }
+        zp = zp * z;
+    }
+}
+// the block's sums of every moment to `partials` [1+NP][NM] (the caller's tile)
+template <int NM>
+__device__ __forceinline__ void kt_moments_store(const double (&acc)[1 + NP][NM], double* __restrict__ partials)
+{
+    __shared__ double lds[4];
+#pragma unroll
+    for (int q = 0; q <= NP; ++q)
+#pragma unroll
+        for (int m = 0; m < NM; ++m) {
+            const double r = block_sum(acc[q][m], lds);
+            if (threadIdx.x == 0) partials[q * NM + m] = r;
+        }
+}
+
 // ---- LSM step of an exercise product with tangents: the cashflow cache is rolled one window back along the frozen policy ----------
 // (controller.py:316-383; K3's k3_roll in dual numbers).  W [S][ld_w] and dW [NP][S][ld_w] hold, per hypothetical state, the
 // discounted cashflows after the previous regression date and their tangents; moments [1+NP][(2K-1) + S K].
 struct KTSArgs {
     KTBook b;
-    const KTEventIds* __restrict__ ev_ids;
-    const int32_t* __restrict__ term_atom;
     const double* __restrict__ coeffs;         // primal coefficients of the base run (decisions)
     double* __restrict__ W;
     double* __restrict__ dW;
@@ -280,11 +303,7 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_lsm_step(const KTSArgs a)
     for (int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x; i < a.b.n; i += (int64_t)gridDim.x * MCX_BLOCK) {
         DN w[S];
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-            w[s].v = a.W[(int64_t)s * a.ld_w + i];
-#pragma unroll
-            for (int q = 0; q < NP; ++q) w[s].d[q] = a.dW[q * a.w_stride + (int64_t)s * a.ld_w + i];
-        }
+        for (int s = 0; s < S; ++s) w[s] = dload<NP>(a.W, a.dW, a.w_stride, (int64_t)s * a.ld_w + i);
         if (a.roll_end > a.roll_begin) {
             int st[S];
             DN sv[S];
@@ -292,14 +311,14 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_lsm_step(const KTSArgs a)
             for (int s0 = 0; s0 < S; ++s0) { st[s0] = s0; sv[s0] = dconst<NP>(0.0); }
             for (int q = a.roll_begin; q < a.roll_end; ++q) {                   // controller.py:333-341
                 const DevEvent e = ldk_struct(&a.b.events[q]);
-                const KTEventIds id = ldk_struct(&a.ev_ids[q]);
+                const DevEventIds id = ldk_struct(&a.b.ev_ids[q]);
                 if (e.kind == MCX_EV_EXERCISE) {
-                    const KTExercise ev = kt_exercise_value(a.b, e, id, a.term_atom, i);      // once per path and date, not per state
+                    const KTExercise ev = kt_exercise_value(a.b, e, id, i);      // once per path and date, not per state
 #pragma unroll
                     for (int s0 = 0; s0 < S; ++s0)
                         if (kt_exercises(e, a.coeffs, K, ev, st[s0])) sv[s0] = sv[s0] + ev.pay;
                 } else {
-                    const DN v = kt_cash_event(a.b, e, id, a.term_atom, i);
+                    const DN v = kt_cash_event(a.b, e, id, i);
 #pragma unroll
                     for (int s0 = 0; s0 < S; ++s0) sv[s0] = sv[s0] + v;
                 }
@@ -315,149 +334,56 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_lsm_step(const KTSArgs a)
 #pragma unroll
             for (int s = 0; s < S; ++s) {
                 w[s] = wn[s];
-                a.W[(int64_t)s * a.ld_w + i] = wn[s].v;
-#pragma unroll
-                for (int q = 0; q < NP; ++q) a.dW[q * a.w_stride + (int64_t)s * a.ld_w + i] = wn[s].d[q];
+                dstore(a.W, a.dW, a.w_stride, (int64_t)s * a.ld_w + i, wn[s]);
             }
         }
         const DN num = kt_atom(a.b, a.num, a.num_id, i);                                   // :368
         const DN z = (kt_atom(a.b, a.x, a.x_id, i) - a.shift) * a.scale;
-        DN zp = dconst<NP>(1.0);
-#pragma unroll
-        for (int k = 0; k < 2 * K - 1; ++k) {
-            acc[0][k] += zp.v;
-#pragma unroll
-            for (int q = 0; q < NP; ++q) acc[1 + q][k] += zp.d[q];
-            if (k < K) {
-#pragma unroll
-                for (int s = 0; s < S; ++s) {
-                    const DN zy = zp * (num * w[s]);
-                    acc[0][(2 * K - 1) + s * K + k] += zy.v;
-#pragma unroll
-                    for (int q = 0; q < NP; ++q) acc[1 + q][(2 * K - 1) + s * K + k] += zy.d[q];
-                }
-            }
-            zp = zp * z;
-        }
+        kt_moments_add<K, S>(acc, z, num, w);
     }
-    __shared__ double lds[4];
-#pragma unroll
-    for (int q = 0; q <= NP; ++q)
-#pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            const double r = block_sum(acc[q][m], lds);
-            if (threadIdx.x == 0) a.partials[((int64_t)blockIdx.x * (1 + NP) + q) * NM + m] = r;
-        }
+    kt_moments_store<NM>(acc, a.partials + (int64_t)blockIdx.x * ((1 + NP) * NM));
 }
 
-// ---- LSM moments with tangents ------------------------------------------------------------------------------------------
+// ---- LSM moments of stateless products ---------------------------------------------------------------------------------------
 // one (product, regression date): the flattened numeraire / explanatory atoms, their ids and the product's cash events it sums
 struct KTLJob {
     DevAtom num, x;
     double shift, scale;
     int32_t ev_first, ev_end, num_id, x_id;
 };
-struct KTLArgs {
-    KTBook b;
-    const KTEventIds* __restrict__ ev_ids;     // [n_events]
-    const int32_t* __restrict__ term_atom;     // [n_terms] atom id of every term
-    KTLJob job;
-    double* __restrict__ partials;             // [gridDim.x][(1+NP)][NM]
-};
 struct KTLBatchArgs {
     KTBook b;
-    const KTEventIds* __restrict__ ev_ids;
-    const int32_t* __restrict__ term_atom;
     const KTLJob* __restrict__ jobs;           // [gridDim.y] the jobs of this launch
     double* __restrict__ partials;             // [gridDim.y][gridDim.x][(1+NP)][NM]
 };
 
-// tile `tile` of `n_tiles` of one job: the paths tile, tile + n_tiles, ... in blocks of MCX_BLOCK, moments to partials[tile].
-// kt_lsm and kt_lsm_batch share this body — and with it the order of every sum — so a job gives the same bits through either.
-template <int K>
-__device__ __forceinline__ void kt_lsm_tile(const KTBook& b, const KTEventIds* __restrict__ ev_ids, const int32_t* __restrict__ term_atom,
-                                            const KTLJob& j, int tile, int n_tiles, double* __restrict__ partials)
-{
-    constexpr int NM = (2 * K - 1) + K;
-    double acc[1 + NP][NM];
-#pragma unroll
-    for (int q = 0; q <= NP; ++q)
-#pragma unroll
-        for (int m = 0; m < NM; ++m) acc[q][m] = 0.0;
-    for (int64_t i = (int64_t)tile * MCX_BLOCK + threadIdx.x; i < b.n; i += (int64_t)n_tiles * MCX_BLOCK) {
-        DN total = dconst<NP>(0.0);
-        for (int q = j.ev_first; q < j.ev_end; ++q)                                       // controller.py:333-352 without the cache
-            total = total + kt_cash_event(b, ldk_struct(&b.events[q]), ldk_struct(&ev_ids[q]), term_atom, i);
-        const DN y = kt_atom(b, j.num, j.num_id, i) * total;                               // :368
-        const DN z = (kt_atom(b, j.x, j.x_id, i) - j.shift) * j.scale;
-        DN zp = dconst<NP>(1.0);
-#pragma unroll
-        for (int k = 0; k < 2 * K - 1; ++k) {
-            acc[0][k] += zp.v;
-#pragma unroll
-            for (int q = 0; q < NP; ++q) acc[1 + q][k] += zp.d[q];
-            if (k < K) {
-                const DN zy = zp * y;
-                acc[0][(2 * K - 1) + k] += zy.v;
-#pragma unroll
-                for (int q = 0; q < NP; ++q) acc[1 + q][(2 * K - 1) + k] += zy.d[q];
-            }
-            zp = zp * z;
-        }
-    }
-    __shared__ double lds[4];
-#pragma unroll
-    for (int q = 0; q <= NP; ++q)
-#pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            const double r = block_sum(acc[q][m], lds);
-            if (threadIdx.x == 0) partials[((int64_t)tile * (1 + NP) + q) * NM + m] = r;
-        }
-}
-
-template <int K>
-__global__ __launch_bounds__(MCX_BLOCK) void kt_lsm(const KTLArgs a)
-{
-    kt_lsm_tile<K>(a.b, a.ev_ids, a.term_atom, a.job, (int)blockIdx.x, (int)gridDim.x, a.partials);
-}
-
-// many jobs in one launch: grid (tiles, jobs).  The job is wave-uniform: its record arrives through scalar loads, as the events do.
+// grid (tiles, jobs): block (t, j) takes the paths t, t + tiles, ... of job j in blocks of MCX_BLOCK, so the order of every sum of
+// a job depends on the path count alone, not on the jobs around it.  The job is wave-uniform: its record arrives through scalar
+// loads, as the events do.
 template <int K>
 __global__ __launch_bounds__(MCX_BLOCK) void kt_lsm_batch(const KTLBatchArgs a)
 {
     constexpr int NM = (2 * K - 1) + K;
     const KTLJob j = ldk_struct(&a.jobs[blockIdx.y]);
-    kt_lsm_tile<K>(a.b, a.ev_ids, a.term_atom, j, (int)blockIdx.x, (int)gridDim.x,
-                   a.partials + (int64_t)blockIdx.y * gridDim.x * ((1 + NP) * NM));
-}
-
-__global__ void kt_sum_partials(const double* __restrict__ partials, int count, int n_blocks, double* __restrict__ out)
-{
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= count) return;
-    double s = 0.0;
-    for (int b = 0; b < n_blocks; ++b) s += partials[(int64_t)b * count + j];
-    out[j] = s;
-}
-
-// kt_sum_partials for partials [n_jobs][n_tiles][count] -> out [n_jobs][count]: every (job, entry) adds its tiles in ascending order
-__global__ void kt_sum_partials_batch(const double* __restrict__ partials, int count, int n_tiles, int64_t total, double* __restrict__ out)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= total) return;
-    const int64_t job = t / count;
-    const int e = (int)(t - job * count);
-    const double* __restrict__ p = partials + job * n_tiles * count + e;
-    double s = 0.0;
-    for (int b = 0; b < n_tiles; ++b) s += p[(int64_t)b * count];
-    out[t] = s;
+    double acc[1 + NP][NM];
+#pragma unroll
+    for (int q = 0; q <= NP; ++q)
+#pragma unroll
+        for (int m = 0; m < NM; ++m) acc[q][m] = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x; i < a.b.n; i += (int64_t)gridDim.x * MCX_BLOCK) {
+        DN total[1] = {dconst<NP>(0.0)};
+        for (int q = j.ev_first; q < j.ev_end; ++q)                                       // controller.py:333-352 without the cache
+            total[0] = total[0] + kt_cash_event(a.b, ldk_struct(&a.b.events[q]), ldk_struct(&a.b.ev_ids[q]), i);
+        const DN num = kt_atom(a.b, j.num, j.num_id, i);                                   // :368
+        const DN z = (kt_atom(a.b, j.x, j.x_id, i) - j.shift) * j.scale;
+        kt_moments_add<K, 1>(acc, z, num, total);
+    }
+    kt_moments_store<NM>(acc, a.partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * ((1 + NP) * NM));
 }
 
 // ---- book evaluation with tangents ----------------------------------------------------------------------------------------
 struct KTEArgs {
     KTBook b;
-    const KTEventIds* __restrict__ ev_ids;
-    const int32_t* __restrict__ term_atom;
     const DevProduct* __restrict__ products;
     const double* __restrict__ coeffs;         // [n_coeffs] regression coefficients of the tangent pass
     const double* __restrict__ dcoeffs;        // [n_coeffs][NP]
@@ -479,12 +405,12 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_eval(const KTEArgs a)
         int state = pr.init_state;                                                        // rights left (exercise products)
         for (int q = pr.ev_begin; q < pr.ev_end; ++q) {
             const DevEvent e = ldk_struct(&a.b.events[q]);
-            const KTEventIds id = ldk_struct(&a.ev_ids[q]);
+            const DevEventIds id = ldk_struct(&a.b.ev_ids[q]);
             if (e.kind <= MCX_EV_OPTION) {
-                acc = acc + kt_cash_event(a.b, e, id, a.term_atom, i);
+                acc = acc + kt_cash_event(a.b, e, id, i);
             } else if (e.kind == MCX_EV_EXERCISE) {
                 // decision from the primal values, tangent through the taken branch only (bermudan_option.py:93-131)
-                const KTExercise ev = kt_exercise_value(a.b, e, id, a.term_atom, i);
+                const KTExercise ev = kt_exercise_value(a.b, e, id, i);
                 if (kt_exercises(e, a.coeffs, K, ev, state)) acc = acc + ev.pay;
             } else {                                                                      // exposures (controller.py:430-447)
                 DN v = dconst<NP>(0.0);
@@ -519,25 +445,16 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_eval(const KTEArgs a)
                     // the coefficient row of the path's exercise state (product.py:150-184); stateless products: row 0
                     const int row0 = e.coeff_off + (pr.n_states > 1 ? state * K : 0);
                     for (int k = 0; k < K; ++k) {
-                        DN ck;
-                        ck.v = a.coeffs[row0 + k];
-#pragma unroll
-                        for (int r = 0; r < NP; ++r) ck.d[r] = a.dcoeffs[(int64_t)(row0 + k) * NP + r];
+                        const DN ck = dload<NP>(a.coeffs + (row0 + k), a.dcoeffs + (int64_t)(row0 + k) * NP, 1, 0);
                         v = v + ck * xp;
                         xp = xp * x;
                     }
                     v = v / kt_atom(a.b, e.num, id.num, i);
                 }
-                const int64_t off = ((int64_t)pr.netting_set * a.n_rows + e.row) * a.b.ld + i;
-                a.expo[off] += v.v;
-#pragma unroll
-                for (int r = 0; r < NP; ++r) a.expo[(1 + r) * ex_stride + off] += v.d[r];
+                dadd(a.expo, a.expo + ex_stride, ex_stride, ((int64_t)pr.netting_set * a.n_rows + e.row) * a.b.ld + i, v);
             }
         }
-        const int64_t off = (int64_t)pr.netting_set * a.b.ld + i;
-        a.cfs[off] += acc.v;
-#pragma unroll
-        for (int r = 0; r < NP; ++r) a.cfs[(1 + r) * cf_stride + off] += acc.d[r];
+        dadd(a.cfs, a.cfs + cf_stride, cf_stride, (int64_t)pr.netting_set * a.b.ld + i, acc);
     }
 }
 
@@ -553,23 +470,15 @@ __device__ __forceinline__ DN kt_thr(const DN& e, double h)
     else r = dconst<NP>(0.0);
     return r;
 }
-__device__ __forceinline__ DN kt_load_expo(const double* __restrict__ expo, int64_t ex_stride, int64_t off)
-{
-    DN e;
-    e.v = expo[off];
-#pragma unroll
-    for (int q = 0; q < NP; ++q) e.d[q] = expo[(1 + q) * ex_stride + off];
-    return e;
-}
 __device__ __forceinline__ DN kt_unsecured(const double* __restrict__ expo, int64_t ex_stride, const int32_t* __restrict__ rows,
                                            const int32_t* __restrict__ delayed, int collateralized, double h, int64_t ld, int m, int64_t i)
 {
-    const DN e = kt_load_expo(expo, ex_stride, (int64_t)ldk(rows + m) * ld + i);
+    const DN e = dload<NP>(expo, expo + ex_stride, ex_stride, (int64_t)ldk(rows + m) * ld + i);
     if (!collateralized) return kt_thr(e, h);
     if (!delayed) return e;
     const int dm = ldk(delayed + m);
     if (dm < 0) return e;
-    return e - kt_thr(kt_load_expo(expo, ex_stride, (int64_t)dm * ld + i), h);
+    return e - kt_thr(dload<NP>(expo, expo + ex_stride, ex_stride, (int64_t)dm * ld + i), h);
 }
 
 struct KTCArgs {
@@ -598,9 +507,7 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_cva(const KTCArgs a)
         const DN cs = kt_atom(a.b, ldk_struct(&a.b.atoms[ca]), ca, i);
         cva = cva + pos * sp * (1.0 - cs);
     }
-    a.out[i] = cva.v * a.lgd;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) a.out[(1 + q) * a.b.ld + i] = cva.d[q] * a.lgd;
+    dstore(a.out, a.out + a.b.ld, a.b.ld, i, cva * a.lgd);
 }
 
 // ---- EPE / ENE profile tangents: sum_i 1[u > 0] du and sum_i 1[u < 0] du per metric date (epe_metric.py, ene_metric.py) -----
@@ -686,69 +593,58 @@ void launch_ktp(const KTPArgs& a, int grid, bool inject, hipStream_t s)
     else hipLaunchKernelGGL((kt_paths<NSLOT, NZ, false>), dim3(grid), dim3(MCX_BLOCK), 0, s, a);
 }
 
-struct DevBuf {            // scoped device allocation
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t upload(const void* src, size_t bytes, hipStream_t s)
-    {
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 8);
-        if (e != hipSuccess) return e;
-        return bytes ? hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    }
-};
-
+// the book's device tables (the id tables are uploaded by the first call that gets here) and the call's dual tensors
 int fill_book(mcx_handle* h, const mcx_book* b, const double* d_datoms, const double* d_paths, const double* d_dpaths, int64_t n_paths,
               int64_t ld, int32_t n_dates, KTBook* out)
 {
-    out->terms = b->d_terms; out->events = b->d_events; out->atoms = b->d_atoms; out->datoms = d_datoms; out->paths = d_paths;
-    out->dpaths = d_dpaths; out->n = n_paths; out->ld = ld; out->pstride = (int64_t)n_dates * b->n_state * ld;
-    out->n_state = b->n_state; out->n_basis = b->n_basis;
+    if (int rc = mcx_book_tangent_ids(h, b)) return rc;
+    out->terms = b->d_terms; out->events = b->d_events; out->atoms = b->d_atoms; out->ev_ids = b->d_event_ids; out->term_atom = b->d_term_atom;
+    out->datoms = d_datoms; out->paths = d_paths; out->dpaths = d_dpaths; out->n = n_paths; out->ld = ld;
+    out->pstride = (int64_t)n_dates * b->n_state * ld; out->n_state = b->n_state; out->n_basis = b->n_basis;
     return 0;
 }
 
-// ids of the atoms behind every event / term (the flattened device records hold copies, the derivative rows are per atom id)
-struct HostIds { std::vector<KTEventIds> ids; std::vector<int32_t> ta; };
-// enqueues the uploads: `host` stays alive until the stream has been synchronised
-int upload_ids_async(mcx_handle* h, const mcx_book* b, HostIds& host, DevBuf& ev_ids, DevBuf& term_atom, hipStream_t s)
+// does event e have a tangent form?  `allowed`: the kinds the caller's kernel handles, one bit (1 << MCX_EV_*) each.  Of those,
+// options in plain mode and exercise events under the Bermudan (0) or FlexiCall (1) rule, neither over per-term denominators
+// (kt_term_sum's `own` is read by CASHFLOW events only).  The callers word their own messages.
+enum KTForm { KT_FORM_OK = 0, KT_FORM_NONE, KT_FORM_TERM_DEN };
+constexpr unsigned KT_CASH_KINDS = 1u << MCX_EV_CASHFLOW | 1u << MCX_EV_OPTION;
+KTForm kt_tangent_form(const mcx_book* b, const DevEvent& e, unsigned allowed)
 {
-    host.ids.resize((size_t)b->n_events);
-    for (int q = 0; q < b->n_events; ++q) { host.ids[q].num = b->h_event_num_atom[q]; host.ids[q].x = b->h_event_x_atom[q]; }
-    host.ta.resize((size_t)b->n_terms);
-    for (int j = 0; j < b->n_terms; ++j) host.ta[j] = b->h_term_atom[j];
-    MCX_HIP(h, ev_ids.upload(host.ids.data(), sizeof(KTEventIds) * host.ids.size(), s));
-    MCX_HIP(h, term_atom.upload(host.ta.data(), sizeof(int32_t) * host.ta.size(), s));
-    return 0;
+    if (e.kind < 0 || e.kind > MCX_EV_EXPO_BS || !(allowed >> e.kind & 1u)) return KT_FORM_NONE;
+    if (e.kind == MCX_EV_OPTION && e.aux[0] != 0.0) return KT_FORM_NONE;
+    if (e.kind == MCX_EV_EXERCISE && e.aux[0] != 0.0 && e.aux[0] != 1.0) return KT_FORM_NONE;
+    if (e.kind == MCX_EV_OPTION || e.kind == MCX_EV_EXERCISE)
+        for (int j = e.term_begin; j < e.term_end; ++j)
+            if (b->h_terms[j].den >= 0) return KT_FORM_TERM_DEN;
+    return KT_FORM_OK;
 }
-int upload_ids(mcx_handle* h, const mcx_book* b, DevBuf& ev_ids, DevBuf& term_atom, hipStream_t s)
+// the check of the events [q0, q1) of a moment entry point, which names the option mode in its message
+int kt_check_cash_events(mcx_handle* h, const mcx_book* b, int q0, int q1, unsigned allowed, const char* who)
 {
-    HostIds host;
-    if (int rc = upload_ids_async(h, b, host, ev_ids, term_atom, s)) return rc;
-    MCX_HIP(h, hipStreamSynchronize(s));
+    for (int q = q0; q < q1; ++q) {
+        const DevEvent& e = b->h_events[q];
+        const KTForm f = kt_tangent_form(b, e, allowed);
+        if (f == KT_FORM_NONE) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: event %d (kind %d, mode %g) has no tangent form", who, q, e.kind, e.aux[0]);
+        if (f == KT_FORM_TERM_DEN) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: option over per-term denominators", who);
+    }
     return 0;
 }
 
 // what mcx_tangent_lsm and mcx_tangent_lsm_batch check of one (product, regression date) before anything is enqueued; fills the
 // device record of the job
-int ktl_check_job(mcx_handle* h, const mcx_book* b, int32_t product, int32_t first_event, int32_t num_atom, int32_t x_atom, double shift,
-                  double scale, const char* who, KTLJob* out)
+int ktl_check_job(mcx_handle* h, const mcx_book* b, const mcx_tangent_lsm_job& q, const char* who, KTLJob* out)
 {
-    if (product < 0 || product >= b->n_products) MCX_FAIL(h, -2, "%s: product out of range", who);
-    const DevProduct& pr = b->h_products[product];
+    if (q.product < 0 || q.product >= b->n_products) MCX_FAIL(h, -2, "%s: product out of range", who);
+    const DevProduct& pr = b->h_products[q.product];
     if (pr.n_states != 1) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: stateless products only", who);
     const int n_cf = pr.cf_end - pr.cf_begin;
-    if (first_event < 0 || first_event > n_cf) MCX_FAIL(h, -2, "%s: first_event out of range", who);
-    for (int q = pr.cf_begin; q < pr.cf_end; ++q) {
-        const DevEvent& e = b->h_events[q];
-        if (!(e.kind == MCX_EV_CASHFLOW || (e.kind == MCX_EV_OPTION && e.aux[0] == 0.0)))
-            MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: event %d (kind %d, mode %g) has no tangent form", who, q, e.kind, e.aux[0]);
-        if (e.kind == MCX_EV_OPTION)
-            for (int j = e.term_begin; j < e.term_end; ++j)
-                if (b->h_terms[j].den >= 0) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: option over per-term denominators", who);
-    }
-    if (num_atom < 0 || num_atom >= b->n_atoms || x_atom < 0 || x_atom >= b->n_atoms) MCX_FAIL(h, -2, "%s: atom out of range", who);
+    if (q.first_event < 0 || q.first_event > n_cf) MCX_FAIL(h, -2, "%s: first_event out of range", who);
+    if (int rc = kt_check_cash_events(h, b, pr.cf_begin, pr.cf_end, KT_CASH_KINDS, who)) return rc;
+    if (q.num_atom < 0 || q.num_atom >= b->n_atoms || q.x_atom < 0 || q.x_atom >= b->n_atoms) MCX_FAIL(h, -2, "%s: atom out of range", who);
     memset(out, 0, sizeof(*out));
-    out->num = mcx_flat_atom(b->h_atoms[num_atom]); out->x = mcx_flat_atom(b->h_atoms[x_atom]); out->num_id = num_atom; out->x_id = x_atom;
-    out->shift = shift; out->scale = scale; out->ev_first = pr.cf_begin + first_event; out->ev_end = pr.cf_end;
+    out->num = mcx_flat_atom(b->h_atoms[q.num_atom]); out->x = mcx_flat_atom(b->h_atoms[q.x_atom]); out->num_id = q.num_atom; out->x_id = q.x_atom;
+    out->shift = q.shift; out->scale = q.scale; out->ev_first = pr.cf_begin + q.first_event; out->ev_end = pr.cf_end;
     return 0;
 }
 
@@ -767,6 +663,62 @@ size_t ktl_partial_cap(const mcx_handle* h)
 }
 constexpr int KTL_MAX_LAUNCH_JOBS = 32768;     // gridDim.y
 
+// mcx_tangent_lsm_batch, and mcx_tangent_lsm as its one-job case (`who`; the batch names the job in front of a job's refusal).
+// Every job of the table in launches of grid (tiles, jobs): the job table (scratch slot 1 where the ring is too small) and the
+// result block (slot 3) exist once per call; partials [job][tile][1+NP][NM] in the workspace, as many whole jobs per launch as
+// fit; ONE synchronisation, at the end
+int ktl_run(mcx_handle* h, const mcx_book* b, const mcx_tangent_lsm_job* h_jobs, int32_t n_jobs, const double* d_datoms, const double* d_paths,
+            const double* d_dpaths, int64_t n_paths, int64_t ld, int32_t n_dates, double* h_moments, hipStream_t s, const char* who, bool name_job)
+{
+    if (ld < n_paths) MCX_FAIL(h, -2, "%s: ld < n_paths", who);
+    const int K = b->n_basis, NM = (2 * K - 1) + K, count = (1 + NP) * NM;
+    std::vector<KTLJob> jobs((size_t)n_jobs);
+    for (int j = 0; j < n_jobs; ++j)
+        if (int rc = ktl_check_job(h, b, h_jobs[j], who, &jobs[j])) {
+            if (name_job) h->err = "job " + std::to_string(j) + ": " + h->err;
+            return rc;
+        }
+    if (K < 1 || K > 4) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: basis size %d has no instantiation", who, K);
+    const size_t out_bytes = sizeof(double) * (size_t)n_jobs * count;
+    if (n_paths <= 0) { memset(h_moments, 0, out_bytes); return 0; }
+    const int tiles = mcx_grid_for(n_paths, MCX_BLOCK, 2 * h->n_cu);       // of every job, whatever the split
+    const size_t job_bytes = sizeof(double) * (size_t)tiles * count;
+    if (job_bytes > h->ws_bytes) MCX_FAIL(h, -2, "%s: workspace too small", who);
+    size_t per_launch = ktl_partial_cap(h) / job_bytes;
+    if (per_launch < 1) per_launch = 1;
+    if (per_launch > (size_t)KTL_MAX_LAUNCH_JOBS) per_launch = KTL_MAX_LAUNCH_JOBS;
+    KTLBatchArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b)) return rc;
+    const KTLJob* d_jobs = (const KTLJob*)mcx_upload_table(h, 1, jobs.data(), sizeof(KTLJob) * jobs.size(), s);
+    double* d_out = (double*)mcx_scratch(h, 3, out_bytes);
+    if (!d_jobs || !d_out) return -100;
+    a.partials = h->d_ws;
+    int rc = 0;
+    for (size_t j0 = 0; j0 < (size_t)n_jobs && rc == 0; j0 += per_launch) {
+        const size_t nj = std::min(per_launch, (size_t)n_jobs - j0);
+        a.jobs = d_jobs + j0;
+        MCX_DISPATCH(KK, K, 4, hipLaunchKernelGGL((kt_lsm_batch<KK>), dim3((unsigned)tiles, (unsigned)nj), dim3(MCX_BLOCK), 0, s, a));
+        rc = mcx_sum_partials(h, h->d_ws, (int)nj, tiles, count, d_out + j0 * count, s);
+    }
+    // the stream is drained before returning, also after a failed launch; h_moments is written by the one copy only
+    hipError_t err = rc == 0 ? hipMemcpyAsync(h_moments, d_out, out_bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    const hipError_t sync = hipStreamSynchronize(s);
+    if (rc) return rc;
+    MCX_HIP(h, err);
+    MCX_HIP(h, sync);
+    return 0;
+}
+
+// the row tables of a metric call (exposure row; delayed row, or none) into its kernel arguments: false + handle error on failure
+template <class Args>
+bool kt_upload_rows(mcx_handle* h, const int32_t* h_rows, const int32_t* h_delayed, int32_t n, Args* a, hipStream_t s)
+{
+    a->rows = (const int32_t*)mcx_upload_table(h, 0, h_rows, sizeof(int32_t) * (size_t)n, s);
+    a->delayed = h_delayed ? (const int32_t*)mcx_upload_table(h, 1, h_delayed, sizeof(int32_t) * (size_t)n, s) : nullptr;
+    return a->rows && (a->delayed || !h_delayed);
+}
+
 }  // namespace
 
 extern "C" int mcx_tangent_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
@@ -784,25 +736,19 @@ extern "C" int mcx_tangent_paths(mcx_handle* h, const mcx_sim* sim, const double
             MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_paths: slot %d: model kind %d has no tangent step", s, kd);
     }
     if (sd.n_z != sd.n_slots) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_paths: one normal per slot expected");
+    if (sd.n_slots < 1 || sd.n_slots > 4) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_paths: %d slots have no instantiation", sd.n_slots);
     hipStream_t s = (hipStream_t)stream;
-    DevBuf dslot, dinit, daux;
-    MCX_HIP(h, dslot.upload(h_dslot, sizeof(double) * (size_t)sd.n_slots * MCX_SLOT_NPARAM * NP, s));
-    MCX_HIP(h, dinit.upload(h_dinit, sizeof(double) * (size_t)sd.n_state * NP, s));
-    MCX_HIP(h, daux.upload(h_daux, sizeof(double) * (size_t)sd.n_steps * sd.n_slots * MCX_AUX * NP, s));
     KTPArgs a;
     memset(&a, 0, sizeof(a));
     mcx_fill_k1_args(sim, seed, path_offset, n_paths, ld, d_paths, d_inject_z, nullptr, &a.k1);
-    a.dslot = (const double*)dslot.p; a.dinit = (const double*)dinit.p; a.daux = (const double*)daux.p; a.dpaths = d_dpaths;
-    a.pstride = (int64_t)sd.n_dates * sd.n_state * ld; a.n_slots = sd.n_slots;
+    a.dslot = (const double*)mcx_upload_table(h, 0, h_dslot, sizeof(double) * (size_t)sd.n_slots * MCX_SLOT_NPARAM * NP, s);
+    a.dinit = (const double*)mcx_upload_table(h, 1, h_dinit, sizeof(double) * (size_t)sd.n_state * NP, s);
+    a.daux = (const double*)mcx_upload_table(h, 2, h_daux, sizeof(double) * (size_t)sd.n_steps * sd.n_slots * MCX_AUX * NP, s);
+    if (!a.dslot || !a.dinit || !a.daux) return -100;
+    a.dpaths = d_dpaths; a.pstride = (int64_t)sd.n_dates * sd.n_state * ld; a.n_slots = sd.n_slots;
     const int grid = (int)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK);
     const bool inj = d_inject_z != nullptr;
-    switch (sd.n_slots) {
-    case 1: launch_ktp<1, 1>(a, grid, inj, s); break;
-    case 2: launch_ktp<2, 2>(a, grid, inj, s); break;
-    case 3: launch_ktp<3, 3>(a, grid, inj, s); break;
-    case 4: launch_ktp<4, 4>(a, grid, inj, s); break;
-    default: MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_paths: %d slots have no instantiation", sd.n_slots);
-    }
+    MCX_DISPATCH(NS, sd.n_slots, 4, launch_ktp<NS, NS>(a, grid, inj, s));
     MCX_HIP(h, hipGetLastError());
     MCX_HIP(h, hipStreamSynchronize(s));
     return 0;
@@ -813,40 +759,10 @@ extern "C" int mcx_tangent_lsm(mcx_handle* h, const mcx_book* b, int32_t product
                                int64_t n_paths, int64_t ld, int32_t n_dates, double* h_moments, void* stream)
 {
     if (!h || !b || !d_datoms || !d_paths || !d_dpaths || !h_moments) return -1;
-    KTLArgs a;
-    memset(&a, 0, sizeof(a));
-    if (int rc = ktl_check_job(h, b, product, first_event, num_atom, x_atom, shift, scale, "mcx_tangent_lsm", &a.job)) return rc;
-    const int K = b->n_basis, NM = (2 * K - 1) + K;
-    if (n_paths <= 0) { memset(h_moments, 0, sizeof(double) * (size_t)(1 + NP) * NM); return 0; }
-    hipStream_t s = (hipStream_t)stream;
-    DevBuf ev_ids, term_atom;
-    if (int rc = upload_ids(h, b, ev_ids, term_atom, s)) return rc;
-    const int grid = mcx_grid_for(n_paths, MCX_BLOCK, 2 * h->n_cu);
-    const int count = (1 + NP) * NM;
-    if ((size_t)(grid + 1) * count * sizeof(double) > h->ws_bytes || (size_t)count * sizeof(double) > h->pinned_bytes)
-        MCX_FAIL(h, -2, "mcx_tangent_lsm: workspace too small");
-    fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b);
-    a.ev_ids = (const KTEventIds*)ev_ids.p; a.term_atom = (const int32_t*)term_atom.p;
-    a.partials = h->d_ws;
-    switch (K) {
-    case 1: hipLaunchKernelGGL((kt_lsm<1>), dim3(grid), dim3(MCX_BLOCK), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((kt_lsm<2>), dim3(grid), dim3(MCX_BLOCK), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((kt_lsm<3>), dim3(grid), dim3(MCX_BLOCK), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((kt_lsm<4>), dim3(grid), dim3(MCX_BLOCK), 0, s, a); break;
-    default: MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_lsm: basis size %d has no instantiation", K);
-    }
-    MCX_HIP(h, hipGetLastError());
-    double* d_out = h->d_ws + (size_t)grid * count;
-    hipLaunchKernelGGL(kt_sum_partials, dim3((count + 63) / 64), dim3(64), 0, s, h->d_ws, count, grid, d_out);
-    MCX_HIP(h, hipGetLastError());
-    MCX_HIP(h, hipMemcpyAsync(h->h_pinned, d_out, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, s));
-    MCX_HIP(h, hipStreamSynchronize(s));
-    memcpy(h_moments, h->h_pinned, sizeof(double) * (size_t)count);
-    return 0;
+    const mcx_tangent_lsm_job job = {product, first_event, num_atom, x_atom, shift, scale};
+    return ktl_run(h, b, &job, 1, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, h_moments, (hipStream_t)stream, "mcx_tangent_lsm", false);
 }
 
-// every job of the table in launches of grid (tiles, jobs): the id tables, the job table and the result block exist once per call;
-// partials [job][tile][1+NP][NM] in the workspace, as many whole jobs per launch as fit; ONE synchronisation, at the end
 extern "C" int mcx_tangent_lsm_batch(mcx_handle* h, const mcx_book* b, const mcx_tangent_lsm_job* h_jobs, int32_t n_jobs,
                                      const double* d_datoms, const double* d_paths, const double* d_dpaths, int64_t n_paths, int64_t ld,
                                      int32_t n_dates, double* h_moments, void* stream)
@@ -854,57 +770,7 @@ extern "C" int mcx_tangent_lsm_batch(mcx_handle* h, const mcx_book* b, const mcx
     if (!h || !b || n_jobs < 0) return -1;
     if (n_jobs == 0) return 0;
     if (!h_jobs || !d_datoms || !d_paths || !d_dpaths || !h_moments) return -1;
-    if (ld < n_paths) MCX_FAIL(h, -2, "mcx_tangent_lsm_batch: ld < n_paths");
-    const int K = b->n_basis, NM = (2 * K - 1) + K, count = (1 + NP) * NM;
-    std::vector<KTLJob> jobs((size_t)n_jobs);
-    for (int j = 0; j < n_jobs; ++j) {
-        const mcx_tangent_lsm_job& q = h_jobs[j];
-        if (int rc = ktl_check_job(h, b, q.product, q.first_event, q.num_atom, q.x_atom, q.shift, q.scale, "mcx_tangent_lsm_batch", &jobs[j])) {
-            h->err = "job " + std::to_string(j) + ": " + h->err;
-            return rc;
-        }
-    }
-    if (K < 1 || K > 4) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_lsm_batch: basis size %d has no instantiation", K);
-    const size_t out_bytes = sizeof(double) * (size_t)n_jobs * count;
-    if (n_paths <= 0) { memset(h_moments, 0, out_bytes); return 0; }
-    const int tiles = mcx_grid_for(n_paths, MCX_BLOCK, 2 * h->n_cu);       // of every job, whatever the split (mcx_tangent_lsm's)
-    const size_t job_bytes = sizeof(double) * (size_t)tiles * count;
-    if (job_bytes > h->ws_bytes) MCX_FAIL(h, -2, "mcx_tangent_lsm_batch: workspace too small");
-    size_t per_launch = ktl_partial_cap(h) / job_bytes;
-    if (per_launch < 1) per_launch = 1;
-    if (per_launch > (size_t)KTL_MAX_LAUNCH_JOBS) per_launch = KTL_MAX_LAUNCH_JOBS;
-    hipStream_t s = (hipStream_t)stream;
-    HostIds host_ids;
-    DevBuf ev_ids, term_atom, d_jobs, d_out;
-    if (int rc = upload_ids_async(h, b, host_ids, ev_ids, term_atom, s)) return rc;
-    MCX_HIP(h, d_jobs.upload(jobs.data(), sizeof(KTLJob) * jobs.size(), s));
-    MCX_HIP(h, hipMalloc(&d_out.p, out_bytes));
-    KTLBatchArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b);
-    a.ev_ids = (const KTEventIds*)ev_ids.p; a.term_atom = (const int32_t*)term_atom.p; a.partials = h->d_ws;
-    hipError_t err = hipSuccess;
-    for (size_t j0 = 0; j0 < (size_t)n_jobs && err == hipSuccess; j0 += per_launch) {
-        const size_t nj = std::min(per_launch, (size_t)n_jobs - j0);
-        a.jobs = (const KTLJob*)d_jobs.p + j0;
-        const dim3 grid((unsigned)tiles, (unsigned)nj);
-        switch (K) {
-        case 1: hipLaunchKernelGGL((kt_lsm_batch<1>), grid, dim3(MCX_BLOCK), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((kt_lsm_batch<2>), grid, dim3(MCX_BLOCK), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((kt_lsm_batch<3>), grid, dim3(MCX_BLOCK), 0, s, a); break;
-        default: hipLaunchKernelGGL((kt_lsm_batch<4>), grid, dim3(MCX_BLOCK), 0, s, a); break;
-        }
-        const int64_t total = (int64_t)nj * count;
-        hipLaunchKernelGGL(kt_sum_partials_batch, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, h->d_ws, count, tiles, total,
-                           (double*)d_out.p + j0 * count);
-        err = hipGetLastError();
-    }
-    // the stream is drained before the scoped buffers go, also after a failed launch; h_moments is written by the one copy only
-    if (err == hipSuccess) err = hipMemcpyAsync(h_moments, d_out.p, out_bytes, hipMemcpyDeviceToHost, s);
-    const hipError_t sync = hipStreamSynchronize(s);
-    MCX_HIP(h, err);
-    MCX_HIP(h, sync);
-    return 0;
+    return ktl_run(h, b, h_jobs, n_jobs, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, h_moments, (hipStream_t)stream, "mcx_tangent_lsm_batch", true);
 }
 
 extern "C" int mcx_tangent_lsm_step(mcx_handle* h, const mcx_book* b, int32_t product, int32_t roll_begin, int32_t roll_end, int32_t num_atom,
@@ -912,38 +778,26 @@ extern "C" int mcx_tangent_lsm_step(mcx_handle* h, const mcx_book* b, int32_t pr
                                     const double* d_dpaths, int64_t n_paths, int64_t ld, int32_t n_dates, double* d_W, double* d_dW,
                                     int64_t ld_w, double* h_moments, void* stream)
 {
+    const char* who = "mcx_tangent_lsm_step";
     if (!h || !b || !d_datoms || !d_paths || !d_dpaths || !d_W || !d_dW || !h_moments) return -1;
-    if (product < 0 || product >= b->n_products) MCX_FAIL(h, -2, "mcx_tangent_lsm_step: product out of range");
+    if (product < 0 || product >= b->n_products) MCX_FAIL(h, -2, "%s: product out of range", who);
     const DevProduct& pr = b->h_products[product];
     const int n_cf = pr.cf_end - pr.cf_begin;
-    if (roll_begin < 0 || roll_end < roll_begin || roll_end > n_cf) MCX_FAIL(h, -2, "mcx_tangent_lsm_step: roll window out of range");
-    if (ld < n_paths || ld_w < n_paths) MCX_FAIL(h, -2, "mcx_tangent_lsm_step: leading dimension < n_paths");
-    for (int q = pr.cf_begin + roll_begin; q < pr.cf_begin + roll_end; ++q) {
-        const DevEvent& e = b->h_events[q];
-        const bool ok = e.kind == MCX_EV_CASHFLOW || (e.kind == MCX_EV_OPTION && e.aux[0] == 0.0) ||
-                        (e.kind == MCX_EV_EXERCISE && (e.aux[0] == 0.0 || e.aux[0] == 1.0));
-        if (!ok) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_lsm_step: event %d (kind %d, mode %g) has no tangent form", q, e.kind, e.aux[0]);
-        if (e.kind != MCX_EV_CASHFLOW)
-            for (int j = e.term_begin; j < e.term_end; ++j)
-                if (b->h_terms[j].den >= 0) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_lsm_step: option over per-term denominators");
-    }
-    if (num_atom < 0 || num_atom >= b->n_atoms || x_atom < 0 || x_atom >= b->n_atoms) MCX_FAIL(h, -2, "mcx_tangent_lsm_step: atom out of range");
-    const int K = b->n_basis, S = pr.n_states, NM = (2 * K - 1) + S * K;
-    if (n_paths <= 0) { memset(h_moments, 0, sizeof(double) * (size_t)(1 + NP) * NM); return 0; }
+    if (roll_begin < 0 || roll_end < roll_begin || roll_end > n_cf) MCX_FAIL(h, -2, "%s: roll window out of range", who);
+    if (ld < n_paths || ld_w < n_paths) MCX_FAIL(h, -2, "%s: leading dimension < n_paths", who);
+    if (int rc = kt_check_cash_events(h, b, pr.cf_begin + roll_begin, pr.cf_begin + roll_end, KT_CASH_KINDS | 1u << MCX_EV_EXERCISE, who)) return rc;
+    if (num_atom < 0 || num_atom >= b->n_atoms || x_atom < 0 || x_atom >= b->n_atoms) MCX_FAIL(h, -2, "%s: atom out of range", who);
+    const int K = b->n_basis, S = pr.n_states, NM = (2 * K - 1) + S * K, count = (1 + NP) * NM;
+    if (n_paths <= 0) { memset(h_moments, 0, sizeof(double) * (size_t)count); return 0; }
     hipStream_t s = (hipStream_t)stream;
-    DevBuf ev_ids, term_atom;
-    if (int rc = upload_ids(h, b, ev_ids, term_atom, s)) return rc;
     const int grid = mcx_grid_for(n_paths, MCX_BLOCK, 2 * h->n_cu);
-    const int count = (1 + NP) * NM;
-    if ((size_t)(grid + 1) * count * sizeof(double) > h->ws_bytes || (size_t)count * sizeof(double) > h->pinned_bytes)
-        MCX_FAIL(h, -2, "mcx_tangent_lsm_step: workspace too small");
     KTSArgs a;
     memset(&a, 0, sizeof(a));
-    fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b);
-    a.ev_ids = (const KTEventIds*)ev_ids.p; a.term_atom = (const int32_t*)term_atom.p; a.coeffs = b->d_coeffs;
-    a.W = d_W; a.dW = d_dW; a.ld_w = ld_w; a.w_stride = (int64_t)S * ld_w;
+    if (int rc = fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b)) return rc;
+    if (!(a.partials = mcx_partials_ws(h, who, grid, count))) return -2;
+    a.coeffs = b->d_coeffs; a.W = d_W; a.dW = d_dW; a.ld_w = ld_w; a.w_stride = (int64_t)S * ld_w;
     a.num = mcx_flat_atom(b->h_atoms[num_atom]); a.x = mcx_flat_atom(b->h_atoms[x_atom]); a.num_id = num_atom; a.x_id = x_atom; a.shift = shift; a.scale = scale;
-    a.partials = h->d_ws; a.roll_begin = pr.cf_begin + roll_begin; a.roll_end = pr.cf_begin + roll_end;
+    a.roll_begin = pr.cf_begin + roll_begin; a.roll_end = pr.cf_begin + roll_end;
     bool launched = true;
 #define MCX_KTS(KK, SS) hipLaunchKernelGGL((kt_lsm_step<KK, SS>), dim3(grid), dim3(MCX_BLOCK), 0, s, a)
     switch (K * 16 + S) {
@@ -953,15 +807,9 @@ extern "C" int mcx_tangent_lsm_step(mcx_handle* h, const mcx_book* b, int32_t pr
     default: launched = false; break;
     }
 #undef MCX_KTS
-    if (!launched) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_lsm_step: (basis=%d, states=%d) has no instantiation", K, S);
+    if (!launched) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: (basis=%d, states=%d) has no instantiation", who, K, S);
     MCX_HIP(h, hipGetLastError());
-    double* d_out = h->d_ws + (size_t)grid * count;
-    hipLaunchKernelGGL(kt_sum_partials, dim3((count + 63) / 64), dim3(64), 0, s, h->d_ws, count, grid, d_out);
-    MCX_HIP(h, hipGetLastError());
-    MCX_HIP(h, hipMemcpyAsync(h->h_pinned, d_out, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, s));
-    MCX_HIP(h, hipStreamSynchronize(s));
-    memcpy(h_moments, h->h_pinned, sizeof(double) * (size_t)count);
-    return 0;
+    return mcx_partials_to_host(h, grid, count, h_moments, s);
 }
 
 extern "C" int mcx_tangent_eval(mcx_handle* h, const mcx_book* b, const double* d_datoms, const double* d_coeffs, const double* d_dcoeffs,
@@ -972,30 +820,25 @@ extern "C" int mcx_tangent_eval(mcx_handle* h, const mcx_book* b, const double* 
     if (n_paths <= 0) return 0;
     for (int p = 0; p < b->n_products; ++p) {
         const DevProduct& pr = b->h_products[p];
+        const unsigned allowed = KT_CASH_KINDS | 1u << MCX_EV_EXPO_POLY | (h_ev_param ? 1u << MCX_EV_EXPO_BS : 0u) |
+                                 (pr.n_states > 1 ? 1u << MCX_EV_EXERCISE : 0u);
         for (int q = pr.ev_begin; q < pr.ev_end; ++q) {
             const DevEvent& e = b->h_events[q];
-            const bool ok = e.kind == MCX_EV_CASHFLOW || (e.kind == MCX_EV_OPTION && e.aux[0] == 0.0) || e.kind == MCX_EV_EXPO_POLY ||
-                            (e.kind == MCX_EV_EXPO_BS && h_ev_param != nullptr) ||
-                            (e.kind == MCX_EV_EXERCISE && pr.n_states > 1 && (e.aux[0] == 0.0 || e.aux[0] == 1.0));
-            if (!ok) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_eval: event %d (kind %d) has no tangent form", q, e.kind);
-            if (e.kind == MCX_EV_OPTION || e.kind == MCX_EV_EXERCISE)
-                for (int j = e.term_begin; j < e.term_end; ++j)
-                    if (b->h_terms[j].den >= 0) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_eval: option over per-term denominators");
+            const KTForm f = kt_tangent_form(b, e, allowed);
+            if (f == KT_FORM_NONE) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_eval: event %d (kind %d) has no tangent form", q, e.kind);
+            if (f == KT_FORM_TERM_DEN) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_eval: option over per-term denominators");
         }
     }
     hipStream_t s = (hipStream_t)stream;
-    DevBuf ev_ids, term_atom, ev_param;
-    if (int rc = upload_ids(h, b, ev_ids, term_atom, s)) return rc;
-    if (h_ev_param) MCX_HIP(h, ev_param.upload(h_ev_param, sizeof(int32_t) * 2 * (size_t)b->n_events, s));
+    KTEArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b)) return rc;
+    if (h_ev_param && !(a.ev_param = (const int32_t*)mcx_upload_table(h, 1, h_ev_param, sizeof(int32_t) * 2 * (size_t)b->n_events, s))) return -100;
     const int n_rows = b->n_expo_rows > 0 ? b->n_expo_rows : 1;
     MCX_HIP(h, hipMemsetAsync(d_cfs, 0, sizeof(double) * (size_t)(1 + NP) * b->n_netting_sets * ld, s));
     MCX_HIP(h, hipMemsetAsync(d_expo, 0, sizeof(double) * (size_t)(1 + NP) * b->n_netting_sets * n_rows * ld, s));
-    KTEArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b);
-    a.ev_ids = (const KTEventIds*)ev_ids.p; a.term_atom = (const int32_t*)term_atom.p; a.products = b->d_products;
-    a.coeffs = d_coeffs; a.dcoeffs = d_dcoeffs; a.cfs = d_cfs; a.expo = d_expo; a.n_products = b->n_products;
-    a.n_ns = b->n_netting_sets; a.n_rows = n_rows; a.ev_param = h_ev_param ? (const int32_t*)ev_param.p : nullptr;
+    a.products = b->d_products; a.coeffs = d_coeffs; a.dcoeffs = d_dcoeffs; a.cfs = d_cfs; a.expo = d_expo; a.n_products = b->n_products;
+    a.n_ns = b->n_netting_sets; a.n_rows = n_rows;
     hipLaunchKernelGGL(kt_eval, dim3((unsigned)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK)), dim3(MCX_BLOCK), 0, s, a);
     MCX_HIP(h, hipGetLastError());
     MCX_HIP(h, hipStreamSynchronize(s));
@@ -1013,17 +856,15 @@ extern "C" int mcx_tangent_cva(mcx_handle* h, const mcx_book* b, const double* d
     for (int m = 0; m < n_dates_metric - 1; ++m)
         if (h_surv[m] < 0 || h_surv[m] >= b->n_atoms || h_cond[m] < 0 || h_cond[m] >= b->n_atoms) MCX_FAIL(h, -2, "mcx_tangent_cva: atom out of range");
     hipStream_t s = (hipStream_t)stream;
-    DevBuf rows, surv, cond, delayed;
-    MCX_HIP(h, rows.upload(h_rows, sizeof(int32_t) * (size_t)n_dates_metric, s));
-    if (h_delayed) MCX_HIP(h, delayed.upload(h_delayed, sizeof(int32_t) * (size_t)n_dates_metric, s));
-    MCX_HIP(h, surv.upload(h_surv, sizeof(int32_t) * (size_t)(n_dates_metric - 1), s));
-    MCX_HIP(h, cond.upload(h_cond, sizeof(int32_t) * (size_t)(n_dates_metric - 1), s));
     KTCArgs a;
     memset(&a, 0, sizeof(a));
-    fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b);
-    a.expo = d_expo_ns; a.rows = (const int32_t*)rows.p; a.surv = (const int32_t*)surv.p; a.cond = (const int32_t*)cond.p; a.out = d_out;
-    a.ex_stride = expo_tangent_stride; a.threshold = threshold; a.lgd = 1.0 - recovery; a.n_dates = n_dates_metric;
-    a.delayed = h_delayed ? (const int32_t*)delayed.p : nullptr; a.collateralized = collateralized;
+    if (int rc = fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b)) return rc;
+    if (!kt_upload_rows(h, h_rows, h_delayed, n_dates_metric, &a, s)) return -100;
+    a.surv = (const int32_t*)mcx_upload_table(h, 2, h_surv, sizeof(int32_t) * (size_t)(n_dates_metric - 1), s);
+    a.cond = (const int32_t*)mcx_upload_table(h, 3, h_cond, sizeof(int32_t) * (size_t)(n_dates_metric - 1), s);
+    if (!a.surv || !a.cond) return -100;
+    a.expo = d_expo_ns; a.out = d_out; a.ex_stride = expo_tangent_stride; a.threshold = threshold; a.lgd = 1.0 - recovery;
+    a.n_dates = n_dates_metric; a.collateralized = collateralized;
     hipLaunchKernelGGL(kt_cva, dim3((unsigned)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK)), dim3(MCX_BLOCK), 0, s, a);
     MCX_HIP(h, hipGetLastError());
     MCX_HIP(h, hipStreamSynchronize(s));
@@ -1041,17 +882,14 @@ extern "C" int mcx_tangent_profiles(mcx_handle* h, const int32_t* h_rows, const 
     hipStream_t s = (hipStream_t)stream;
     const int grid = mcx_grid_for(n_paths, MCX_BLOCK, 64);
     std::vector<double> part((size_t)n_dates_metric * grid * 2 * NP);
-    DevBuf rows, d_part, delayed;
-    MCX_HIP(h, rows.upload(h_rows, sizeof(int32_t) * (size_t)n_dates_metric, s));
-    if (h_delayed) MCX_HIP(h, delayed.upload(h_delayed, sizeof(int32_t) * (size_t)n_dates_metric, s));
-    MCX_HIP(h, hipMalloc(&d_part.p, sizeof(double) * part.size()));
     KTFArgs a;
-    a.expo = d_expo_ns; a.rows = (const int32_t*)rows.p; a.delayed = h_delayed ? (const int32_t*)delayed.p : nullptr;
-    a.collateralized = collateralized; a.pad = 0; a.partials = (double*)d_part.p; a.ex_stride = expo_tangent_stride;
-    a.n = n_paths; a.ld = ld; a.threshold = threshold;
+    memset(&a, 0, sizeof(a));
+    if (!kt_upload_rows(h, h_rows, h_delayed, n_dates_metric, &a, s)) return -100;
+    if (!(a.partials = (double*)mcx_scratch(h, 2, sizeof(double) * part.size()))) return -100;
+    a.expo = d_expo_ns; a.collateralized = collateralized; a.ex_stride = expo_tangent_stride; a.n = n_paths; a.ld = ld; a.threshold = threshold;
     hipLaunchKernelGGL(kt_profiles, dim3(grid, n_dates_metric), dim3(MCX_BLOCK), 0, s, a);
     MCX_HIP(h, hipGetLastError());
-    MCX_HIP(h, hipMemcpyAsync(part.data(), d_part.p, sizeof(double) * part.size(), hipMemcpyDeviceToHost, s));
+    MCX_HIP(h, hipMemcpyAsync(part.data(), a.partials, sizeof(double) * part.size(), hipMemcpyDeviceToHost, s));
     MCX_HIP(h, hipStreamSynchronize(s));
     for (int m = 0; m < n_dates_metric; ++m)
         for (int b = 0; b < grid; ++b)
@@ -1068,21 +906,21 @@ extern "C" int mcx_tangent_pick(mcx_handle* h, const int32_t* h_rows, const int3
     for (int m = 0; m < n_dates_metric; ++m) { h_out[(size_t)m * (1 + NP)] = -1.0; for (int q = 0; q < NP; ++q) h_out[(size_t)m * (1 + NP) + 1 + q] = 0.0; }
     if (n_paths <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    DevBuf rows, delayed, targets, first, out;
-    MCX_HIP(h, rows.upload(h_rows, sizeof(int32_t) * (size_t)n_dates_metric, s));
-    if (h_delayed) MCX_HIP(h, delayed.upload(h_delayed, sizeof(int32_t) * (size_t)n_dates_metric, s));
-    MCX_HIP(h, targets.upload(h_targets, sizeof(double) * (size_t)n_dates_metric, s));
-    MCX_HIP(h, hipMalloc(&first.p, sizeof(unsigned long long) * (size_t)n_dates_metric));
-    MCX_HIP(h, hipMemsetAsync(first.p, 0xFF, sizeof(unsigned long long) * (size_t)n_dates_metric, s));
-    MCX_HIP(h, hipMalloc(&out.p, sizeof(double) * (size_t)n_dates_metric * (1 + NP)));
     KTQArgs a;
-    a.expo = d_expo_ns; a.rows = (const int32_t*)rows.p; a.delayed = h_delayed ? (const int32_t*)delayed.p : nullptr;
-    a.targets = (const double*)targets.p; a.first = (unsigned long long*)first.p; a.out = (double*)out.p;
-    a.ex_stride = expo_tangent_stride; a.n = n_paths; a.ld = ld; a.threshold = threshold; a.collateralized = collateralized; a.pad = 0;
+    memset(&a, 0, sizeof(a));
+    if (!kt_upload_rows(h, h_rows, h_delayed, n_dates_metric, &a, s)) return -100;
+    a.targets = (const double*)mcx_upload_table(h, 2, h_targets, sizeof(double) * (size_t)n_dates_metric, s);
+    // results, slot 3: out [n_dates][1+NP], then first [n_dates]
+    const size_t out_bytes = sizeof(double) * (size_t)n_dates_metric * (1 + NP), first_bytes = sizeof(unsigned long long) * (size_t)n_dates_metric;
+    a.out = (double*)mcx_scratch(h, 3, out_bytes + first_bytes);
+    if (!a.targets || !a.out) return -100;
+    a.first = (unsigned long long*)(a.out + (size_t)n_dates_metric * (1 + NP));
+    MCX_HIP(h, hipMemsetAsync(a.first, 0xFF, first_bytes, s));
+    a.expo = d_expo_ns; a.ex_stride = expo_tangent_stride; a.n = n_paths; a.ld = ld; a.threshold = threshold; a.collateralized = collateralized;
     hipLaunchKernelGGL(kt_pick_find, dim3(mcx_grid_for(n_paths, MCX_BLOCK, 256), n_dates_metric), dim3(MCX_BLOCK), 0, s, a);
     hipLaunchKernelGGL(kt_pick_read, dim3((n_dates_metric + 63) / 64), dim3(64), 0, s, a, n_dates_metric);
     MCX_HIP(h, hipGetLastError());
-    MCX_HIP(h, hipMemcpyAsync(h_out, out.p, sizeof(double) * (size_t)n_dates_metric * (1 + NP), hipMemcpyDeviceToHost, s));
+    MCX_HIP(h, hipMemcpyAsync(h_out, a.out, out_bytes, hipMemcpyDeviceToHost, s));
     MCX_HIP(h, hipStreamSynchronize(s));
     return 0;
 }

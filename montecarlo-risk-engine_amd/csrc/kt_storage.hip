@@ -192,15 +192,6 @@ __global__ __launch_bounds__(MCX_BLOCK) void kts_step(const KTSStepArgs a)
     }
 }
 
-__global__ void kts_sum_partials(const double* __restrict__ partials, int count, int n_blocks, double* __restrict__ out)
-{
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= count) return;
-    double s = 0.0;
-    for (int b = 0; b < n_blocks; ++b) s += partials[(int64_t)b * count + j];
-    out[j] = s;
-}
-
 // ---- main simulation ---------------------------------------------------------------------------------------------------------
 struct KTSEvalArgs {
     KTSBook b;
@@ -393,17 +384,6 @@ __global__ __launch_bounds__(MCX_BLOCK) void kts_paths(const KTSPathArgs a)
     }
 }
 
-// a call's host table on the device: the handle's staging ring, or (a table larger than a quarter of the ring) one of the
-// handle's scratch buffers — no allocation per call
-const void* kts_upload(mcx_handle* h, int slot, const void* src, size_t bytes, hipStream_t s)
-{
-    static const double none = 0.0;
-    if (bytes == 0) return mcx_stage_small(h, &none, sizeof(none), s);
-    if (bytes <= h->small_bytes / 4) return mcx_stage_small(h, src, bytes, s);
-    void* big = mcx_scratch(h, slot, bytes);
-    return big ? mcx_upload_call_data(h, src, bytes, big, s) : nullptr;
-}
-
 void kts_fill_book(const mcx_book* b, const double* d_datoms, const double* d_paths, const double* d_dpaths, int64_t ld, int32_t n_dates,
                    KTSBook* out)
 {
@@ -440,12 +420,11 @@ extern "C" int mcx_tangent_storage_lsm_step(mcx_handle* h, const mcx_book* b, co
     if (n_paths <= 0) { memset(h_moments, 0, sizeof(double) * (size_t)count); return 0; }
     hipStream_t s = (hipStream_t)stream;
     const int grid = mcx_grid_for(n_paths, MCX_BLOCK, 4 * h->n_cu);
-    if ((size_t)(grid + 1) * count * sizeof(double) > h->ws_bytes || (size_t)count * sizeof(double) > h->pinned_bytes)
-        MCX_FAIL(h, -2, "%s: workspace too small", who);
     KTSStepArgs a;
     memset(&a, 0, sizeof(a));
     kts_fill_book(b, d_datoms, d_paths, d_dpaths, ld, n_dates, &a.b);
-    a.W_old = d_W_old; a.dW_old = d_dW_old; a.W_new = d_W_new; a.dW_new = d_dW_new; a.partials = h->d_ws;
+    a.W_old = d_W_old; a.dW_old = d_dW_old; a.W_new = d_W_new; a.dW_new = d_dW_new;
+    if (!(a.partials = mcx_partials_ws(h, who, grid, count))) return -2;
     k6_set_atom(b, num_atom, a.num); k6_set_atom(b, x_atom, a.x); a.rnum = a.num; a.rx = a.x;
     a.shift = shift; a.scale = scale; a.n = n_paths; a.ld_w = ld_w; a.w_stride = (int64_t)S * ld_w; a.S = S;
     a.f32_cache = (flags & MCX_LSM_F32_CACHE) ? 1 : 0;
@@ -459,13 +438,7 @@ extern "C" int mcx_tangent_storage_lsm_step(mcx_handle* h, const mcx_book* b, co
     }
     K6_DISPATCH(K, 4, hipLaunchKernelGGL((kts_step<KK>), dim3(grid), dim3(MCX_BLOCK), 0, s, a));
     MCX_HIP(h, hipGetLastError());
-    double* d_out = h->d_ws + (size_t)grid * count;
-    hipLaunchKernelGGL(kts_sum_partials, dim3((count + 63) / 64), dim3(64), 0, s, h->d_ws, count, grid, d_out);
-    MCX_HIP(h, hipGetLastError());
-    MCX_HIP(h, hipMemcpyAsync(h->h_pinned, d_out, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, s));
-    MCX_HIP(h, hipStreamSynchronize(s));
-    memcpy(h_moments, h->h_pinned, sizeof(double) * (size_t)count);
-    return 0;
+    return mcx_partials_to_host(h, grid, count, h_moments, s);
 }
 
 extern "C" int mcx_tangent_storage_eval(mcx_handle* h, const mcx_book* b, const mcx_storage_desc* desc, const mcx_storage_op* h_ops, int32_t n_ops,
@@ -496,8 +469,8 @@ extern "C" int mcx_tangent_storage_eval(mcx_handle* h, const mcx_book* b, const 
         k6_fill_date(b, desc->dates[j], dates[j]);
     }
     hipStream_t s = (hipStream_t)stream;
-    const void* d_dates = kts_upload(h, 0, dates.data(), sizeof(KTSDate) * dates.size(), s);
-    const void* d_ops = kts_upload(h, 1, h_ops, sizeof(mcx_storage_op) * (size_t)n_ops, s);
+    const void* d_dates = mcx_upload_table(h, 0, dates.data(), sizeof(KTSDate) * dates.size(), s);
+    const void* d_ops = mcx_upload_table(h, 1, h_ops, sizeof(mcx_storage_op) * (size_t)n_ops, s);
     if (!d_dates || !d_ops) return -100;
     KTSEvalArgs a;
     memset(&a, 0, sizeof(a));
@@ -533,10 +506,10 @@ extern "C" int mcx_tangent_paths_s2f(mcx_handle* h, const mcx_sim* sim, const do
         if (sp.chol_idx < 0 || sp.chol_idx >= sd.n_chol || sp.store_idx >= sd.n_dates) MCX_FAIL(h, -2, "%s: step %d out of range", who, k);
     }
     hipStream_t s = (hipStream_t)stream;
-    const void* dslot = kts_upload(h, 0, h_dslot, sizeof(double) * (size_t)MCX_SLOT_NPARAM * NP, s);
-    const void* dinit = kts_upload(h, 1, h_dinit, sizeof(double) * (size_t)3 * NP, s);
-    const void* daux = kts_upload(h, 2, h_daux, sizeof(double) * (size_t)sd.n_steps * MCX_AUX * NP, s);
-    const void* dchol = kts_upload(h, 3, h_dchol, sizeof(double) * (size_t)sd.n_chol * 4 * NP, s);
+    const void* dslot = mcx_upload_table(h, 0, h_dslot, sizeof(double) * (size_t)MCX_SLOT_NPARAM * NP, s);
+    const void* dinit = mcx_upload_table(h, 1, h_dinit, sizeof(double) * (size_t)3 * NP, s);
+    const void* daux = mcx_upload_table(h, 2, h_daux, sizeof(double) * (size_t)sd.n_steps * MCX_AUX * NP, s);
+    const void* dchol = mcx_upload_table(h, 3, h_dchol, sizeof(double) * (size_t)sd.n_chol * 4 * NP, s);
     if (!dslot || !dinit || !daux || !dchol) return -100;
     KTSPathArgs a;
     memset(&a, 0, sizeof(a));

@@ -208,6 +208,7 @@ extern "C" int mcx_book_create(mcx_handle* h, const mcx_book_desc* d, mcx_book**
     b->d_bridge = nullptr; b->d_bridge_inject = nullptr;
     b->ex_mode = 0; b->d_ex_bits = nullptr; b->ex_ld = 0;
     b->d_vpoly = nullptr; b->d_vcoef = nullptr;
+    b->d_event_ids = nullptr; b->d_term_atom = nullptr;
     b->h_event_vpoly.assign((size_t)d->n_events, -1);
     auto upload = [&](void** dst, const void* src, size_t bytes) -> bool {        // false: the error is in h->err; the caller frees
         hipError_t e = hipMalloc(dst, bytes ? bytes : 8);
@@ -235,6 +236,7 @@ extern "C" void mcx_book_destroy(mcx_book* b)
     hipFree(b->d_atoms); hipFree(b->d_terms); hipFree(b->d_events); hipFree(b->d_products); hipFree(b->d_coeffs);
     hipFree(b->d_bridge); hipFree(b->d_bridge_inject);
     hipFree(b->d_vpoly); hipFree(b->d_vcoef);
+    hipFree(b->d_event_ids); hipFree(b->d_term_atom);
     delete b;
 }
 
@@ -332,6 +334,32 @@ const void* mcx_upload_call_data(mcx_handle* h, const void* src, size_t bytes, v
     return fallback;
 }
 
+const void* mcx_upload_table(mcx_handle* h, int slot, const void* src, size_t bytes, hipStream_t s)
+{
+    static const double none = 0.0;
+    if (bytes == 0) return mcx_stage_small(h, &none, sizeof(none), s);
+    if (bytes <= h->small_bytes / 4) return mcx_stage_small(h, src, bytes, s);
+    void* big = mcx_scratch(h, slot, bytes);
+    return big ? mcx_upload_call_data(h, src, bytes, big, s) : nullptr;
+}
+
+int mcx_book_tangent_ids(mcx_handle* h, const mcx_book* b)
+{
+    if (b->d_event_ids && b->d_term_atom) return 0;
+    std::vector<DevEventIds> ids((size_t)b->n_events);
+    for (int q = 0; q < b->n_events; ++q) { ids[q].num = b->h_event_num_atom[q]; ids[q].x = b->h_event_x_atom[q]; }
+    const size_t ev_bytes = sizeof(DevEventIds) * ids.size(), ta_bytes = sizeof(int32_t) * b->h_term_atom.size();
+    if (!b->d_event_ids) {
+        MCX_HIP(h, hipMalloc((void**)&b->d_event_ids, ev_bytes ? ev_bytes : 8));
+        if (ev_bytes) MCX_HIP(h, hipMemcpy(b->d_event_ids, ids.data(), ev_bytes, hipMemcpyHostToDevice));
+    }
+    if (!b->d_term_atom) {
+        MCX_HIP(h, hipMalloc((void**)&b->d_term_atom, ta_bytes ? ta_bytes : 8));
+        if (ta_bytes) MCX_HIP(h, hipMemcpy(b->d_term_atom, b->h_term_atom.data(), ta_bytes, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
 int mcx_upload_unsec(mcx_handle* h, const mcx_unsecured_desc* u, DevUnsec* out, int32_t** d_tmp, hipStream_t s)
 {
     if (u->n_dates < 1 || u->n_dates > MCX_MAX_METRIC_DATES) MCX_FAIL(h, -2, "unsecured desc: n_dates %d out of range", u->n_dates);
@@ -372,7 +400,47 @@ __global__ void k_finish_acc(const double* __restrict__ partials, int n_records,
         out[r].n = n_paths; out[r].shift = shifts[r]; out[r].s1 = s1; out[r].s2 = s2;
     }
 }
+
+// partials [n_jobs][n_tiles][count] -> out [n_jobs][count]: every (job, entry) adds its tiles in ascending order
+__global__ void k_sum_partials(const double* __restrict__ partials, int count, int n_tiles, int64_t total, double* __restrict__ out)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const int64_t job = t / count;
+    const int e = (int)(t - job * count);
+    const double* __restrict__ p = partials + job * n_tiles * count + e;
+    double s = 0.0;
+    for (int b = 0; b < n_tiles; ++b) s += p[(int64_t)b * count];
+    out[t] = s;
+}
 }  // namespace
+
+int mcx_sum_partials(mcx_handle* h, const double* d_partials, int n_jobs, int n_tiles, int count, double* d_out, hipStream_t s)
+{
+    const int64_t total = (int64_t)n_jobs * count;
+    hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_partials, count, n_tiles, total, d_out);
+    MCX_HIP(h, hipGetLastError());
+    return 0;
+}
+
+double* mcx_partials_ws(mcx_handle* h, const char* who, int n_tiles, int count)
+{
+    if ((size_t)(n_tiles + 1) * count * sizeof(double) > h->ws_bytes || (size_t)count * sizeof(double) > h->pinned_bytes) {
+        h->err = std::string(who) + ": workspace too small";
+        return nullptr;
+    }
+    return h->d_ws;
+}
+
+int mcx_partials_to_host(mcx_handle* h, int n_tiles, int count, double* h_out, hipStream_t s)
+{
+    double* d_out = h->d_ws + (size_t)n_tiles * count;
+    if (int rc = mcx_sum_partials(h, h->d_ws, 1, n_tiles, count, d_out, s)) return rc;
+    MCX_HIP(h, hipMemcpyAsync(h->h_pinned, d_out, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, s));
+    MCX_HIP(h, hipStreamSynchronize(s));
+    memcpy(h_out, h->h_pinned, sizeof(double) * (size_t)count);
+    return 0;
+}
 
 int mcx_finish_acc(mcx_handle* h, const double* d_partials, int n_records, int n_blocks, double n_paths,
                    const double* d_shifts, mcx_acc* h_out, hipStream_t s)

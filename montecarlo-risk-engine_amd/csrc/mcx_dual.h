@@ -35,6 +35,37 @@ template <int P> __device__ __forceinline__ Dual<P> drcp_r(const Dual<P>& b, dou
 // torch.clamp(x, min=lo): gradient mask x >= lo
 template <int P> __device__ __forceinline__ Dual<P> dclamp_min(const Dual<P>& a, double lo) { Dual<P> r; const bool pass = a.v >= lo; r.v = a.v < lo ? lo : a.v;   /* (a NaN value stays NaN: torch.clamp) */ for (int j = 0; j < P; ++j) r.d[j] = pass ? a.d[j] : 0.0; return r; }
 template <int P> __device__ __forceinline__ Dual<P> dclamp(const Dual<P>& a, double lo, double hi) { Dual<P> r; const bool pass = a.v >= lo && a.v <= hi; r.v = fmin(fmax(a.v, lo), hi); for (int j = 0; j < P; ++j) r.d[j] = pass ? a.d[j] : 0.0; return r; }
+// torch.maximum(x, 0): gradient 1 for x > 0, 1/2 at the tie, 0 otherwise
+template <int P> __device__ __forceinline__ Dual<P> dmax0(const Dual<P>& x)
+{
+    const double w = x.v > 0.0 ? 1.0 : (x.v == 0.0 ? 0.5 : 0.0);
+    Dual<P> r;
+    r.v = fmax(x.v, 0.0);
+#pragma unroll
+    for (int q = 0; q < P; ++q) r.d[q] = w * x.d[q];
+    return r;
+}
+// a dual number kept as separate images in memory: the value at v[off], tangent q at d[q * stride + off]
+template <int P> __device__ __forceinline__ Dual<P> dload(const double* __restrict__ v, const double* __restrict__ d, int64_t stride, int64_t off)
+{
+    Dual<P> r;
+    r.v = v[off];
+#pragma unroll
+    for (int q = 0; q < P; ++q) r.d[q] = d[q * stride + off];
+    return r;
+}
+template <int P> __device__ __forceinline__ void dstore(double* v, double* d, int64_t stride, int64_t off, const Dual<P>& x)
+{
+    v[off] = x.v;
+#pragma unroll
+    for (int q = 0; q < P; ++q) d[q * stride + off] = x.d[q];
+}
+template <int P> __device__ __forceinline__ void dadd(double* v, double* d, int64_t stride, int64_t off, const Dual<P>& x)
+{
+    v[off] += x.v;
+#pragma unroll
+    for (int q = 0; q < P; ++q) d[q * stride + off] += x.d[q];
+}
 template <int P> __device__ __forceinline__ Dual<P> ddegree(const Dual<P>& x, bool fuzzy, double eps)
 {
     if (!fuzzy) return dconst<P>(x.v > 0.0 ? 1.0 : 0.0);

@@ -123,6 +123,8 @@ struct DevProduct {
     int32_t netting_set, init_state, n_states, flags;
 };
 
+struct DevEventIds { int32_t num, x; };      // atom ids behind the numeraire / explanatory copies a DevEvent carries
+
 struct mcx_book {
     int n_atoms, n_terms, n_events, n_products, n_netting_sets, n_expo_rows, n_basis, n_coeffs, want_cfs, want_expo;
     int n_state;                   // inferred: max col + 1 is NOT used; D comes from the sim (passed via paths layout)
@@ -139,6 +141,10 @@ struct mcx_book {
     std::vector<int32_t> h_event_t_idx;
     std::vector<int32_t> h_event_num_atom, h_event_x_atom, h_term_atom;
     std::vector<DevProduct> h_products;
+    // device images of the id tables for the tangent kernels (they index per-atom derivative rows): constants of the book, uploaded
+    // by the first forward-mode call that needs them (mcx_book_tangent_ids) and freed with the book
+    mutable DevEventIds* d_event_ids;     // [n_events]
+    mutable int32_t* d_term_atom;         // [n_terms]
     // exercise decisions recorded (1) / replayed (2) by K2 and K3 (mcx_book_set_exercise_replay): [n_events][ex_ld] bytes
     int ex_mode;
     uint8_t* d_ex_bits;
@@ -376,6 +382,18 @@ void* mcx_stage_small(mcx_handle* h, const void* src, size_t bytes, hipStream_t 
 // the same for tables that may exceed the ring (job tables of batched steps): through the ring when they fit, otherwise copied into
 // `fallback` (a device buffer of >= bytes) and completed before returning — `src` may be freed as soon as the call returns either way
 const void* mcx_upload_call_data(mcx_handle* h, const void* src, size_t bytes, void* fallback, hipStream_t s);
+// a call's host table on the device without an allocation per call: through the ring, or (a table larger than a quarter of the
+// ring) through the handle's scratch buffer `slot`; an empty table gives a valid pointer.  nullptr + handle error on failure
+const void* mcx_upload_table(mcx_handle* h, int slot, const void* src, size_t bytes, hipStream_t s);
+// the book's id tables on the device (mcx_book::d_event_ids, d_term_atom): uploaded on the first call, complete on return
+int mcx_book_tangent_ids(mcx_handle* h, const mcx_book* b);
+// moments from per-tile partial sums, for an entry point that returns them to the host.  mcx_partials_ws: the place in the
+// workspace for `n_tiles` blocks of `count` partials and their sum, or nullptr ("<who>: workspace too small" in the handle).
+// mcx_partials_to_host: adds the tiles in ascending order, copies the `count` sums through the pinned buffer into h_out and
+// synchronises the stream.  mcx_sum_partials is the sum alone: partials [n_jobs][n_tiles][count] -> d_out [n_jobs][count]
+double* mcx_partials_ws(mcx_handle* h, const char* who, int n_tiles, int count);
+int mcx_partials_to_host(mcx_handle* h, int n_tiles, int count, double* h_out, hipStream_t s);
+int mcx_sum_partials(mcx_handle* h, const double* d_partials, int n_jobs, int n_tiles, int count, double* d_out, hipStream_t s);
 int mcx_upload_unsec(mcx_handle* h, const mcx_unsecured_desc* u, DevUnsec* out, int32_t** d_tmp, hipStream_t s);
 int mcx_finish_acc(mcx_handle* h, const double* d_partials, int n_records, int n_blocks, double n_paths,
                    const double* d_shifts, mcx_acc* h_out, hipStream_t s);
