@@ -413,12 +413,23 @@ int  mcx_tangent_european(mcx_handle* h, const mcx_sim* sim, const mcx_tangent_o
  *   h_dslot [n_slots][MCX_SLOT_NPARAM][NP], h_dinit [n_state][NP], h_daux [n_steps][n_slots][MCX_AUX][NP]   (simulation)
  *   d_datoms [n_atoms][5][NP] = d(a, d, b, c0, c1)                                                          (book, device)
  * Tangent tensors carry the parameter index outermost: d_dpaths [NP][T][D][ld], d_cfs [1+NP][n_ns][ld] (index 0 = value),
- * d_expo [1+NP][n_ns][n_rows][ld].  Scope: EULER; BS / Vasicek / CIR++ slots; cashflow, plain option, exercise and polynomial-
- * exposure events; otherwise MCX_E_NOT_FUSABLE (the caller falls back to bump-and-revalue). */
+ * d_expo [1+NP][n_ns][n_rows][ld].  Scope: EULER with BS / Vasicek / CIR++ slots, ANALYTICAL with BS / Vasicek slots
+ * (mcx_tangent_paths_chol); cashflow, plain option, exercise and polynomial-exposure events; otherwise MCX_E_NOT_FUSABLE (the caller
+ * falls back to bump-and-revalue). */
 #define MCX_TANGENT_NP 4
 int  mcx_tangent_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
                        uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths, double* d_dpaths, int64_t ld,
                        const double* d_inject_z, void* stream);
+/* mcx_tangent_paths with the tangent of the Cholesky factors, h_dchol [n_chol][n_z][n_z][NP] next to the descriptor's chol.  Under
+ * ANALYTICAL the factor of the per-dt covariance depends on the model parameters (sigma sqrt(dt) for Black-Scholes,
+ * sqrt(sigma^2 / (2a) (1 - e^(-2 a dt))) for Vasicek, sigma_i sqrt(dt) (L_rho)_ij for correlated Black-Scholes assets), and the
+ * reference's tape differentiates through it (models/model.py:56-64).  Accepted: EULER with the slot kinds of mcx_tangent_paths
+ * (h_dchol may be NULL and is ignored: the call IS mcx_tangent_paths, bit for bit); ANALYTICAL with every slot MCX_MODEL_BS or
+ * MCX_MODEL_VASICEK (h_dchol required).  -1: a NULL argument; -2: ld < n_paths; MCX_E_NOT_FUSABLE with the reason in
+ * mcx_last_error: another scheme, another slot kind, n_z != n_slots, more than 4 slots.  A refused call enqueues and writes nothing. */
+int  mcx_tangent_paths_chol(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                            const double* h_dchol, uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths,
+                            double* d_dpaths, int64_t ld, const double* d_inject_z, void* stream);
 /* dual normal equations of (product, regression date): Y = numeraire * sum of the product's cash events with index >=
  * first_event; h_moments [1+NP][(2K-1)+K]: sums of z^k (k < 2K-1) then of z^k Y (k < K), z = (x - shift) * scale */
 int  mcx_tangent_lsm(mcx_handle* h, const mcx_book* book, int32_t product, int32_t first_event, int32_t num_atom, int32_t x_atom,

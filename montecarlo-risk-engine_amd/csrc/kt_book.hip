@@ -12,9 +12,10 @@
 // closed-form coefficients of each atom) arrive as arrays next to the primal descriptors (mcx/aad.py builds them).
 //   kt_lsm_step : the same for products with exercise rights (Bermudan / American / FlexiCall): the cashflow cache rolled back
 //              along the FROZEN exercise policy in dual numbers, moments per hypothetical state
-// Scope: EULER scheme; Black-Scholes / Vasicek / CIR++ (stochastic and deterministic) slots; cashflow, plain option and exercise
-// events, polynomial (also state-indexed) and analytic Black-Scholes exposures; thresholds and MPoR collateral in the metric
-// kernels.  Anything else keeps the common-random-number bump path.
+// Scope: EULER scheme with Black-Scholes / Vasicek / CIR++ (stochastic and deterministic) slots, ANALYTICAL scheme with Black-Scholes /
+// Vasicek slots (mcx_tangent_paths_chol: the Cholesky factor of the per-dt covariance carries a tangent); cashflow, plain option and
+// exercise events, polynomial (also state-indexed) and analytic Black-Scholes exposures; thresholds and MPoR collateral in the
+// metric kernels.  Anything else keeps the common-random-number bump path.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -143,6 +144,90 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_paths(const KTPArgs a)
                 break;
             }
             default: break;
+            }
+        }
+        const int st = sp.store_idx;
+        if (st >= 0) ktp_store<NSLOT>(a, st, i, reg);
+    }
+}
+
+// acc + l z for a dual factor entry and a plain normal: every image is one multiply-add, as the primal product's (k1_paths.hip)
+__device__ __forceinline__ DN ktp_fma(const DN& l, double z, const DN& acc)
+{
+    DN r;
+    r.v = fma(l.v, z, acc.v);
+#pragma unroll
+    for (int q = 0; q < NP; ++q) r.d[q] = fma(l.d[q], z, acc.d[q]);
+    return r;
+}
+
+// kt_paths in its second mode: the ANALYTICAL scheme of Black-Scholes and Vasicek slots, one normal per slot.  The factor of the
+// per-dt covariance depends on the parameters: row s of it is a dual number (dchol next to k.chol, both wave-uniform), and the step
+// maps are the primal analytic branches of step_slot (mcx_device.h) in dual numbers.  Initial state, draws (the same normals as the
+// EULER mode and as K1: one Box-Muller pair per two, an odd NZ drops the last sine) and stores as kt_paths, whose code stays as it was.
+struct KTPCholArgs {
+    KTPArgs p;
+    const double* __restrict__ dchol;   // [n_chol][n_z][n_z][NP]
+};
+
+template <int NSLOT, int NZ, bool INJECT>
+__global__ __launch_bounds__(MCX_BLOCK) void kt_paths_chol(const KTPCholArgs ca)
+{
+    const KTPArgs& a = ca.p;
+    const K1Args& k = a.k1;
+    __shared__ double bm_lds[INJECT ? 2 : MCX_BM_LDS_DOUBLES];
+    const double* tab = nullptr;
+    if (!INJECT) { mcx_bm_load(bm_lds); tab = bm_lds; }
+    const int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x;
+    if (i >= k.n) return;
+    DN reg[2 * NSLOT];
+#pragma unroll
+    for (int s = 0; s < NSLOT; ++s) {
+        const int c = k.slots[s].state_off;
+        const bool bs = k.slots[s].kind == MCX_MODEL_BS;
+        reg[2 * s] = ld_dual(k.init_state[c], a.dinit + (int64_t)c * NP);
+        reg[2 * s + 1] = bs ? dconst<NP>(0.0) : ld_dual(k.init_state[c + 1], a.dinit + (int64_t)(c + 1) * NP);
+    }
+    for (int t = 0; t < k.n_initial_store; ++t) ktp_store<NSLOT>(a, t, i, reg);
+    const uint64_t path = k.path_offset + (uint64_t)i;
+#pragma unroll 1
+    for (int step = 0; step < k.n_steps; ++step) {
+        const mcx_step sp = ldk_struct(&k.steps[step]);
+        double z[NZ];
+        if (INJECT) {
+#pragma unroll
+            for (int j = 0; j < NZ; ++j) z[j] = k.inject_z[((int64_t)step * NZ + j) * k.ld + i];
+        } else {
+#pragma unroll
+            for (int q = 0; q < (NZ + 1) / 2; ++q) {
+                double ua, z0, z1;
+                draw_pair<true>(k.seed, path, (uint32_t)step, (uint32_t)q, ua, z0, z1, tab);
+                z[2 * q] = z0;
+                if (2 * q + 1 < NZ) z[2 * q + 1] = z1;
+            }
+        }
+        const double* __restrict__ L = k.chol + (int64_t)sp.chol_idx * NZ * NZ;
+        const double* __restrict__ dL = ca.dchol + (int64_t)sp.chol_idx * NZ * NZ * NP;
+        const double dt = sp.dt;
+#pragma unroll
+        for (int s = 0; s < NSLOT; ++s) {
+            DN zs = dconst<NP>(0.0);                                          // (L z)_s with the factor's tangent
+#pragma unroll
+            for (int c = 0; c <= s; ++c) zs = ktp_fma(ld_dual(ldk(L + s * NZ + c), dL + (int64_t)(s * NZ + c) * NP), z[c], zs);
+            const double* __restrict__ p = k.slots[s].p;
+            const double* __restrict__ dp = a.dslot + (int64_t)s * MCX_SLOT_NPARAM * NP;
+            const double* __restrict__ ax = k.aux + ((int64_t)step * NSLOT + s) * MCX_AUX;
+            const double* __restrict__ dax = a.daux + ((int64_t)step * NSLOT + s) * MCX_AUX * NP;
+            DN& s0 = reg[2 * s];
+            DN& s1 = reg[2 * s + 1];
+            if (k.slots[s].kind == MCX_MODEL_BS) {                            // black_scholes.py:61-67
+                const DN drift = ld_dual(ldk(ax + 0), dax + 0 * NP), ito = ld_dual(ldk(ax + 1), dax + 1 * NP);
+                s0 = s0 * dexp(drift + (zs - ito));
+            } else {                                                          // MCX_MODEL_VASICEK, vasicek.py:76-86
+                const DN mean = ld_dual(p[2], dp + 2 * NP), decay = ld_dual(ldk(ax + 0), dax + 0 * NP);
+                const DN r = s0;
+                s1 = s1 + r * dt;
+                s0 = (mean + (r - mean) * decay) + zs;
             }
         }
         const int st = sp.store_idx;
@@ -592,6 +677,12 @@ void launch_ktp(const KTPArgs& a, int grid, bool inject, hipStream_t s)
     if (inject) hipLaunchKernelGGL((kt_paths<NSLOT, NZ, true>), dim3(grid), dim3(MCX_BLOCK), 0, s, a);
     else hipLaunchKernelGGL((kt_paths<NSLOT, NZ, false>), dim3(grid), dim3(MCX_BLOCK), 0, s, a);
 }
+template <int NSLOT, int NZ>
+void launch_ktp_chol(const KTPCholArgs& a, int grid, bool inject, hipStream_t s)
+{
+    if (inject) hipLaunchKernelGGL((kt_paths_chol<NSLOT, NZ, true>), dim3(grid), dim3(MCX_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL((kt_paths_chol<NSLOT, NZ, false>), dim3(grid), dim3(MCX_BLOCK), 0, s, a);
+}
 
 // the book's device tables (the id tables are uploaded by the first call that gets here) and the call's dual tensors
 int fill_book(mcx_handle* h, const mcx_book* b, const double* d_datoms, const double* d_paths, const double* d_dpaths, int64_t n_paths,
@@ -719,24 +810,35 @@ bool kt_upload_rows(mcx_handle* h, const int32_t* h_rows, const int32_t* h_delay
     return a->rows && (a->delayed || !h_delayed);
 }
 
-}  // namespace
-
-extern "C" int mcx_tangent_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
-                                 uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths, double* d_dpaths, int64_t ld,
-                                 const double* d_inject_z, void* stream)
+// mcx_tangent_paths and mcx_tangent_paths_chol.  `chol_entry`: the latter, which also takes the ANALYTICAL scheme of Black-Scholes /
+// Vasicek slots with the tangent of the factors (h_dchol).  Every check comes before the first upload: a refused call enqueues nothing
+int ktp_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux, const double* h_dchol,
+              uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths, double* d_dpaths, int64_t ld, const double* d_inject_z,
+              void* stream, const char* who, bool chol_entry)
 {
     if (!h || !sim || !h_dslot || !h_dinit || !h_daux || !d_paths || !d_dpaths) return -1;
-    if (n_paths <= 0) return 0;
-    if (ld < n_paths) MCX_FAIL(h, -2, "mcx_tangent_paths: ld < n_paths");
     const mcx_sim_desc& sd = sim->desc;
-    if (sd.scheme != MCX_SCHEME_EULER) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_paths: EULER scheme only");
+    const bool analytic = chol_entry && sd.scheme == MCX_SCHEME_ANALYTICAL;
+    if (analytic && !h_dchol) return -1;
+    if (n_paths <= 0) return 0;
+    if (ld < n_paths) MCX_FAIL(h, -2, "%s: ld < n_paths", who);
+    if (sd.scheme != MCX_SCHEME_EULER && !analytic)
+        MCX_FAIL(h, MCX_E_NOT_FUSABLE, chol_entry ? "%s: scheme %d: EULER or ANALYTICAL scheme only" : "%s: EULER scheme only", who, (int)sd.scheme);
     for (int s = 0; s < sd.n_slots; ++s) {
         const int kd = sd.slots[s].kind;
-        if (kd != MCX_MODEL_BS && kd != MCX_MODEL_VASICEK && kd != MCX_MODEL_CIRPP && kd != MCX_MODEL_CIRPP_DET)
-            MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_paths: slot %d: model kind %d has no tangent step", s, kd);
+        if (analytic) {
+            if (kd != MCX_MODEL_BS && kd != MCX_MODEL_VASICEK)
+                MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: slot %d: model kind %d has no analytic tangent step", who, s, kd);
+        } else if (kd != MCX_MODEL_BS && kd != MCX_MODEL_VASICEK && kd != MCX_MODEL_CIRPP && kd != MCX_MODEL_CIRPP_DET)
+            MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: slot %d: model kind %d has no tangent step", who, s, kd);
     }
-    if (sd.n_z != sd.n_slots) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_paths: one normal per slot expected");
-    if (sd.n_slots < 1 || sd.n_slots > 4) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_paths: %d slots have no instantiation", sd.n_slots);
+    if (sd.n_z != sd.n_slots) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: one normal per slot expected", who);
+    if (sd.n_slots < 1 || sd.n_slots > 4) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: %d slots have no instantiation", who, sd.n_slots);
+    if (analytic) {                                       // the kernel indexes h_dchol by the steps' factor index
+        if (sd.n_chol < 1) MCX_FAIL(h, -2, "%s: no Cholesky factor", who);
+        for (int k = 0; k < sd.n_steps; ++k)
+            if (sim->h_steps[k].chol_idx < 0 || sim->h_steps[k].chol_idx >= sd.n_chol) MCX_FAIL(h, -2, "%s: step %d: factor out of range", who, k);
+    }
     hipStream_t s = (hipStream_t)stream;
     KTPArgs a;
     memset(&a, 0, sizeof(a));
@@ -745,13 +847,41 @@ extern "C" int mcx_tangent_paths(mcx_handle* h, const mcx_sim* sim, const double
     a.dinit = (const double*)mcx_upload_table(h, 1, h_dinit, sizeof(double) * (size_t)sd.n_state * NP, s);
     a.daux = (const double*)mcx_upload_table(h, 2, h_daux, sizeof(double) * (size_t)sd.n_steps * sd.n_slots * MCX_AUX * NP, s);
     if (!a.dslot || !a.dinit || !a.daux) return -100;
+    const double* dchol = nullptr;
+    if (analytic) {
+        dchol = (const double*)mcx_upload_table(h, 3, h_dchol, sizeof(double) * (size_t)sd.n_chol * sd.n_z * sd.n_z * NP, s);
+        if (!dchol) return -100;
+    }
     a.dpaths = d_dpaths; a.pstride = (int64_t)sd.n_dates * sd.n_state * ld; a.n_slots = sd.n_slots;
     const int grid = (int)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK);
     const bool inj = d_inject_z != nullptr;
-    MCX_DISPATCH(NS, sd.n_slots, 4, launch_ktp<NS, NS>(a, grid, inj, s));
+    if (analytic) {
+        KTPCholArgs ac;
+        ac.p = a; ac.dchol = dchol;
+        MCX_DISPATCH(NS, sd.n_slots, 4, launch_ktp_chol<NS, NS>(ac, grid, inj, s));
+    }
+    else { MCX_DISPATCH(NS, sd.n_slots, 4, launch_ktp<NS, NS>(a, grid, inj, s)); }
     MCX_HIP(h, hipGetLastError());
     MCX_HIP(h, hipStreamSynchronize(s));
     return 0;
+}
+
+}  // namespace
+
+extern "C" int mcx_tangent_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                                 uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths, double* d_dpaths, int64_t ld,
+                                 const double* d_inject_z, void* stream)
+{
+    return ktp_paths(h, sim, h_dslot, h_dinit, h_daux, nullptr, seed, path_offset, n_paths, d_paths, d_dpaths, ld, d_inject_z, stream,
+                     "mcx_tangent_paths", false);
+}
+
+extern "C" int mcx_tangent_paths_chol(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                                      const double* h_dchol, uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths,
+                                      double* d_dpaths, int64_t ld, const double* d_inject_z, void* stream)
+{
+    return ktp_paths(h, sim, h_dslot, h_dinit, h_daux, h_dchol, seed, path_offset, n_paths, d_paths, d_dpaths, ld, d_inject_z, stream,
+                     "mcx_tangent_paths_chol", true);
 }
 
 extern "C" int mcx_tangent_lsm(mcx_handle* h, const mcx_book* b, int32_t product, int32_t first_event, int32_t num_atom, int32_t x_atom,

@@ -23,7 +23,7 @@ _EXPORTS = [
     "mcx_comm_unique_id", "mcx_comm_init", "mcx_comm_destroy", "mcx_allreduce_f64", "mcx_allgather_f64",
     "mcx_book_create", "mcx_book_destroy", "mcx_book_set_coeffs", "mcx_eval_book", "mcx_eval_book_describe", "mcx_resolve_atoms",
     "mcx_lsm_stats", "mcx_lsm_step", "mcx_lsm_run", "mcx_lsm_solve", "mcx_lsm_step_batch", "mcx_lsm_step_batch_dev", "mcx_lsm_solve_batch", "mcx_lsm_run_batch", "mcx_book_get_coeffs", "mcx_book_set_coeffs_batch", "mcx_book_set_bridge_rng", "mcx_book_set_exercise_replay",
-    "mcx_fused_is_straight_line", "mcx_tangent_paths", "mcx_tangent_lsm", "mcx_tangent_lsm_batch", "mcx_tangent_lsm_step", "mcx_tangent_eval", "mcx_tangent_cva", "mcx_tangent_profiles", "mcx_tangent_pick",
+    "mcx_fused_is_straight_line", "mcx_tangent_paths", "mcx_tangent_paths_chol", "mcx_tangent_lsm", "mcx_tangent_lsm_batch", "mcx_tangent_lsm_step", "mcx_tangent_eval", "mcx_tangent_cva", "mcx_tangent_profiles", "mcx_tangent_pick",
     "mcx_box_muller", "mcx_tangent_european", "mcx_fused_create", "mcx_fused_destroy", "mcx_fused_num_records", "mcx_fused_run", "mcx_fused_eval_paths", "mcx_fused_run_device", "mcx_fused_eval_paths_device", "mcx_fused_set_timing", "mcx_fused_kernel_times", "mcx_fused_describe",
     "mcx_value_poly_fit", "mcx_book_collapse_values", "mcx_book_value_poly_info", "mcx_rows_minmax",
     "mcx_storage_create", "mcx_storage_destroy", "mcx_storage_lsm_step", "mcx_storage_lsm_run", "mcx_storage_eval",
@@ -69,6 +69,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_tangent_storage_eval.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i64, vp]
     lib.mcx_tangent_lsm_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, i64, i64, i32, vp, vp]
     lib.mcx_tangent_paths_s2f.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
+    lib.mcx_tangent_paths_chol.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_fused_num_records.argtypes = [C.c_void_p]
     lib.mcx_fused_is_straight_line.argtypes = [C.c_void_p]
     lib.mcx_fused_describe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
@@ -420,6 +421,27 @@ class HipBackend:
             self.h, sim.ptr, _abi.ptr(a[0]), _abi.ptr(a[1]), _abi.ptr(a[2]), C.c_uint64(seed), C.c_uint64(path_offset),
             C.c_int64(n_paths), _vp(paths.data_ptr()), _vp(dpaths.data_ptr()), C.c_int64(n_paths),
             _vp(inject_z.data_ptr() if inject_z is not None else 0), self._stream()), "mcx_tangent_paths")
+        return paths, dpaths
+
+    def tangent_paths_chol(self, sim, dslot: np.ndarray, dinit: np.ndarray, daux: np.ndarray, dchol: np.ndarray | None, seed: int,
+                           path_offset: int, n_paths: int, inject_z=None, out=None, ld: int | None = None):
+        """tangent_paths with the tangent of the Cholesky factors, dchol [n_chol][n_z][n_z][NP] (mcx_tangent_paths_chol): the
+        ANALYTICAL scheme of Black-Scholes / Vasicek slots; under EULER dchol may be None and the call is tangent_paths.
+        out: (paths, dpaths) to write into instead of fresh tensors; ld: their leading dimension when it is not n_paths"""
+        plan = sim.plan
+        NP = _abi.TANGENT_NP
+        paths, dpaths = out if out is not None else (self.empty(plan.n_dates, plan.n_state, n_paths),
+                                                     self.empty(NP, plan.n_dates, plan.n_state, n_paths))
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (dslot, dinit, daux)]
+        assert a[0].shape == (plan.n_slots, _abi.SLOT_NPARAM, NP) and a[1].shape == (plan.n_state, NP)
+        assert a[2].shape == (plan.n_steps, plan.n_slots, _abi.AUX, NP)
+        if dchol is not None:
+            dchol = np.ascontiguousarray(dchol, dtype=np.float64)
+            assert dchol.shape == (len(plan.chol), plan.n_z, plan.n_z, NP)
+        self._check(self.lib.mcx_tangent_paths_chol(
+            self.h, sim.ptr, _abi.ptr(a[0]), _abi.ptr(a[1]), _abi.ptr(a[2]), _abi.ptr(dchol) if dchol is not None else None, seed,
+            path_offset, n_paths, paths.data_ptr(), dpaths.data_ptr(), n_paths if ld is None else ld,
+            inject_z.data_ptr() if inject_z is not None else None, self._stream()), "mcx_tangent_paths_chol")
         return paths, dpaths
 
     def tangent_lsm(self, book, product: int, first_event: int, num_atom: int, x_atom: int, shift: float, scale: float,

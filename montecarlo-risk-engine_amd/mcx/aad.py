@@ -10,7 +10,9 @@ Tangent kernels exist (BASELINE configs 2 and 4) for PV metrics of European opti
 Black-Scholes or Heston model.
 
 Sensitivities through the LSM regression (CVA / PV of stateless books under BS / Vasicek / CIR++ Euler) run in forward mode too:
-`run_with_tangent_book` drives csrc/kt_book.hip (dual paths -> dual normal equations -> dual book -> dual CVA).
+`run_with_tangent_book` drives csrc/kt_book.hip (dual paths -> dual normal equations -> dual book -> dual CVA).  So do books under
+the ANALYTICAL scheme whose slots are Black-Scholes or Vasicek: there the Cholesky factor of the per-dt covariance depends on the
+parameters, the models give it in closed form (`Model._analytic_factor_entries`) and mcx_tangent_paths_chol carries its tangent.
 
 Every other configuration (`run_with_bumps`): sensitivities through the LSM regression — CVA / EPE / PFE greeks, SURVEY §8f
 rank 1, reference test `tests/pytests/test_cva_large_netting_set_aad_vs_fd.py` — are computed by CENTRAL DIFFERENCES WITH
@@ -18,7 +20,7 @@ COMMON RANDOM NUMBERS: the Philox counters (or the injected draws) are identical
 quotient converges to the same pathwise derivative the reference's tape returns (including the dependence of the regression
 coefficients on the parameters through the pre-simulation), with O(h^2) truncation and no sampling noise.  It costs 2P + 1
 passes of the millisecond-scale hot path and serves what the forward-mode kernels do not cover (exercise products, PFE,
-collateral, analytic exposures, non-Euler schemes).
+collateral, analytic exposures, the QE scheme, Heston / Hull-White / S2F slots under ANALYTICAL).
 
 Exercise products (American / Bermudan / FlexiCall): the reference's tape has NO gradient through the boolean
 `should_exercise` (bermudan_option.py:122-128): its sensitivities hold the exercise policy fixed.  A plain bump would let paths
@@ -237,7 +239,18 @@ def _host_descriptors(sc, model=None, dtype=np.float64):
     out = dict(slots=slots, init=np.array(model._initial_state(), dtype=dtype), aux=aux, atoms=atoms)
     if hasattr(model, "_cholesky_entries"):          # factors that depend on the parameters (a correlation that is one of them)
         out["chol"] = np.array([model._cholesky_entries(sim.scheme, dt) for dt in sim.chol_dt], dtype=dtype).reshape(len(sim.chol_dt), sim.n_z, sim.n_z)
+    elif _analytic_factor_form(model, sim.scheme):   # ANALYTICAL: the factor of the per-dt covariance (volatilities, mean reversion)
+        out["chol"] = np.array([model._analytic_factor_entries(dt) for dt in sim.chol_dt], dtype=dtype).reshape(len(sim.chol_dt), sim.n_z, sim.n_z)
     return out, shape
+
+
+def _analytic_factor_form(model, scheme) -> bool:
+    """does `model` give the ANALYTICAL scheme's Cholesky factor in closed form (Model._analytic_factor_entries), with every slot
+    one whose analytic step the dual path kernel has (csrc/kt_book.hip kt_paths: Black-Scholes, Vasicek)?"""
+    entries = getattr(model, "_analytic_factor_entries", None)
+    if scheme.name != "ANALYTICAL" or entries is None or entries(1.0) is None:
+        return False
+    return all(sp.kind in (_abi.MODEL_BS, _abi.MODEL_VASICEK) for sp in model._slots())
 
 
 def _set_complex_step(model, j: int, h: float):
@@ -349,7 +362,10 @@ def run_with_tangent_book(sc):
     # Schwartz two-factor dual paths serve books that hold a storage; every other book keeps the route it had (no tangent form)
     s2f = hasattr(sc.model, "_cholesky_entries") and hasattr(sc.backend, "tangent_paths_s2f") \
         and any(getattr(p, "is_storage", False) for p in sc.products)
-    if sc.simulation_scheme.name != "EULER" and not (s2f and sc.simulation_scheme.name == "ANALYTICAL"):
+    # ANALYTICAL: the factor of the per-dt covariance depends on the parameters; mcx_tangent_paths_chol carries its tangent for
+    # Black-Scholes and Vasicek slots whose models give it in closed form
+    chol = not s2f and hasattr(sc.backend, "tangent_paths_chol") and _analytic_factor_form(sc.model, sc.simulation_scheme)
+    if sc.simulation_scheme.name != "EULER" and not (s2f and sc.simulation_scheme.name == "ANALYTICAL") and not chol:
         raise _NoTangentForm("scheme")
     if any(m.metric_type not in (MetricType.PV, MetricType.CVA, MetricType.EPE, MetricType.ENE, MetricType.CE, MetricType.EEPE,
                                  MetricType.PFE) or not m._native for m in rm.metrics):
@@ -443,6 +459,8 @@ def run_with_tangent_book(sc):
         def dual_paths(seed, off_, n_, inject_z):
             if s2f:
                 return be.tangent_paths_s2f(sim, dslot, dinit, daux, pad(dd["chol"]), seed, off_, n_, inject_z)
+            if chol:
+                return be.tangent_paths_chol(sim, dslot, dinit, daux, pad(dd["chol"]), seed, off_, n_, inject_z)
             return be.tangent_paths(sim, dslot, dinit, daux, seed, off_, n_, inject_z)
         coeffs, dcoeffs = np.zeros(max(n_coeffs, 1)), np.zeros((max(n_coeffs, 1), NP))
         if has_exercise and n_coeffs:

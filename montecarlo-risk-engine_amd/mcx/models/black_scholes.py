@@ -49,6 +49,12 @@ class BlackScholesModel(Model):
         sigma = self.get_volatility()
         return torch.diag(sigma * sigma * float(delta_t))            # black_scholes.py:44-48
 
+    def _analytic_factor_entries(self, delta_t):
+        """the ANALYTICAL scheme's factor in closed form: sqrt(sigma^2 dt) = sigma sqrt(dt).  Complex-safe: the volatility is a
+        model parameter, so the factor carries a tangent (mcx/aad.py evaluates this at theta + i h; csrc/kt_book.hip kt_paths)."""
+        sigma = self._pf(1)
+        return [[csqrt(sigma * sigma * float(delta_t))]]
+
     def _slots(self):
         return [SlotSpec(_abi.MODEL_BS, [self._pf(0), self._pf(1), self._pf(2)], 1, 1)]
 

@@ -14,7 +14,7 @@ from ..common.enums import SimulationScheme
 from ..common.packages import FLOAT, device
 from ..request_interface.request_types import AtomicRequestType as RT
 from .black_scholes import deterministic_rate_atom
-from .model import AtomCoef, Model, SlotSpec
+from .model import AtomCoef, Model, SlotSpec, scaled_correlation_factor
 
 
 class BlackScholesMulti(Model):
@@ -51,6 +51,11 @@ class BlackScholesMulti(Model):
             S = torch.diag(self.get_volatility().detach())
             hit = self.__dict__["_scs"] = (vols, S @ self.correlation_matrix @ S)
         return hit[1] * float(delta_t)                                       # black_scholes_multi.py:56-61
+
+    def _analytic_factor_entries(self, delta_t):
+        """the ANALYTICAL scheme's factor in closed form, complex-safe in the volatilities (mcx/aad.py; csrc/kt_book.hip kt_paths)"""
+        n = self.num_assets
+        return scaled_correlation_factor(self, [self._pf(n + i) for i in range(n)], self.correlation_matrix, delta_t)
 
     # ---- native hooks -------------------------------------------------------------------------------------------
     def _rate(self) -> float:

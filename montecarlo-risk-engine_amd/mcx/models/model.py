@@ -31,6 +31,18 @@ def csqrt(x):
     return cmath.sqrt(x) if isinstance(x, complex) else math.sqrt(x)
 
 
+def scaled_correlation_factor(owner, vols, correlation: torch.Tensor, delta_t: float):
+    """the lower factor of the covariance S rho S dt of n Black-Scholes assets in closed form: sigma_i sqrt(dt) (L_rho)_ij, with L_rho
+    the factor of the correlation matrix — real and parameter-free, computed once and kept on `owner`.  `vols` may be complex
+    (complex-step differentiation of the descriptors, mcx/aad.py): the volatilities are model parameters, the correlations are not."""
+    L = owner.__dict__.get("_l_rho")
+    if L is None:
+        L = owner.__dict__["_l_rho"] = np.linalg.cholesky(correlation.detach().cpu().numpy().astype(np.float64))
+    sq = math.sqrt(float(delta_t))
+    n = len(vols)
+    return [[vols[i] * sq * float(L[i, j]) if j <= i else 0.0 for j in range(n)] for i in range(n)]
+
+
 @dataclass
 class SlotSpec:
     kind: int

@@ -11,7 +11,7 @@ import torch
 from ..common.enums import SimulationScheme
 from ..common.packages import FLOAT, device
 from .black_scholes import BlackScholesModel
-from .model import Model
+from .model import Model, scaled_correlation_factor
 
 
 class ModelConfig(Model):
@@ -90,6 +90,20 @@ class ModelConfig(Model):
             raise NotImplementedError("Inter covariance not implemented for the requested pair of models.")
 
         return self._assemble(lambda m: m._get_covariance_matrix(dt).detach(), inter)
+
+    def _analytic_factor_entries(self, delta_t):
+        """the ANALYTICAL scheme's joint factor in closed form where there is one: a single sub-model's own, or, for Black-Scholes
+        leaves, sigma_i sqrt(dt) times the factor of the joint correlation matrix (the only pairing `_get_covariance_matrix`
+        assembles).  None otherwise: the forward-mode pass then has no tangent of the factor (mcx/aad.py)."""
+        if len(self.models) == 1:
+            own = getattr(self.models[0], "_analytic_factor_entries", None)
+            return own(delta_t) if own is not None else None
+        if not all(isinstance(m, BlackScholesModel) for m in self.models):
+            return None
+        corr = self.__dict__.get("_joint_rho")
+        if corr is None:
+            corr = self.__dict__["_joint_rho"] = self._get_correlation_matrix(SimulationScheme.ANALYTICAL)
+        return scaled_correlation_factor(self, [m._pf(1) for m in self.models], corr, delta_t)
 
     # ---- native hooks -------------------------------------------------------------------------------------------
     def _slots(self):

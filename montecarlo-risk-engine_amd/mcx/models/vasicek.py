@@ -40,6 +40,13 @@ class VasicekModel(Model):
         decay = torch.exp(-a * float(delta_t))
         return torch.diag((sigma ** 2 / (2 * a)) * (1 - decay ** 2))   # vasicek.py:52-59
 
+    def _analytic_factor_entries(self, delta_t):
+        """the ANALYTICAL scheme's factor in closed form: sqrt(sigma^2 / (2a) (1 - e^(-2 a dt))).  Complex-safe: the volatility and
+        the mean-reversion speed are model parameters, so the factor carries tangents (mcx/aad.py; csrc/kt_book.hip kt_paths)."""
+        sigma, a = self._pf(1), self._pf(3)
+        decay = cexp(-a * float(delta_t))
+        return [[csqrt((sigma ** 2 / (2 * a)) * (1 - decay ** 2))]]
+
     def _zcb_coeffs(self, time1: float, time2: float) -> tuple[float, float]:
         """P(t1,t2 | r) = exp(alpha - B r)  (vasicek.py:114-128)"""
         sigma, theta, a = self._pf(1), self._pf(2), self._pf(3)
