@@ -346,9 +346,24 @@ int  mcx_fused_is_straight_line(const mcx_fused* f);
  * mcx_fused_run) or streaming a paths tensor (simulate == 0, mcx_fused_eval_paths) launches, from the same host function that
  * chooses the launch.  out[MCX_FDESC_*] is the header below, then two entries per timeline date t:
  * out[MCX_FDESC_HEADER + 2 t] = 1 when the date is straight-line (evaluated from its FastDate record), 0 when interpreted, and
- * out[MCX_FDESC_HEADER + 2 t + 1] = the record's flag bits.  Returns the number of entries (MCX_FDESC_HEADER + 2 n_dates); when
- * that exceeds cap nothing is written; < 0 on error. */
+ * out[MCX_FDESC_HEADER + 2 t + 1] = the record's flag bits (MCX_FD_*).  Returns the number of entries (MCX_FDESC_HEADER +
+ * 2 n_dates); when that exceeds cap nothing is written; -1 on an invalid argument, the only error: the call reads host
+ * memory alone. */
 enum { MCX_ROUTE_NONE = 0, MCX_ROUTE_LEAN = 1, MCX_ROUTE_FUSED = 2 };
+enum {                         /* flag bits of a date's straight-line record (csrc/kf_common.h FastDate::flags)    */
+    MCX_FD_CASH = 1,           /* cashflows or a plain option payoff feed the PV record / the cashflow output      */
+    MCX_FD_EXPO = 2,           /* a polynomial (regression) exposure is evaluated                                  */
+    MCX_FD_CVA = 4,            /* the date adds a CVA increment                                                    */
+    MCX_FD_PROFILE = 8,        /* the date records an EPE / ENE pair                                               */
+    MCX_FD_CONST_NUM = 16,     /* the numeraire is a constant (no exponential)                                     */
+    MCX_FD_METRIC = 32,        /* a metric operation (threshold, profile and / or CVA) is present                  */
+    MCX_FD_MERGED = 64,        /* the CVA increment may use the merged discount x survival factor: no threshold,   */
+                               /*   no EPE / ENE record on this date                                               */
+    MCX_FD_EXERCISE = 128,     /* exercise event of the book's one two-state exercise product                      */
+    MCX_FD_STATE_EXPO = 256,   /* the exposure's coefficient row is indexed by the lane's exercise state           */
+    MCX_FD_OPTION = 512,       /* the date's cash value is a plain option payoff max(sign (value - strike), 0)     */
+    MCX_FD_EX_VPOLY = 1024     /* the exercise value is also available as one verified polynomial                  */
+};
 enum {
     MCX_FDESC_LEAN = 0,        /* every date straight-line (mcx_fused_is_straight_line)                          */
     MCX_FDESC_NPF = 1,         /* 1 KiB prefetch pieces of the object (0, 1, 2)                                    */

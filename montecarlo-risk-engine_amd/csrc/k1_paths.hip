@@ -279,29 +279,10 @@ static int generate_paths_impl(mcx_handle* h, const mcx_sim* sim, uint64_t seed,
     a.init_paths = d_init_state;
     hipStream_t s = (hipStream_t)stream;
     const bool inj = d_inject_z != nullptr;
-    switch (mcx_sim_signature(d)) {       // specialised (compile-time model kinds) instantiations of the hot configurations
-    case SIG_VAS_CIR_E: launch_k1<2, 2, SIG_VAS_CIR_E>(a, inj, s); break;
-    case SIG_BS_A: launch_k1<1, 1, SIG_BS_A>(a, inj, s); break;
-    case SIG_BS_E: launch_k1<1, 1, SIG_BS_E>(a, inj, s); break;
-    case SIG_HESTON_QE: launch_k1<1, 2, SIG_HESTON_QE>(a, inj, s); break;
-    case SIG_HESTON_E: launch_k1<1, 2, SIG_HESTON_E>(a, inj, s); break;
-    case SIG_VAS_E: launch_k1<1, 1, SIG_VAS_E>(a, inj, s); break;
-    case SIG_VAS_A: launch_k1<1, 1, SIG_VAS_A>(a, inj, s); break;
-    case SIG_BS_VAS_CIRDET_E: launch_k1<3, 3, SIG_BS_VAS_CIRDET_E>(a, inj, s); break;
-    default:
-        switch (d.n_slots * 16 + d.n_z) {
-        case 1 * 16 + 1: launch_k1<1, 1, SIG_GENERIC>(a, inj, s); break;
-        case 1 * 16 + 2: launch_k1<1, 2, SIG_GENERIC>(a, inj, s); break;
-        case 2 * 16 + 2: launch_k1<2, 2, SIG_GENERIC>(a, inj, s); break;
-        case 3 * 16 + 3: launch_k1<3, 3, SIG_GENERIC>(a, inj, s); break;
-        case 4 * 16 + 4: launch_k1<4, 4, SIG_GENERIC>(a, inj, s); break;
-        case 5 * 16 + 5: launch_k1<5, 5, SIG_GENERIC>(a, inj, s); break;
-        case 6 * 16 + 6: launch_k1<6, 6, SIG_GENERIC>(a, inj, s); break;
-        case 7 * 16 + 7: launch_k1<7, 7, SIG_GENERIC>(a, inj, s); break;
-        case 8 * 16 + 8: launch_k1<8, 8, SIG_GENERIC>(a, inj, s); break;
-        default: MCX_FAIL(h, -4, "mcx_generate_paths: unsupported (slots=%d, z=%d)", d.n_slots, d.n_z);
-        }
-    }
+    const bool launched = mcx_dispatch_signature<8>(d, [&](auto nslot, auto nz, auto sig) {
+        launch_k1<decltype(nslot)::value, decltype(nz)::value, decltype(sig)::value>(a, inj, s);
+    });
+    if (!launched) MCX_FAIL(h, -4, "mcx_generate_paths: unsupported (slots=%d, z=%d)", d.n_slots, d.n_z);
     MCX_HIP(h, hipGetLastError());
     return 0;
 }

@@ -6,17 +6,19 @@
 
 
 
+enum { FA_EXP = 1, FA_AFFINE = 2 };      // FAtom::parts: the atom has an exponential term (b != 0), an affine term (a or d != 0)
 struct FAtom {             // value = a + d*x + b*exp(c0 + c1*x), x = register `reg` of the lane (reg < 0: x = 0)
-    int32_t reg, pad;
+    int32_t reg, parts;
     double a, d, b, c0, c1;
 };
 struct FTerm { double w; FAtom atom; };
+enum { FE_SAME_NUM = 2 };  // FEvent::flags (beside the book's own event flags): same numeraire as the previous event of the date
 struct FEvent {
     int32_t kind, flags;
     int32_t term_begin, term_end;
     int32_t coeff_off, row;
     int32_t ns, sidx;          // netting-set slot (0..3), stateful-product slot (0..3) or -1
-    int32_t init_state, pad;
+    int32_t init_state, n_states;      // of the event's product
     double strike, sign;
     double aux[4];
     FAtom num, x;
@@ -29,7 +31,25 @@ struct FMetricOp {             // one (netting set, metric date) pair, executed 
     FAtom surv, cond;
 };
 
+static_assert(sizeof(FAtom) == 48 && sizeof(FEvent) == 184 && sizeof(FMetricOp) == 120, "program records are uploaded byte for byte");
+
 struct ChunkHeader { int32_t n_ev, n_mop, n_terms, bytes; };
+
+// FastDate::flags.  The values are the public MCX_FD_* (include/mcx.h), which mcx_fused_describe reports per date.
+enum {
+    FD_CASH = MCX_FD_CASH,                // cashflows (k0, k1, t_*) or a plain option payoff: feeds the PV record / cashflow output
+    FD_EXPO = MCX_FD_EXPO,                // polynomial exposure in x_a + x_d reg[x_reg], rows coeff_off0 / coeff_off1
+    FD_CVA = MCX_FD_CVA,                  // CVA increment: survival s_*, conditional survival c_*
+    FD_PROFILE = MCX_FD_PROFILE,          // EPE / ENE records rec_profile, rec_profile + 1
+    FD_CONST_NUM = MCX_FD_CONST_NUM,      // constant numeraire: 1/numeraire = ni_c0
+    FD_METRIC = MCX_FD_METRIC,            // a metric op is present (thr, and FD_PROFILE and / or FD_CVA)
+    FD_MERGED = MCX_FD_MERGED,            // the CVA increment may use the merged discount x survival factor (m_*): no threshold,
+                                          //     no EPE / ENE record on this date
+    FD_EXERCISE = MCX_FD_EXERCISE,        // exercise event of the book's ONE two-state exercise product (ex_*)
+    FD_STATE_EXPO = MCX_FD_STATE_EXPO,    // the exposure's coefficient row is indexed by the lane's exercise state
+    FD_OPTION = MCX_FD_OPTION,            // the cash value is a plain option payoff (op_strike, op_sign)
+    FD_EX_VPOLY = MCX_FD_EX_VPOLY         // the exercise value is also ONE verified polynomial (ex_p_*)
+};
 
 // Straight-line record of a date whose program is the common linear-book shape (one netting set; cashflows that are an
 // affine term + <= 4 exponential terms over a pure-exponential or constant numeraire, or a plain option payoff; polynomial
@@ -39,29 +59,27 @@ struct ChunkHeader { int32_t n_ev, n_mop, n_terms, bytes; };
 struct FastDate {
     // ---- hot head (FastDateHot below is a view of these 144 bytes: ONE batch of scalar loads at the top of a date) ----
     int32_t valid, flags;            // valid: 0 interpreted, 1 straight-line (lean_date, in kf_lean and kf_fused alike)
-                                     // flags: 1 cash, 2 expo, 4 cva, 8 profile, 16 constant numeraire, 32 metric op present,
-                                     // 64: the CVA increment may use the merged discount x survival factor (m_*): no threshold,
-                                     //     no EPE / ENE record on this date
+                                     // flags: FD_* above
     int32_t ni_reg, lin_reg, n_exp, x_reg, coeff_off0, coeff_off1, rec_profile, s_reg, c_reg, pad;
     int32_t t_reg[4];
     double x_a, x_d;                 // explanatory x = x_a + x_d * reg[x_reg]
     double c_a, c_b, c_c0, c_c1;     // S(t,t+) cond = c_a + c_b exp(c_c0 + c_c1 reg[c_reg])
-    double m_b, m_c0, m_n1, m_s1;    // S(0,t) / numeraire = m_b exp(m_c0 + m_n1 reg[ni_reg] + m_s1 reg[s_reg])   (flag 64)
+    double m_b, m_c0, m_n1, m_s1;    // S(0,t) / numeraire = m_b exp(m_c0 + m_n1 reg[ni_reg] + m_s1 reg[s_reg])   (FD_MERGED)
     // ---- the rest: read at the point of use ----
-    double ni_c0, ni_c1;             // 1/numeraire = exp(ni_c0 + ni_c1 x)   (flag 16: = ni_c0)
+    double ni_c0, ni_c1;             // 1/numeraire = exp(ni_c0 + ni_c1 x)   (FD_CONST_NUM: = ni_c0)
     double k0, k1;                   // cash affine part k0 + k1 * reg[lin_reg]
     double t_w[4], t_c0[4], t_c1[4];
     double thr;
     double s_b, s_c0, s_c1;          // S(0,t)       = s_b exp(s_c0 + s_c1 reg[s_reg])
-    // flag 128: exercise event of the book's ONE two-state exercise product (bermudan_option.py:93-131): immediate value
+    // FD_EXERCISE: exercise event of the book's ONE two-state exercise product (bermudan_option.py:93-131): immediate value
     // max(ex_sign (ex_k0 + ex_k1 reg[ex_lin_reg] + sum_j w_j exp(c0_j + c1_j reg[r_j]) - ex_strike), 0) over the LeanTerm range
     // [ex_term_off, ex_term_off + ex_n); continuation = polynomial (row of state 1 at ex_coeff_off + n_basis) in ex_x_a + ex_x_d reg[ex_x_reg]
-    // flag 256: the exposure polynomial's coefficient row is indexed by the lane's exercise state (coeff_off0 + state * n_basis)
+    // FD_STATE_EXPO: the exposure polynomial's coefficient row is indexed by the lane's exercise state (coeff_off0 + state * n_basis)
     int32_t ex_n, ex_term_off, ex_coeff_off, ex_x_reg, ex_lin_reg, ex_pad;
     double ex_k0, ex_k1, ex_strike, ex_sign, ex_x_a, ex_x_d;
-    // flag 512: the date's cash value is a plain option payoff (european_option.py:45-68): max(op_sign (value - op_strike), 0)
+    // FD_OPTION: the date's cash value is a plain option payoff (european_option.py:45-68): max(op_sign (value - op_strike), 0)
     double op_strike, op_sign;
-    // flag 1024: the exercise value (affine part, constants and every exponential term) is also available as ONE verified polynomial of
+    // FD_EX_VPOLY: the exercise value (affine part, constants and every exponential term) is also available as ONE verified polynomial of
     // reg[ex_p_reg] (mcx_vpoly.hip): p(t), t = fma(x, ex_p_ih, ex_p_ms), ex_p_blk blocks of 4 coefficients at vcoef + ex_p_off, valid
     // for ex_p_lo <= x <= ex_p_hi; a wave that holds a path outside runs the LeanTerm loop
     double ex_p_lo, ex_p_hi, ex_p_ms, ex_p_ih;
@@ -142,10 +160,10 @@ __device__ __forceinline__ double f_atom(const FAtom& a, const double (&reg)[NRE
 {
     // the program lives in LDS, so its fields arrive in VGPRs; the CONTROL fields are made wave-uniform SGPRs
     // (v_readfirstlane) so that selects / branches are scalar instead of exec-masked divergent code
-    const int r = RFL(a.reg), fl = RFL(a.pad);          // pad: bit0 = has exp term, bit1 = has affine term
+    const int r = RFL(a.reg), fl = RFL(a.parts);
     const double x = r >= 0 ? reg[r] : 0.0;             // uniform dynamic index -> M0-relative VGPR read (v_movrels)
-    double v = (fl & 2) ? fma(a.d, x, a.a) : 0.0;
-    if (fl & 1) v = fma(a.b, mcx_exp(fma(a.c1, x, a.c0)), v);
+    double v = (fl & FA_AFFINE) ? fma(a.d, x, a.a) : 0.0;
+    if (fl & FA_EXP) v = fma(a.b, mcx_exp(fma(a.c1, x, a.c0)), v);
     return v;
 }
 
@@ -258,7 +276,7 @@ __device__ __forceinline__ void lean_date(int t, const int64_t (&i)[PPL], const 
     //  four SIMDs of a CU share: ~500 scalar instructions per date and wave of the general program cap it at ~4.3 TB/s)
     if ((PPL == 1 || !STORE) && !(STORE && k.paths)) {
         const FastDateHot hot = ldk_struct((const FastDateHot*)fp);
-        const bool pure_cva = (hot.flags & (64 | 128 | 256 | 2)) == (64 | 2) && !((hot.flags & 1) && (a.cfs != nullptr || a.rec_pv[0] >= 0)) &&
+        const bool pure_cva = (hot.flags & (FD_MERGED | FD_EXERCISE | FD_STATE_EXPO | FD_EXPO)) == (FD_MERGED | FD_EXPO) && !((hot.flags & FD_CASH) && (a.cfs != nullptr || a.rec_pv[0] >= 0)) &&
                               a.expo == nullptr && a.n_basis == 3 && hot.c_b != 0.0;
         if (pure_cva) {
             const double* __restrict__ cf = a.coeffs;
@@ -297,12 +315,12 @@ __device__ __forceinline__ void lean_date(int t, const int64_t (&i)[PPL], const 
     }
     const int flags = FD(flags);
     // cashflows feed the PV record / the cashflow output only; a CVA / exposure-profile run skips them
-    const bool want_cash = (flags & 1) && (a.cfs != nullptr || a.rec_pv[0] >= 0);
+    const bool want_cash = (flags & FD_CASH) && (a.cfs != nullptr || a.rec_pv[0] >= 0);
     // CVA-only date without threshold: relu(p / N) S (1 - Sc) = relu(p) (S / N) (1 - Sc), one exponential for S / N
-    const bool merged = (flags & 64) && !(flags & 128) && !want_cash && a.expo == nullptr;
+    const bool merged = (flags & FD_MERGED) && !(flags & FD_EXERCISE) && !want_cash && a.expo == nullptr;
     double inv[PPL];
     if (!merged) {
-        if (flags & 16) {
+        if (flags & FD_CONST_NUM) {
             const double c = FD(ni_c0);
 #pragma unroll
             for (int q = 0; q < PPL; ++q) inv[q] = c;
@@ -326,7 +344,7 @@ __device__ __forceinline__ void lean_date(int t, const int64_t (&i)[PPL], const 
 #pragma unroll
             for (int q = 0; q < PPL; ++q) val[q] = fma(w, mcx_exp_tab(fma(c1, reg[q][r], c0), etab, ec), val[q]);
         }
-        if (flags & 512) {                                 // plain option payoff (european_option.py:45-68)
+        if (flags & FD_OPTION) {                                 // plain option payoff (european_option.py:45-68)
             const double strike = FD(op_strike), sign = FD(op_sign);
 #pragma unroll
             for (int q = 0; q < PPL; ++q) val[q] = fmax(sign * (val[q] - strike), 0.0);
@@ -334,7 +352,7 @@ __device__ __forceinline__ void lean_date(int t, const int64_t (&i)[PPL], const 
 #pragma unroll
         for (int q = 0; q < PPL; ++q) cfs[q] = fma(val[q], inv[q], cfs[q]);
     }
-    if (flags & 128) {
+    if (flags & FD_EXERCISE) {
         // exercise event of the two-state product (bermudan_option.py:93-131): exercise iff the immediate value exceeds the
         // regression continuation value and a right is left; the (up to ~64) exponential terms of the immediate value come
         // through scalar loads, one 32-byte record per term, and serve both paths of the lane
@@ -343,7 +361,7 @@ __device__ __forceinline__ void lean_date(int t, const int64_t (&i)[PPL], const 
         // the whole value as ONE verified polynomial of the state variable (mcx_vpoly.hip: ~20 multiply-adds for both paths of the
         // lane instead of ~15 VALU per term and path); a wave that holds a path outside the verified range runs the terms
         bool collapsed = false;
-        if (flags & 1024) {
+        if (flags & FD_EX_VPOLY) {
             const double lo = FD(ex_p_lo), hi = FD(ex_p_hi);
             const int pr = FD(ex_p_reg);
             bool in = true;
@@ -403,13 +421,13 @@ __device__ __forceinline__ void lean_date(int t, const int64_t (&i)[PPL], const 
     double p[PPL];
 #pragma unroll
     for (int q = 0; q < PPL; ++q) p[q] = 0.0;
-    if (flags & 2) {
+    if (flags & FD_EXPO) {
         const double xa = FD(x_a), xd = FD(x_d);
         const int xr = FD(x_reg), off0 = FD(coeff_off0), off1 = FD(coeff_off1);
         double x[PPL];
 #pragma unroll
         for (int q = 0; q < PPL; ++q) x[q] = fma(xd, reg[q][xr], xa);
-        if (flags & 256) {
+        if (flags & FD_STATE_EXPO) {
             // exposure of the exercise product: the coefficient row of the lane's state (product.py:150-184)
             double p0[PPL], p1[PPL];
 #pragma unroll
@@ -456,12 +474,12 @@ __device__ __forceinline__ void lean_date(int t, const int64_t (&i)[PPL], const 
             for (int q = 0; q < PPL; ++q) if (live[q]) a.expo[(int64_t)row * a.ld_out + i[q]] = e[q];
         }
     }
-    if (flags & 32) {
+    if (flags & FD_METRIC) {
         const double thr = FD(thr);
         double u[PPL];
 #pragma unroll
         for (int q = 0; q < PPL; ++q) u[q] = dev_thr(e[q], thr);
-        if (flags & 8) {
+        if (flags & FD_PROFILE) {
             const int rp = FD(rec_profile);
             double up[PPL], un[PPL];
 #pragma unroll
@@ -469,7 +487,7 @@ __device__ __forceinline__ void lean_date(int t, const int64_t (&i)[PPL], const 
             lean_record<PPL>(up, live, rp, a.n_rec, first_tile, lds);
             lean_record<PPL>(un, live, rp + 1, a.n_rec, first_tile, lds);
         }
-        if (flags & 4) {
+        if (flags & FD_CVA) {
             const double sb = FD(s_b), sc0 = FD(s_c0), sc1 = FD(s_c1);
             const int sr = FD(s_reg);
             double sp[PPL], cs[PPL];

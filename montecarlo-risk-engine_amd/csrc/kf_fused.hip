@@ -47,7 +47,7 @@ __device__ __forceinline__ void kf_on_date(KArgs& a, int t, int64_t i, bool live
         struct { int kind, flags, term_begin, term_end, coeff_off, ns, sidx, init_state; double strike, sign; const FAtom &num, &x; } e =
             {RFL(ev.kind), RFL(ev.flags), RFL(ev.term_begin), RFL(ev.term_end), RFL(ev.coeff_off), RFL(ev.ns), RFL(ev.sidx),
              RFL(ev.init_state), ev.strike, ev.sign, ev.num, ev.x};
-        if (!(e.flags & 2)) inv_num = 1.0 / f_atom<NREG>(e.num, reg);       // flag bit1: same numeraire as the previous event
+        if (!(e.flags & FE_SAME_NUM)) inv_num = 1.0 / f_atom<NREG>(e.num, reg);
         double v = 0.0;
         if (e.kind <= MCX_EV_EXERCISE) {
             double val = 0.0, glog = 0.0;
@@ -360,28 +360,29 @@ void launch_kf(const FusedArgs& a, int grid, size_t lds, const KfRoute& r, bool 
 }  // namespace
 
 struct mcx_fused {
-    const mcx_sim* sim;
-    const mcx_book* book;
-    int n_rec, n_ns, n_dates, n_expo_rows, n_stateful, want_pv;
-    unsigned char* d_prog;
-    FastDate* d_fast;
-    int32_t* d_date_off;
-    int32_t* d_date_row;
-    int chunk_cap, npf, max_chunk;      // max_chunk: bytes of the largest interpreted chunk (0: none)
-    int lean;                  // every date has a FastDate record kf_lean.hip can run (valid != 0)
-    FastDateCva* d_cva;        // [n_dates] when every date runs in the cva-date kernel of kf_lean.hip, else nullptr
-    int cva_steps;             // (d_cva) sub-steps up to and including the last one that stores a date with a CVA increment
-    LeanTerm* d_lterms;
-    double* d_vcoef;           // this object's copy of the exercise-value polynomial coefficients (the book may rebuild its own)
-    int32_t rec_pv[MCX_FUSED_MAX_NS], rec_cva[MCX_FUSED_MAX_NS];
-    double lgd[MCX_FUSED_MAX_NS];
-    int32_t init_state[MCX_FUSED_MAX_STATEFUL];
-    double* d_partials;
-    size_t partial_bytes;
-    mcx_acc* d_out;
+    const mcx_sim* sim = nullptr;
+    const mcx_book* book = nullptr;
+    int n_rec = 0, n_ns = 0, n_dates = 0, n_expo_rows = 0, n_stateful = 0, want_pv = 0;
+    unsigned char* d_prog = nullptr;
+    FastDate* d_fast = nullptr;
+    int32_t* d_date_off = nullptr;
+    int32_t* d_date_row = nullptr;
+    int chunk_cap = 0, npf = 0, max_chunk = 0;      // max_chunk: bytes of the largest interpreted chunk (0: none)
+    int lean = 0;              // every date has a FastDate record kf_lean.hip can run (valid != 0)
+    FastDateCva* d_cva = nullptr;      // [n_dates] when every date runs in the cva-date kernel of kf_lean.hip, else nullptr
+    int cva_steps = 0;         // (d_cva) sub-steps up to and including the last one that stores a date with a CVA increment
+    LeanTerm* d_lterms = nullptr;
+    double* d_vcoef = nullptr; // this object's copy of the exercise-value polynomial coefficients (the book may rebuild its own)
+    int32_t rec_pv[MCX_FUSED_MAX_NS] = {}, rec_cva[MCX_FUSED_MAX_NS] = {};
+    double lgd[MCX_FUSED_MAX_NS] = {};
+    int32_t init_state[MCX_FUSED_MAX_STATEFUL] = {};
+    std::vector<int32_t> date_desc;    // [n_dates][2] host copy of every FastDate's (valid, flags): what mcx_fused_describe reports
+    double* d_partials = nullptr;
+    size_t partial_bytes = 0;
+    mcx_acc* d_out = nullptr;
     // optional timing of the main kernel alone (mcx_fused_set_timing): event pairs around its launch, on the launch stream
-    mutable hipEvent_t tev[2 * MCX_FUSED_TIMING_RING];
-    mutable int timing, t_count, t_launch;      // timing: 0 off, k > 0: every k-th launch is timed
+    mutable hipEvent_t tev[2 * MCX_FUSED_TIMING_RING] = {};
+    mutable int timing = 0, t_count = 0, t_launch = 0;      // timing: 0 off, k > 0: every k-th launch is timed
 };
 
 static void fused_timing_off(mcx_fused* f)
@@ -427,346 +428,478 @@ extern "C" void mcx_fused_destroy(mcx_fused* f)
 
 extern "C" int mcx_fused_num_records(const mcx_fused* f) { return f ? f->n_rec : -1; }
 
-extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_book* book, const mcx_fused_desc* d, mcx_fused** out)
+// ---- mcx_fused_create: the plan of a pass, built on the host stage by stage (no stage calls HIP), then uploaded -----------------
+namespace {
+
+// What the stages decide: the tables the kernels read, exactly as uploaded, and the scalars of the launch.
+struct FusedPlan {
+    std::vector<unsigned char> prog;       // chunks of the interpreted dates (header | events | terms | metric ops), 16-byte aligned
+    std::vector<FastDate> fast;            // [n_dates] (a date that is not straight-line keeps what was derived before it failed)
+    std::vector<FastDateCva> cva_dates;    // [n_dates], uploaded when cva_only
+    std::vector<LeanTerm> lterms;          // exponential terms of the exercise values + one spare entry
+    std::vector<double> vcoef;             // value-polynomial coefficients + one spare block
+    std::vector<int32_t> date_off, date_row;
+    int n_rec = 0, n_stateful = 0, npf = 0, chunk_cap = 0, max_chunk = 0, cva_steps = 0;
+    bool lean = false, cva_only = false;
+    int32_t rec_pv[MCX_FUSED_MAX_NS], rec_cva[MCX_FUSED_MAX_NS];
+    double lgd[MCX_FUSED_MAX_NS];
+    int32_t init_state[MCX_FUSED_MAX_STATEFUL] = {};
+};
+
+// the book's program per timeline date before it is packed or turned into FastDate records (product order preserved)
+struct DateLists {
+    std::vector<std::vector<FEvent>> events;
+    std::vector<std::vector<int>> event_q;          // book index of each bucketed event
+    std::vector<std::vector<FTerm>> terms;
+    std::vector<std::vector<FMetricOp>> mops;
+    explicit DateLists(int T) : events(T), event_q(T), terms(T), mops(T) {}
+};
+
+// why the book is not fusable: the reason recorded last is the one reported (the stages stop at the end of the event or metric
+// operation that recorded it)
+struct Refusal {
+    bool ok = true;
+    std::string why;
+    void operator()(const char* reason) { ok = false; why = reason; }
+};
+
+// stage 1: the arguments, in the order their failures are reported
+int check_arguments(mcx_handle* h, const mcx_sim_desc& sd, const mcx_book* book, const mcx_fused_desc* d)
 {
-    if (!h || !sim || !book || !d || !out) return -1;
-    const mcx_sim_desc& sd = sim->desc;
     if (book->n_state != sd.n_state) MCX_FAIL(h, -2, "mcx_fused_create: book and sim disagree on the state dimension");
     if (d->n_netting_sets < 1 || d->n_netting_sets > MCX_FUSED_MAX_NS || d->n_netting_sets != book->n_netting_sets)
         MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: %d netting sets (max %d)", book->n_netting_sets, MCX_FUSED_MAX_NS);
     if (d->n_expo_rows != book->n_expo_rows) MCX_FAIL(h, -2, "mcx_fused_create: n_expo_rows mismatch");
-    const int T = sd.n_dates;
     for (int s = 0; s < sd.n_slots; ++s)
         if (sd.slots[s].kind == MCX_MODEL_S2F) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: the Schwartz two-factor spot is a derived state column");
-    // state column -> lane register
-    int col_reg[MCX_MAX_STATE];
+    if ((int)book->h_event_t_idx.size() != book->n_events) MCX_FAIL(h, -2, "mcx_fused_create: internal (event dates missing)");
+    return 0;
+}
+
+// state column -> lane register
+void state_registers(const mcx_sim_desc& sd, int (&col_reg)[MCX_MAX_STATE])
+{
     for (int s = 0; s < sd.n_slots; ++s) {
         col_reg[sd.slots[s].state_off] = 2 * s;
         if (sd.slots[s].kind != MCX_MODEL_BS) col_reg[sd.slots[s].state_off + 1] = 2 * s + 1;
     }
-    bool ok = true;
-    std::string why;
-    auto fatom = [&](const mcx_atom& q, int t_event) {
-        FAtom o; o.a = q.a; o.d = q.d; o.b = q.b; o.c0 = q.c0; o.c1 = q.c1; o.reg = -1;
-        o.pad = (q.b != 0.0 ? 1 : 0) | ((q.a != 0.0 || q.d != 0.0) ? 2 : 0);
-        if (q.col >= 0) {
-            if (q.t_idx != t_event) { ok = false; why = "an event reads the state of another date (unequal swap tenors)"; }
-            o.reg = col_reg[q.col];
-        }
-        return o;
-    };
-    const DevEventVec& hev = book->h_events;
-    const std::vector<DevTerm>& hte = book->h_terms;
-    auto devatom_to_mcx = [](const DevAtom& q) { mcx_atom o; o.t_idx = q.t_idx; o.col = q.col; o.a = q.a; o.d = q.d; o.b = q.b; o.c0 = q.c0; o.c1 = q.c1; return o; };
+}
 
-    // events bucketed by timeline date, product order preserved
-    std::vector<std::vector<FEvent>> by_date(T);
-    std::vector<std::vector<int>> by_date_q(T);              // book index of each bucketed event
-    std::vector<std::vector<FTerm>> terms_by_date(T);
-    int n_stateful = 0;
-    int32_t init_state[MCX_FUSED_MAX_STATEFUL] = {0, 0, 0, 0};
-    if ((int)book->h_event_t_idx.size() != book->n_events) MCX_FAIL(h, -2, "mcx_fused_create: internal (event dates missing)");
-    for (int p = 0; p < book->n_products && ok; ++p) {
-        const DevProduct& pr = book->h_products[p];
+FAtom fatom(const mcx_atom& q, int t_event, const int* col_reg, Refusal& no)
+{
+    FAtom o; o.a = q.a; o.d = q.d; o.b = q.b; o.c0 = q.c0; o.c1 = q.c1; o.reg = -1;
+    o.parts = (q.b != 0.0 ? FA_EXP : 0) | ((q.a != 0.0 || q.d != 0.0) ? FA_AFFINE : 0);
+    if (q.col >= 0) {
+        if (q.t_idx != t_event) no("an event reads the state of another date (unequal swap tenors)");
+        o.reg = col_reg[q.col];
+    }
+    return o;
+}
+FAtom fatom(const DevAtom& q, int t_event, const int* col_reg, Refusal& no)
+{
+    mcx_atom o; o.t_idx = q.t_idx; o.col = q.col; o.a = q.a; o.d = q.d; o.b = q.b; o.c0 = q.c0; o.c1 = q.c1;
+    return fatom(o, t_event, col_reg, no);
+}
+
+// stage 2: the book's events and their terms bucketed by timeline date; the slots and initial states of the exercise products
+void bucket_events(const mcx_book& book, int T, const int* col_reg, FusedPlan& p, DateLists& dl, Refusal& no)
+{
+    const DevEventVec& hev = book.h_events;
+    const std::vector<DevTerm>& hte = book.h_terms;
+    for (int pi = 0; pi < book.n_products && no.ok; ++pi) {
+        const DevProduct& pr = book.h_products[pi];
         if (pr.ev_end == pr.ev_begin) continue;
         int sidx = -1;
         if (pr.n_states > 1) {
-            if (n_stateful >= MCX_FUSED_MAX_STATEFUL) { ok = false; why = "too many exercise products"; break; }
-            sidx = n_stateful;
-            init_state[n_stateful++] = pr.init_state;
+            if (p.n_stateful >= MCX_FUSED_MAX_STATEFUL) { no("too many exercise products"); break; }
+            sidx = p.n_stateful;
+            p.init_state[p.n_stateful++] = pr.init_state;
         }
-        for (int q = pr.ev_begin; q < pr.ev_end && ok; ++q) {
+        for (int q = pr.ev_begin; q < pr.ev_end && no.ok; ++q) {
             const DevEvent& e = hev[q];
-            const int t = book->h_event_t_idx[q];
-            if (t < 0 || t >= T) { ok = false; why = "event date out of range"; break; }
+            const int t = book.h_event_t_idx[q];
+            if (t < 0 || t >= T) { no("event date out of range"); break; }
             FEvent fe;
             memset(&fe, 0, sizeof(fe));
             fe.kind = e.kind; fe.flags = e.flags; fe.coeff_off = e.coeff_off; fe.row = e.row; fe.ns = pr.netting_set; fe.sidx = sidx;
-            fe.init_state = pr.init_state; fe.pad = pr.n_states; fe.strike = e.strike; fe.sign = e.sign;
+            fe.init_state = pr.init_state; fe.n_states = pr.n_states; fe.strike = e.strike; fe.sign = e.sign;
             for (int w = 0; w < 4; ++w) fe.aux[w] = e.aux[w];
-            if (e.kind == MCX_EV_OPTION && (e.aux[0] == 4.0 || e.aux[0] == 5.0)) { ok = false; why = "barrier monitoring is evaluated by the book kernel (K2)"; }
-            fe.num = fatom(devatom_to_mcx(e.num), t);
-            fe.x = fatom(devatom_to_mcx(e.x), t);
-            std::vector<FTerm>& terms = terms_by_date[t];
+            if (e.kind == MCX_EV_OPTION && (e.aux[0] == 4.0 || e.aux[0] == 5.0)) no("barrier monitoring is evaluated by the book kernel (K2)");
+            fe.num = fatom(e.num, t, col_reg, no);
+            fe.x = fatom(e.x, t, col_reg, no);
+            std::vector<FTerm>& terms = dl.terms[t];
             fe.term_begin = (int)terms.size();
             for (int j = e.term_begin; j < e.term_end; ++j) {
-                if (hte[j].den >= 0) { ok = false; why = "a cashflow term carries its own numeraire (unequal swap tenors)"; break; }
-                FTerm ft; ft.w = hte[j].w; ft.atom = fatom(devatom_to_mcx(hte[j].atom), t);
+                if (hte[j].den >= 0) { no("a cashflow term carries its own numeraire (unequal swap tenors)"); break; }
+                FTerm ft; ft.w = hte[j].w; ft.atom = fatom(hte[j].atom, t, col_reg, no);
                 terms.push_back(ft);
             }
             fe.term_end = (int)terms.size();
-            // numeraire identical to the previous event of this date: reuse 1/numeraire (flag bit1)
-            if (!by_date[t].empty() && memcmp(&by_date[t].back().num, &fe.num, sizeof(FAtom)) == 0) fe.flags |= 2;
-            else fe.flags &= ~2;
-            by_date[t].push_back(fe);
-            by_date_q[t].push_back(q);
+            // numeraire identical to the previous event of this date: reuse 1/numeraire
+            if (!dl.events[t].empty() && memcmp(&dl.events[t].back().num, &fe.num, sizeof(FAtom)) == 0) fe.flags |= FE_SAME_NUM;
+            else fe.flags &= ~FE_SAME_NUM;
+            dl.events[t].push_back(fe);
+            dl.event_q[t].push_back(q);
         }
     }
-    // metric ops
-    std::vector<std::vector<FMetricOp>> mop_by_date(T);
-    std::vector<int32_t> date_row(T, -1);
-    for (int r = 0; r < d->n_expo_rows; ++r) {
-        const int t = d->row_t_idx[r];
-        if (t < 0 || t >= T) MCX_FAIL(h, -2, "mcx_fused_create: exposure row %d has no timeline date", r);
-        date_row[t] = r;
-    }
-    mcx_fused* f = new mcx_fused();
-    memset(f, 0, sizeof(*f));
-    int n_rec = 0;
-    for (int k = 0; k < MCX_FUSED_MAX_NS; ++k) { f->rec_pv[k] = -1; f->rec_cva[k] = -1; f->lgd[k] = 0.0; }
-    for (int k = 0; k < d->n_netting_sets && ok; ++k) {
-        const mcx_fused_ns_desc& nd = d->ns[k];
-        if (nd.netting_set != k) { ok = false; why = "netting-set descriptors must be in order"; break; }
-        if (d->want_pv) f->rec_pv[k] = n_rec++;
+}
+
+// stage 3: the numbering of the records ([PV][2 n_dates profiles][CVA] per netting set) and the metric operations of every date
+void build_metric_ops(const mcx_book& book, const mcx_fused_desc& d, const int* col_reg, FusedPlan& p, DateLists& dl, Refusal& no)
+{
+    for (int k = 0; k < MCX_FUSED_MAX_NS; ++k) { p.rec_pv[k] = -1; p.rec_cva[k] = -1; p.lgd[k] = 0.0; }
+    for (int k = 0; k < d.n_netting_sets && no.ok; ++k) {
+        const mcx_fused_ns_desc& nd = d.ns[k];
+        if (nd.netting_set != k) { no("netting-set descriptors must be in order"); break; }
+        if (d.want_pv) p.rec_pv[k] = p.n_rec++;
         int rec_prof = -1;
-        if (nd.want_profiles) { rec_prof = n_rec; n_rec += 2 * nd.n_dates; }
-        if (nd.want_cva) { f->rec_cva[k] = n_rec++; f->lgd[k] = 1.0 - nd.recovery; }
+        if (nd.want_profiles) { rec_prof = p.n_rec; p.n_rec += 2 * nd.n_dates; }
+        if (nd.want_cva) { p.rec_cva[k] = p.n_rec++; p.lgd[k] = 1.0 - nd.recovery; }
         for (int m = 0; m < nd.n_dates; ++m) {
             const int row = nd.row[m];
-            if (row < 0 || row >= d->n_expo_rows) { ok = false; why = "metric row out of range"; break; }
-            const int t = d->row_t_idx[row];
+            if (row < 0 || row >= d.n_expo_rows) { no("metric row out of range"); break; }
+            const int t = d.row_t_idx[row];
             FMetricOp mo;
             memset(&mo, 0, sizeof(mo));
             mo.ns = k; mo.m = m; mo.threshold = nd.threshold;
             mo.rec_profile = nd.want_profiles ? rec_prof + 2 * m : -1;
             mo.has_cva = (nd.want_cva && m < nd.n_dates - 1) ? 1 : 0;
-            mo.surv.reg = -1; mo.cond.reg = -1; mo.surv.pad = 0; mo.cond.pad = 0;
+            mo.surv.reg = -1; mo.cond.reg = -1; mo.surv.parts = 0; mo.cond.parts = 0;
             if (mo.has_cva) {
                 const int sa = nd.surv_atoms[m], ca = nd.cond_atoms[m];
-                if (sa < 0 || sa >= book->n_atoms || ca < 0 || ca >= book->n_atoms) { ok = false; why = "CVA atom out of range"; break; }
-                mo.surv = fatom(book->h_atoms[sa], t);
-                mo.cond = fatom(book->h_atoms[ca], t);
+                if (sa < 0 || sa >= book.n_atoms || ca < 0 || ca >= book.n_atoms) { no("CVA atom out of range"); break; }
+                mo.surv = fatom(book.h_atoms[sa], t, col_reg, no);
+                mo.cond = fatom(book.h_atoms[ca], t, col_reg, no);
             }
-            if (mo.rec_profile >= 0 || mo.has_cva) mop_by_date[t].push_back(mo);
+            if (mo.rec_profile >= 0 || mo.has_cva) dl.mops[t].push_back(mo);
         }
     }
-    if (!ok) { delete f; MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: %s", why.c_str()); }
-    if (n_rec < 1) { delete f; MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: no reducible metric requested"); }
-    if ((size_t)9 * n_rec * sizeof(double) > 48 * 1024) { delete f; MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: %d records exceed the LDS budget", n_rec); }
+}
 
-    // straight-line records for dates of the linear-book shape (FastDate); such dates need no interpreted chunk
-    std::vector<FastDate> fast(T);
-    std::vector<LeanTerm> lterms;
-    std::vector<double> vcoef;
-    const bool fast_dates_enabled = d->n_netting_sets == 1;
-    for (int t = 0; t < T; ++t) {
-        FastDate fd;
-        memset(&fd, 0, sizeof(fd));
-        fd.ni_reg = fd.lin_reg = fd.x_reg = fd.s_reg = fd.c_reg = -1;
-        fd.coeff_off0 = fd.coeff_off1 = -1; fd.rec_profile = -1;
-        for (int j = 0; j < 4; ++j) fd.t_reg[j] = -1;
-        bool okf = fast_dates_enabled;
-        const FAtom* num = nullptr;
-        int n_expo = 0;
-        for (size_t ei = 0; ei < by_date[t].size(); ++ei) {
-            const FEvent& e = by_date[t][ei];
-            if (!okf) break;
-            const bool stateful = e.sidx >= 0;
-            if (stateful && (e.sidx != 0 || e.pad != 2 || d->n_netting_sets != 1)) { okf = false; break; }      // one two-state product
-            const bool plain_option = e.kind == MCX_EV_OPTION && e.aux[0] == 0.0 && !stateful;
-            if (e.kind != MCX_EV_CASHFLOW && e.kind != MCX_EV_EXPO_POLY && !plain_option &&
-                !(e.kind == MCX_EV_EXERCISE && stateful && e.aux[0] == 0.0)) { okf = false; break; }
-            if (stateful && e.kind == MCX_EV_CASHFLOW) { okf = false; break; }
-            if ((plain_option || e.kind == MCX_EV_CASHFLOW) && (fd.flags & 512)) { okf = false; break; }      // the payoff's max() stands alone
-            if (plain_option) {
-                if (fd.flags & 1) { okf = false; break; }
-                fd.flags |= 512;
-                fd.op_strike = e.strike; fd.op_sign = e.sign;
-            }
-            if (num && memcmp(num, &e.num, sizeof(FAtom)) != 0) { okf = false; break; }     // one numeraire per date
-            num = &e.num;
-            if (e.kind == MCX_EV_EXERCISE) {
-                if ((fd.flags & (128 | 2)) || e.x.b != 0.0) { okf = false; break; }            // one exercise event, before the exposure
-                fd.flags |= 128;
-                fd.ex_term_off = (int32_t)lterms.size(); fd.ex_coeff_off = e.coeff_off; fd.ex_strike = e.strike; fd.ex_sign = e.sign;
-                fd.ex_x_reg = e.x.reg; fd.ex_x_a = e.x.a; fd.ex_x_d = e.x.d; fd.ex_lin_reg = -1;
-                for (int j = e.term_begin; j < e.term_end && okf; ++j) {
-                    const FTerm& tm = terms_by_date[t][j];
-                    fd.ex_k0 += tm.w * tm.atom.a;
-                    if (tm.atom.d != 0.0) {
-                        if (fd.ex_lin_reg >= 0 && fd.ex_lin_reg != tm.atom.reg) okf = false;
-                        fd.ex_lin_reg = tm.atom.reg; fd.ex_k1 += tm.w * tm.atom.d;
-                    }
-                    if (tm.atom.b != 0.0) {
-                        if (tm.atom.reg < 0 || tm.atom.c1 == 0.0) fd.ex_k0 += tm.w * tm.atom.b * exp(tm.atom.c0);      // state-independent term
-                        else { LeanTerm lt; lt.w = tm.w * tm.atom.b; lt.c0 = tm.atom.c0; lt.c1 = tm.atom.c1; lt.reg = tm.atom.reg; lt.pad = 0; lterms.push_back(lt); }
-                    }
-                }
-                fd.ex_n = (int32_t)lterms.size() - fd.ex_term_off;
-                // the book's verified value polynomial of this event (mcx_book_collapse_values), copied into this object
-                const int vq = book->h_event_vpoly.empty() ? -1 : book->h_event_vpoly[by_date_q[t][ei]];
-                if (okf && vq >= 0) {
-                    const DevVPoly& vp = book->h_vpoly[vq];
-                    fd.flags |= 1024;
-                    fd.ex_p_lo = vp.lo; fd.ex_p_hi = vp.hi; fd.ex_p_ms = vp.ms; fd.ex_p_ih = vp.ih;
-                    fd.ex_p_off = (int32_t)vcoef.size(); fd.ex_p_blk = vp.n_blk; fd.ex_p_reg = col_reg[vp.col];
-                    vcoef.insert(vcoef.end(), book->h_vcoef.begin() + vp.coef_off, book->h_vcoef.begin() + vp.coef_off + (size_t)vp.n_blk * MCX_VPOLY_BLK);
-                }
-                continue;
-            }
-            if (e.kind == MCX_EV_CASHFLOW || plain_option) {
-                fd.flags |= 1;
-                for (int j = e.term_begin; j < e.term_end && okf; ++j) {
-                    const FTerm& tm = terms_by_date[t][j];
-                    fd.k0 += tm.w * tm.atom.a;
-                    if (tm.atom.d != 0.0) {
-                        if (fd.lin_reg >= 0 && fd.lin_reg != tm.atom.reg) okf = false;
-                        fd.lin_reg = tm.atom.reg; fd.k1 += tm.w * tm.atom.d;
-                    }
-                    if (tm.atom.b != 0.0) {
-                        if (fd.n_exp >= 4) { okf = false; break; }
-                        fd.t_reg[fd.n_exp] = tm.atom.reg; fd.t_w[fd.n_exp] = tm.w * tm.atom.b;
-                        fd.t_c0[fd.n_exp] = tm.atom.c0; fd.t_c1[fd.n_exp] = tm.atom.c1; fd.n_exp++;
-                    }
-                }
-            } else {
-                if (e.x.b != 0.0 || n_expo >= 2) { okf = false; break; }
-                if ((fd.flags & 2) && (fd.x_reg != e.x.reg || fd.x_a != e.x.a || fd.x_d != e.x.d)) { okf = false; break; }
-                if (stateful && n_expo > 0) { okf = false; break; }                            // the state-indexed exposure stands alone
-                if ((fd.flags & 256)) { okf = false; break; }
-                fd.flags |= 2; fd.x_reg = e.x.reg; fd.x_a = e.x.a; fd.x_d = e.x.d;
-                int off = e.coeff_off >= 0 ? e.coeff_off + e.init_state * book->n_basis : -1;
-                if (stateful) { fd.flags |= 256; off = e.coeff_off; if (off < 0) { okf = false; break; } }
-                (n_expo == 0 ? fd.coeff_off0 : fd.coeff_off1) = off;
-                n_expo++;
-            }
+// ---- stage 4: the FastDate record of one date.  Each piece returns false when the date is not of the straight-line shape; the
+// record keeps what was derived up to that point (it is uploaded with valid = 0 and never read).
+
+// the affine part w (a + d x) of a term joins k0 + k1 reg[lin_reg]; false: the date's terms are linear in two registers
+bool fold_affine(const FTerm& tm, double& k0, double& k1, int32_t& lin_reg)
+{
+    k0 += tm.w * tm.atom.a;
+    if (tm.atom.d == 0.0) return true;
+    const bool one_reg = lin_reg < 0 || lin_reg == tm.atom.reg;
+    lin_reg = tm.atom.reg; k1 += tm.w * tm.atom.d;
+    return one_reg;
+}
+
+// the exercise event of the one two-state product: immediate value (affine part + LeanTerm range, and the book's verified value
+// polynomial of the event, mcx_book_collapse_values, copied into this object) against the regression continuation value
+bool fast_exercise(const FEvent& e, int q_book, const std::vector<FTerm>& terms, const mcx_book& book, const int* col_reg, FusedPlan& p,
+                   FastDate& fd)
+{
+    if ((fd.flags & (FD_EXERCISE | FD_EXPO)) || e.x.b != 0.0) return false;            // one exercise event, before the exposure
+    fd.flags |= FD_EXERCISE;
+    fd.ex_term_off = (int32_t)p.lterms.size(); fd.ex_coeff_off = e.coeff_off; fd.ex_strike = e.strike; fd.ex_sign = e.sign;
+    fd.ex_x_reg = e.x.reg; fd.ex_x_a = e.x.a; fd.ex_x_d = e.x.d; fd.ex_lin_reg = -1;
+    bool ok = true;
+    for (int j = e.term_begin; j < e.term_end && ok; ++j) {
+        const FTerm& tm = terms[j];
+        ok = fold_affine(tm, fd.ex_k0, fd.ex_k1, fd.ex_lin_reg);
+        if (tm.atom.b != 0.0) {
+            if (tm.atom.reg < 0 || tm.atom.c1 == 0.0) fd.ex_k0 += tm.w * tm.atom.b * exp(tm.atom.c0);      // state-independent term
+            else { LeanTerm lt; lt.w = tm.w * tm.atom.b; lt.c0 = tm.atom.c0; lt.c1 = tm.atom.c1; lt.reg = tm.atom.reg; lt.pad = 0; p.lterms.push_back(lt); }
         }
-        if (okf && num) {
-            if (num->a == 0.0 && num->d == 0.0 && num->b > 0.0) { fd.ni_reg = num->reg; fd.ni_c0 = -num->c0 - log(num->b); fd.ni_c1 = -num->c1; }
-            else if (num->b == 0.0 && num->d == 0.0 && num->a != 0.0) { fd.flags |= 16; fd.ni_c0 = 1.0 / num->a; }
-            else okf = false;
-        }
-        if (okf && mop_by_date[t].size() > 1) okf = false;
-        if (okf && mop_by_date[t].size() == 1) {
-            const FMetricOp& mo = mop_by_date[t][0];
-            fd.flags |= 32; fd.thr = mo.threshold;
-            if (mo.rec_profile >= 0) { fd.flags |= 8; fd.rec_profile = mo.rec_profile; }
-            if (mo.has_cva) {
-                if (mo.surv.a != 0.0 || mo.surv.d != 0.0 || mo.cond.d != 0.0) okf = false;
-                fd.flags |= 4;
-                fd.s_reg = mo.surv.reg; fd.s_b = mo.surv.b; fd.s_c0 = mo.surv.c0; fd.s_c1 = mo.surv.c1;
-                fd.c_reg = mo.cond.reg; fd.c_a = mo.cond.a; fd.c_b = mo.cond.b; fd.c_c0 = mo.cond.c0; fd.c_c1 = mo.cond.c1;
-            }
-        }
-        if (okf && !num && !mop_by_date[t].empty()) { fd.flags |= 16; fd.ni_c0 = 1.0; }      // metric op on an empty date
-        // a state reference that is absent (reg < 0) becomes register 0 with a zero coefficient: the kernels may then index the
-        // lane's state registers without a range test
-        auto bind = [](int32_t& r, double& coef) { if (r < 0) { r = 0; coef = 0.0; } };
-        bind(fd.ni_reg, fd.ni_c1); bind(fd.lin_reg, fd.k1); bind(fd.x_reg, fd.x_d); bind(fd.s_reg, fd.s_c1); bind(fd.c_reg, fd.c_c1);
-        bind(fd.ex_x_reg, fd.ex_x_d); bind(fd.ex_lin_reg, fd.ex_k1);
-        for (int j = 0; j < 4; ++j) bind(fd.t_reg[j], fd.t_c1[j]);
-        // merged discount x survival factor of the CVA increment: relu(p / N) S (1 - Sc) = relu(p) (S / N) (1 - Sc) when the date
-        // has no threshold and records no EPE / ENE profile: one exponential instead of two
-        if (okf && (fd.flags & 4) && !(fd.flags & 8) && fd.thr == 0.0) {
-            fd.flags |= 64;
-            if (fd.flags & 16) { fd.m_b = fd.s_b * fd.ni_c0; fd.m_c0 = fd.s_c0; fd.m_n1 = 0.0; }
-            else { fd.m_b = fd.s_b; fd.m_c0 = fd.s_c0 + fd.ni_c0; fd.m_n1 = fd.ni_c1; }
-            fd.m_s1 = fd.s_c1;
-        }
-        if (!okf) lterms.resize(fd.ex_term_off <= (int32_t)lterms.size() && (fd.flags & 128) ? fd.ex_term_off : lterms.size());
-        fd.valid = okf ? 1 : 0;
-        fast[t] = fd;
     }
-    // per-date program chunks: header | events | terms | metric ops, 16-byte aligned
-    std::vector<unsigned char> prog;
-    std::vector<int32_t> date_off(T + 1, 0);
-    int max_chunk = 0;
-    bool bs_exposure = false;
-    for (int t = 0; t < T; ++t) for (const FEvent& e : by_date[t]) if (e.kind == MCX_EV_EXPO_BS) bs_exposure = true;
+    fd.ex_n = (int32_t)p.lterms.size() - fd.ex_term_off;
+    if (!ok) return false;
+    const int vq = book.h_event_vpoly.empty() ? -1 : book.h_event_vpoly[q_book];
+    if (vq >= 0) {
+        const DevVPoly& vp = book.h_vpoly[vq];
+        fd.flags |= FD_EX_VPOLY;
+        fd.ex_p_lo = vp.lo; fd.ex_p_hi = vp.hi; fd.ex_p_ms = vp.ms; fd.ex_p_ih = vp.ih;
+        fd.ex_p_off = (int32_t)p.vcoef.size(); fd.ex_p_blk = vp.n_blk; fd.ex_p_reg = col_reg[vp.col];
+        p.vcoef.insert(p.vcoef.end(), book.h_vcoef.begin() + vp.coef_off, book.h_vcoef.begin() + vp.coef_off + (size_t)vp.n_blk * MCX_VPOLY_BLK);
+    }
+    return true;
+}
+
+// a cashflow or a plain option payoff: affine part + at most four exponential terms in the record itself
+bool fast_cash(const FEvent& e, const std::vector<FTerm>& terms, FastDate& fd)
+{
+    fd.flags |= FD_CASH;
+    bool ok = true;
+    for (int j = e.term_begin; j < e.term_end && ok; ++j) {
+        const FTerm& tm = terms[j];
+        ok = fold_affine(tm, fd.k0, fd.k1, fd.lin_reg);
+        if (tm.atom.b != 0.0) {
+            if (fd.n_exp >= 4) return false;
+            fd.t_reg[fd.n_exp] = tm.atom.reg; fd.t_w[fd.n_exp] = tm.w * tm.atom.b;
+            fd.t_c0[fd.n_exp] = tm.atom.c0; fd.t_c1[fd.n_exp] = tm.atom.c1; fd.n_exp++;
+        }
+    }
+    return ok;
+}
+
+// a polynomial exposure: at most two rows in one explanatory variable, or the state-indexed rows of the exercise product alone
+bool fast_exposure(const FEvent& e, int n_basis, FastDate& fd, int& n_expo)
+{
+    const bool stateful = e.sidx >= 0;
+    if (e.x.b != 0.0 || n_expo >= 2) return false;
+    if ((fd.flags & FD_EXPO) && (fd.x_reg != e.x.reg || fd.x_a != e.x.a || fd.x_d != e.x.d)) return false;
+    if (stateful && n_expo > 0) return false;                                          // the state-indexed exposure stands alone
+    if (fd.flags & FD_STATE_EXPO) return false;
+    fd.flags |= FD_EXPO; fd.x_reg = e.x.reg; fd.x_a = e.x.a; fd.x_d = e.x.d;
+    int off = e.coeff_off >= 0 ? e.coeff_off + e.init_state * n_basis : -1;
+    if (stateful) { fd.flags |= FD_STATE_EXPO; off = e.coeff_off; if (off < 0) return false; }
+    (n_expo == 0 ? fd.coeff_off0 : fd.coeff_off1) = off;
+    n_expo++;
+    return true;
+}
+
+// one event of the date; num: the date's one numeraire so far
+bool fast_event(const FEvent& e, int q_book, const std::vector<FTerm>& terms, const mcx_book& book, const int* col_reg, FusedPlan& p,
+                FastDate& fd, const FAtom*& num, int& n_expo)
+{
+    const bool stateful = e.sidx >= 0;
+    if (stateful && (e.sidx != 0 || e.n_states != 2)) return false;                    // one two-state product
+    const bool plain_option = e.kind == MCX_EV_OPTION && e.aux[0] == 0.0 && !stateful;
+    if (e.kind != MCX_EV_CASHFLOW && e.kind != MCX_EV_EXPO_POLY && !plain_option &&
+        !(e.kind == MCX_EV_EXERCISE && stateful && e.aux[0] == 0.0)) return false;
+    if (stateful && e.kind == MCX_EV_CASHFLOW) return false;
+    if ((plain_option || e.kind == MCX_EV_CASHFLOW) && (fd.flags & FD_OPTION)) return false;      // the payoff's max() stands alone
+    if (plain_option) {
+        if (fd.flags & FD_CASH) return false;
+        fd.flags |= FD_OPTION;
+        fd.op_strike = e.strike; fd.op_sign = e.sign;
+    }
+    if (num && memcmp(num, &e.num, sizeof(FAtom)) != 0) return false;                  // one numeraire per date
+    num = &e.num;
+    if (e.kind == MCX_EV_EXERCISE) return fast_exercise(e, q_book, terms, book, col_reg, p, fd);
+    if (e.kind == MCX_EV_CASHFLOW || plain_option) return fast_cash(e, terms, fd);
+    return fast_exposure(e, book.n_basis, fd, n_expo);
+}
+
+// 1/numeraire of the date's events: a pure exponential of one register, or a constant
+bool fast_numeraire(const FAtom& num, FastDate& fd)
+{
+    if (num.a == 0.0 && num.d == 0.0 && num.b > 0.0) { fd.ni_reg = num.reg; fd.ni_c0 = -num.c0 - log(num.b); fd.ni_c1 = -num.c1; }
+    else if (num.b == 0.0 && num.d == 0.0 && num.a != 0.0) { fd.flags |= FD_CONST_NUM; fd.ni_c0 = 1.0 / num.a; }
+    else return false;
+    return true;
+}
+
+// at most one metric operation: its threshold, its EPE / ENE records, its CVA increment (pure-exponential survival)
+bool fast_metric_op(const std::vector<FMetricOp>& mops, FastDate& fd)
+{
+    if (mops.size() > 1) return false;
+    if (mops.empty()) return true;
+    const FMetricOp& mo = mops[0];
+    bool ok = true;
+    fd.flags |= FD_METRIC; fd.thr = mo.threshold;
+    if (mo.rec_profile >= 0) { fd.flags |= FD_PROFILE; fd.rec_profile = mo.rec_profile; }
+    if (mo.has_cva) {
+        if (mo.surv.a != 0.0 || mo.surv.d != 0.0 || mo.cond.d != 0.0) ok = false;
+        fd.flags |= FD_CVA;
+        fd.s_reg = mo.surv.reg; fd.s_b = mo.surv.b; fd.s_c0 = mo.surv.c0; fd.s_c1 = mo.surv.c1;
+        fd.c_reg = mo.cond.reg; fd.c_a = mo.cond.a; fd.c_b = mo.cond.b; fd.c_c0 = mo.cond.c0; fd.c_c1 = mo.cond.c1;
+    }
+    return ok;
+}
+
+// merged discount x survival factor of the CVA increment: relu(p / N) S (1 - Sc) = relu(p) (S / N) (1 - Sc) when the date has no
+// threshold and records no EPE / ENE profile: one exponential instead of two
+void fast_merged_factor(FastDate& fd)
+{
+    if (!(fd.flags & FD_CVA) || (fd.flags & FD_PROFILE) || fd.thr != 0.0) return;
+    fd.flags |= FD_MERGED;
+    if (fd.flags & FD_CONST_NUM) { fd.m_b = fd.s_b * fd.ni_c0; fd.m_c0 = fd.s_c0; fd.m_n1 = 0.0; }
+    else { fd.m_b = fd.s_b; fd.m_c0 = fd.s_c0 + fd.ni_c0; fd.m_n1 = fd.ni_c1; }
+    fd.m_s1 = fd.s_c1;
+}
+
+// the straight-line record of date t (valid = 1), for a date of the linear-book shape in a book of one netting set; any other
+// date is interpreted from its chunk (valid = 0)
+FastDate build_fast_date(int t, const mcx_book& book, const mcx_fused_desc& d, const int* col_reg, const DateLists& dl, FusedPlan& p)
+{
+    FastDate fd;
+    memset(&fd, 0, sizeof(fd));
+    fd.ni_reg = fd.lin_reg = fd.x_reg = fd.s_reg = fd.c_reg = -1;
+    fd.coeff_off0 = fd.coeff_off1 = -1; fd.rec_profile = -1;
+    for (int j = 0; j < 4; ++j) fd.t_reg[j] = -1;
+    const std::vector<FMetricOp>& mops = dl.mops[t];
+    const FAtom* num = nullptr;
+    int n_expo = 0;
+    bool ok = d.n_netting_sets == 1;
+    for (size_t ei = 0; ei < dl.events[t].size() && ok; ++ei)
+        ok = fast_event(dl.events[t][ei], dl.event_q[t][ei], dl.terms[t], book, col_reg, p, fd, num, n_expo);
+    if (ok && num) ok = fast_numeraire(*num, fd);
+    ok = ok && fast_metric_op(mops, fd);
+    if (ok && !num && !mops.empty()) { fd.flags |= FD_CONST_NUM; fd.ni_c0 = 1.0; }      // metric op on an empty date
+    // a state reference that is absent (reg < 0) becomes register 0 with a zero coefficient: the kernels may then index the
+    // lane's state registers without a range test
+    auto bind = [](int32_t& r, double& coef) { if (r < 0) { r = 0; coef = 0.0; } };
+    bind(fd.ni_reg, fd.ni_c1); bind(fd.lin_reg, fd.k1); bind(fd.x_reg, fd.x_d); bind(fd.s_reg, fd.s_c1); bind(fd.c_reg, fd.c_c1);
+    bind(fd.ex_x_reg, fd.ex_x_d); bind(fd.ex_lin_reg, fd.ex_k1);
+    for (int j = 0; j < 4; ++j) bind(fd.t_reg[j], fd.t_c1[j]);
+    if (ok) fast_merged_factor(fd);
+    if (!ok && (fd.flags & FD_EXERCISE)) p.lterms.resize(fd.ex_term_off);      // the terms of an exercise value that is interpreted after all
+    fd.valid = ok ? 1 : 0;
+    return fd;
+}
+
+// stage 5: the chunks of the interpreted dates (header | events | terms | metric ops, 16-byte aligned) and the size of a wave's
+// program slot; a straight-line date is evaluated from its FastDate record by lean_date and has no chunk
+void pack_chunks(const DateLists& dl, FusedPlan& p)
+{
+    const int T = (int)p.fast.size();
+    p.date_off.assign(T + 1, 0);
     for (int t = 0; t < T; ++t) {
-        date_off[t] = (int32_t)prog.size();
-        if (fast[t].valid) continue;                   // evaluated from its FastDate record by lean_date: no interpreted chunk
+        p.date_off[t] = (int32_t)p.prog.size();
+        if (p.fast[t].valid) continue;
+        const std::vector<FEvent>& ev = dl.events[t];
+        const std::vector<FTerm>& tm = dl.terms[t];
+        const std::vector<FMetricOp>& mo = dl.mops[t];
         ChunkHeader hd;
-        hd.n_ev = (int)by_date[t].size(); hd.n_mop = (int)mop_by_date[t].size(); hd.n_terms = (int)terms_by_date[t].size();
-        const size_t bytes = sizeof(hd) + sizeof(FEvent) * by_date[t].size() + sizeof(FTerm) * terms_by_date[t].size() +
-                             sizeof(FMetricOp) * mop_by_date[t].size();
+        hd.n_ev = (int)ev.size(); hd.n_mop = (int)mo.size(); hd.n_terms = (int)tm.size();
+        const size_t bytes = sizeof(hd) + sizeof(FEvent) * ev.size() + sizeof(FTerm) * tm.size() + sizeof(FMetricOp) * mo.size();
         const size_t padded = (bytes + 15) & ~(size_t)15;
         hd.bytes = (int32_t)padded;
-        const size_t base = prog.size();
-        prog.resize(base + padded, 0);
-        unsigned char* p = prog.data() + base;
-        memcpy(p, &hd, sizeof(hd)); p += sizeof(hd);
-        if (hd.n_ev) { memcpy(p, by_date[t].data(), sizeof(FEvent) * by_date[t].size()); p += sizeof(FEvent) * by_date[t].size(); }
-        if (hd.n_terms) { memcpy(p, terms_by_date[t].data(), sizeof(FTerm) * terms_by_date[t].size()); p += sizeof(FTerm) * terms_by_date[t].size(); }
-        if (hd.n_mop) memcpy(p, mop_by_date[t].data(), sizeof(FMetricOp) * mop_by_date[t].size());
-        max_chunk = std::max(max_chunk, (int)padded);
+        const size_t base = p.prog.size();
+        p.prog.resize(base + padded, 0);
+        unsigned char* dst = p.prog.data() + base;
+        memcpy(dst, &hd, sizeof(hd)); dst += sizeof(hd);
+        if (hd.n_ev) { memcpy(dst, ev.data(), sizeof(FEvent) * ev.size()); dst += sizeof(FEvent) * ev.size(); }
+        if (hd.n_terms) { memcpy(dst, tm.data(), sizeof(FTerm) * tm.size()); dst += sizeof(FTerm) * tm.size(); }
+        if (hd.n_mop) memcpy(dst, mo.data(), sizeof(FMetricOp) * mo.size());
+        p.max_chunk = std::max(p.max_chunk, (int)padded);
     }
-    date_off[T] = (int32_t)prog.size();
-    if (bs_exposure) { delete f; MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: analytic Black-Scholes exposures are evaluated by the book kernel (K2)"); }
-    bool lean = d->n_netting_sets == 1 && n_stateful <= 1;
-    for (int t = 0; t < T; ++t) lean = lean && fast[t].valid != 0;
+    p.date_off[T] = (int32_t)p.prog.size();
+    p.prog.resize(p.prog.size() + 4096, 0);       // slack so the fixed-size prefetch of the last chunk stays in bounds
     // no interpreted date at all: no program slots (NPF = 0, chunk_cap = 0)
-    f->npf = max_chunk == 0 ? 0 : (max_chunk <= 1024 ? 1 : (max_chunk <= 2048 ? 2 : 0));
-    f->chunk_cap = f->npf > 0 ? f->npf * 1024 : ((max_chunk + 255) & ~255);
-    f->max_chunk = max_chunk;
+    p.npf = p.max_chunk == 0 ? 0 : (p.max_chunk <= 1024 ? 1 : (p.max_chunk <= 2048 ? 2 : 0));
+    p.chunk_cap = p.npf > 0 ? p.npf * 1024 : ((p.max_chunk + 255) & ~255);
+}
+
+// every date straight-line in a book kf_lean.hip can run
+bool straight_line_book(const mcx_sim_desc& sd, const mcx_fused_desc& d, const FusedPlan& p)
+{
+    bool lean = d.n_netting_sets == 1 && p.n_stateful <= 1;
+    for (const FastDate& fd : p.fast) lean = lean && fd.valid != 0;
     // the straight-line kernel skips the zero test under the CIR++ diffusion root: it needs a positive initial intensity (the
     // reference asserts y0 > 0, cirpp.py:40; the state is floored at 1e-12 after every step); other starts run the interpreter
     for (int q = 0; q < sd.n_slots; ++q)
         if (sd.slots[q].kind == MCX_MODEL_CIRPP && !(sd.init_state[sd.slots[q].state_off] > 0.0)) lean = false;
-    f->lean = lean ? 1 : 0;
-    // the cva-date kernel of kf_lean.hip: a Vasicek + CIR++ (Euler) CVA book without a PV record whose every date either is the merged
-    // CVA increment of lean_date (regression exposure of n_basis = 3, no threshold, no EPE / ENE record, no exercise, a conditional
-    // survival that depends on the state) on the signature's canonical registers, or has no effect on the CVA
-    std::vector<FastDateCva> cva_dates(T);
-    bool cva_only = lean && mcx_sim_signature(sd) == SIG_VAS_CIR_E && f->rec_pv[0] < 0 && f->rec_cva[0] >= 0 && book->n_basis == 3;
-    for (int t = 0; t < T && cva_only; ++t) {
-        const FastDate& fd = fast[t];
-        FastDateCva& c = cva_dates[t];
+    return lean;
+}
+
+// the merged CVA increment and nothing else: what the cva-date kernel evaluates
+bool is_cva_increment(const FastDate& fd) { return (fd.flags & (FD_MERGED | FD_EXERCISE | FD_STATE_EXPO)) == FD_MERGED; }
+
+// stage 6: the cva-date kernel of kf_lean.hip: a Vasicek + CIR++ (Euler) CVA book without a PV record whose every date either is the
+// merged CVA increment of lean_date (regression exposure of n_basis = 3, no threshold, no EPE / ENE record, no exercise, a
+// conditional survival that depends on the state) on the signature's canonical registers, or has no effect on the CVA
+void build_cva_dates(const mcx_sim& sim, const mcx_book& book, FusedPlan& p)
+{
+    const int T = (int)p.fast.size();
+    p.cva_dates.resize(T);
+    p.cva_only = p.lean && mcx_sim_signature(sim.desc) == SIG_VAS_CIR_E && p.rec_pv[0] < 0 && p.rec_cva[0] >= 0 && book.n_basis == 3;
+    for (int t = 0; t < T && p.cva_only; ++t) {
+        const FastDate& fd = p.fast[t];
+        FastDateCva& c = p.cva_dates[t];
         memset(&c, 0, sizeof(c));
         c.coeff_off0 = c.coeff_off1 = -1;
-        if ((fd.flags & (64 | 128 | 256)) == 64) {
-            cva_only = fd.c_b != 0.0 && fd.s_reg == FDC_S_REG && fd.ni_reg == FDC_NI_REG && fd.c_reg == FDC_C_REG && fd.x_reg == FDC_X_REG;
+        if (is_cva_increment(fd)) {
+            p.cva_only = fd.c_b != 0.0 && fd.s_reg == FDC_S_REG && fd.ni_reg == FDC_NI_REG && fd.c_reg == FDC_C_REG && fd.x_reg == FDC_X_REG;
             c.m_s1 = fd.m_s1; c.m_n1 = fd.m_n1; c.m_c0 = fd.m_c0; c.m_b = fd.m_b;
             c.c_c1 = fd.c_c1; c.c_c0 = fd.c_c0; c.c_a = fd.c_a; c.c_b = fd.c_b;
             c.x_d = fd.x_d; c.x_a = fd.x_a;
-            if (fd.flags & 2) { c.coeff_off0 = fd.coeff_off0; c.coeff_off1 = fd.coeff_off1; }
-        } else if (fd.flags & (32 | 128 | 256)) {
-            cva_only = false;          // a threshold, an EPE / ENE record or an exercise: the general program
+            if (fd.flags & FD_EXPO) { c.coeff_off0 = fd.coeff_off0; c.coeff_off1 = fd.coeff_off1; }
+        } else if (fd.flags & (FD_METRIC | FD_EXERCISE | FD_STATE_EXPO)) {
+            p.cva_only = false;        // a threshold, an EPE / ENE record or an exercise: the general program
         }
     }
     // The dates after the last CVA increment are all-zero records: each adds +0.0 to the CVA, so the cva-date kernel need not
     // simulate up to them.  cva_steps is the index just past the last sub-step that stores a date with an increment.
     int cva_steps = 0;
-    for (size_t k = 0; k < sim->h_steps.size() && cva_only; ++k) {
-        const int st = sim->h_steps[k].store_idx;
-        if (st >= 0 && st < T && (fast[st].flags & (64 | 128 | 256)) == 64) cva_steps = (int)k + 1;
+    for (size_t k = 0; k < sim.h_steps.size() && p.cva_only; ++k) {
+        const int st = sim.h_steps[k].store_idx;
+        if (st >= 0 && st < T && is_cva_increment(p.fast[st])) cva_steps = (int)k + 1;
     }
     // (a book without any increment: nothing to stop at, the whole table like every other kernel)
-    f->cva_steps = cva_steps > 0 ? cva_steps : (int)sim->h_steps.size();
-    // LDS budget: 4 wave slots + the record area (dynamic) must fit comfortably; with kf_fused's static tables (Box-Muller 4 KiB,
-    // exponential 1 KiB) a block holds at most 65 KiB of the CU's 160 KiB
-    if ((size_t)4 * f->chunk_cap + sizeof(double) * 9 * (size_t)n_rec > 60 * 1024) {
-        delete f;
-        MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: a date's event program (%d B) exceeds the per-wave LDS slot budget", max_chunk);
-    }
+    p.cva_steps = cva_steps > 0 ? cva_steps : (int)sim.h_steps.size();
+}
 
-    f->sim = sim; f->book = book; f->n_rec = n_rec; f->n_ns = d->n_netting_sets; f->n_dates = T; f->n_expo_rows = d->n_expo_rows;
-    f->n_stateful = n_stateful; f->want_pv = d->want_pv;
-    for (int q = 0; q < MCX_FUSED_MAX_STATEFUL; ++q) f->init_state[q] = init_state[q];
-    auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, bytes ? bytes : 8);
+// stage 7, the only one that touches the device: the accepted plan becomes a mcx_fused
+int upload(mcx_handle* h, const mcx_sim* sim, const mcx_book* book, const mcx_fused_desc& d, const FusedPlan& p, mcx_fused** out)
+{
+    mcx_fused* f = new mcx_fused();
+    f->sim = sim; f->book = book; f->n_rec = p.n_rec; f->n_ns = d.n_netting_sets; f->n_dates = (int)p.fast.size(); f->n_expo_rows = d.n_expo_rows;
+    f->n_stateful = p.n_stateful; f->want_pv = d.want_pv;
+    f->npf = p.npf; f->chunk_cap = p.chunk_cap; f->max_chunk = p.max_chunk; f->lean = p.lean ? 1 : 0; f->cva_steps = p.cva_steps;
+    for (int k = 0; k < MCX_FUSED_MAX_NS; ++k) { f->rec_pv[k] = p.rec_pv[k]; f->rec_cva[k] = p.rec_cva[k]; f->lgd[k] = p.lgd[k]; }
+    for (int q = 0; q < MCX_FUSED_MAX_STATEFUL; ++q) f->init_state[q] = p.init_state[q];
+    for (const FastDate& fd : p.fast) { f->date_desc.push_back(fd.valid); f->date_desc.push_back(fd.flags); }
+    auto up = [&](auto** dst, const auto& src) -> hipError_t {
+        const size_t bytes = sizeof(src[0]) * src.size();
+        hipError_t e = hipMalloc((void**)dst, bytes ? bytes : 8);
         if (e != hipSuccess) return e;
-        return bytes ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+        return bytes ? hipMemcpy(*dst, src.data(), bytes, hipMemcpyHostToDevice) : hipSuccess;
     };
-    prog.resize(prog.size() + 4096, 0);       // slack so the fixed-size prefetch of the last chunk stays in bounds
-    lterms.resize(lterms.size() + 1);          // never empty
-    vcoef.resize(vcoef.size() + MCX_VPOLY_BLK, 0.0);      // the spare block the kernels prefetch
-    f->partial_bytes = sizeof(double) * 4 * (size_t)n_rec * 2048;
-    hipError_t e = up((void**)&f->d_prog, prog.data(), prog.size());
-    if (e == hipSuccess) e = up((void**)&f->d_fast, fast.data(), sizeof(FastDate) * fast.size());
-    if (e == hipSuccess && cva_only) e = up((void**)&f->d_cva, cva_dates.data(), sizeof(FastDateCva) * cva_dates.size());
-    if (e == hipSuccess) e = up((void**)&f->d_lterms, lterms.data(), sizeof(LeanTerm) * lterms.size());
-    if (e == hipSuccess) e = up((void**)&f->d_vcoef, vcoef.data(), sizeof(double) * vcoef.size());
-    if (e == hipSuccess) e = up((void**)&f->d_date_off, date_off.data(), sizeof(int32_t) * date_off.size());
-    if (e == hipSuccess) e = up((void**)&f->d_date_row, date_row.data(), sizeof(int32_t) * date_row.size());
+    f->partial_bytes = sizeof(double) * 4 * (size_t)p.n_rec * 2048;
+    hipError_t e = up(&f->d_prog, p.prog);
+    if (e == hipSuccess) e = up(&f->d_fast, p.fast);
+    if (e == hipSuccess && p.cva_only) e = up(&f->d_cva, p.cva_dates);
+    if (e == hipSuccess) e = up(&f->d_lterms, p.lterms);
+    if (e == hipSuccess) e = up(&f->d_vcoef, p.vcoef);
+    if (e == hipSuccess) e = up(&f->d_date_off, p.date_off);
+    if (e == hipSuccess) e = up(&f->d_date_row, p.date_row);
     if (e == hipSuccess) e = hipMalloc(&f->d_partials, f->partial_bytes);
-    if (e == hipSuccess) e = hipMalloc(&f->d_out, sizeof(mcx_acc) * (size_t)n_rec);
+    if (e == hipSuccess) e = hipMalloc(&f->d_out, sizeof(mcx_acc) * (size_t)p.n_rec);
     if (e != hipSuccess) {                                   // nothing leaks: the partially built object is destroyed
         mcx_fused_destroy(f);
         MCX_FAIL(h, -100 - (int)e, "mcx_fused_create: %s", hipGetErrorString(e));
     }
     *out = f;
     return 0;
+}
+
+}  // namespace
+
+extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_book* book, const mcx_fused_desc* d, mcx_fused** out)
+{
+    if (!h || !sim || !book || !d || !out) return -1;
+    const mcx_sim_desc& sd = sim->desc;
+    if (const int rc = check_arguments(h, sd, book, d)) return rc;
+    const int T = sd.n_dates;
+    int col_reg[MCX_MAX_STATE];
+    state_registers(sd, col_reg);
+
+    FusedPlan p;
+    DateLists dl(T);
+    Refusal no;
+    bucket_events(*book, T, col_reg, p, dl, no);
+    p.date_row.assign(T, -1);
+    for (int r = 0; r < d->n_expo_rows; ++r) {
+        const int t = d->row_t_idx[r];
+        if (t < 0 || t >= T) MCX_FAIL(h, -2, "mcx_fused_create: exposure row %d has no timeline date", r);
+        p.date_row[t] = r;
+    }
+    build_metric_ops(*book, *d, col_reg, p, dl, no);
+    if (!no.ok) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: %s", no.why.c_str());
+    if (p.n_rec < 1) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: no reducible metric requested");
+    if ((size_t)9 * p.n_rec * sizeof(double) > 48 * 1024) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: %d records exceed the LDS budget", p.n_rec);
+
+    for (int t = 0; t < T; ++t) p.fast.push_back(build_fast_date(t, *book, *d, col_reg, dl, p));
+    p.lterms.resize(p.lterms.size() + 1);          // never empty: the spare term the kernels prefetch
+    p.vcoef.resize(p.vcoef.size() + MCX_VPOLY_BLK, 0.0);      // the spare block the kernels prefetch
+    pack_chunks(dl, p);
+    for (int t = 0; t < T; ++t)
+        for (const FEvent& e : dl.events[t])
+            if (e.kind == MCX_EV_EXPO_BS) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: analytic Black-Scholes exposures are evaluated by the book kernel (K2)");
+    p.lean = straight_line_book(sd, *d, p);
+    build_cva_dates(*sim, *book, p);
+    // LDS budget: 4 wave slots + the record area (dynamic) must fit comfortably; with kf_fused's static tables (Box-Muller 4 KiB,
+    // exponential 1 KiB) a block holds at most 65 KiB of the CU's 160 KiB
+    if ((size_t)4 * p.chunk_cap + sizeof(double) * 9 * (size_t)p.n_rec > 60 * 1024)
+        MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: a date's event program (%d B) exceeds the per-wave LDS slot budget", p.max_chunk);
+    return upload(h, sim, book, *d, p, out);
 }
 
 // the one place that decides which kernel a pass runs (fused_run_impl launches it, mcx_fused_describe reports it)
@@ -837,25 +970,10 @@ static int fused_run_impl(mcx_handle* h, const mcx_fused* f, bool simulate, uint
         // keep the tiles-per-block count integral when possible (equal work per block)
         if (tiles > 2048) { int per = (int)((tiles + 2047) / 2048); grid = (int)((tiles + per - 1) / per); }
         const size_t lds = sizeof(double) * (size_t)((9 * f->n_rec + 1) & ~1) + (size_t)4 * f->chunk_cap;
-        switch (mcx_sim_signature(sd)) {
-        case SIG_VAS_CIR_E: launch_kf<2, 2, SIG_VAS_CIR_E>(a, grid, lds, route, simulate, s); break;
-        case SIG_BS_A: launch_kf<1, 1, SIG_BS_A>(a, grid, lds, route, simulate, s); break;
-        case SIG_BS_E: launch_kf<1, 1, SIG_BS_E>(a, grid, lds, route, simulate, s); break;
-        case SIG_HESTON_QE: launch_kf<1, 2, SIG_HESTON_QE>(a, grid, lds, route, simulate, s); break;
-        case SIG_HESTON_E: launch_kf<1, 2, SIG_HESTON_E>(a, grid, lds, route, simulate, s); break;
-        case SIG_VAS_E: launch_kf<1, 1, SIG_VAS_E>(a, grid, lds, route, simulate, s); break;
-        case SIG_VAS_A: launch_kf<1, 1, SIG_VAS_A>(a, grid, lds, route, simulate, s); break;
-        case SIG_BS_VAS_CIRDET_E: launch_kf<3, 3, SIG_BS_VAS_CIRDET_E>(a, grid, lds, route, simulate, s); break;
-        default:
-            switch (sd.n_slots * 16 + sd.n_z) {
-            case 1 * 16 + 1: launch_kf<1, 1, SIG_GENERIC>(a, grid, lds, route, simulate, s); break;
-            case 1 * 16 + 2: launch_kf<1, 2, SIG_GENERIC>(a, grid, lds, route, simulate, s); break;
-            case 2 * 16 + 2: launch_kf<2, 2, SIG_GENERIC>(a, grid, lds, route, simulate, s); break;
-            case 3 * 16 + 3: launch_kf<3, 3, SIG_GENERIC>(a, grid, lds, route, simulate, s); break;
-            case 4 * 16 + 4: launch_kf<4, 4, SIG_GENERIC>(a, grid, lds, route, simulate, s); break;
-            default: MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: (slots=%d, z=%d) has no fused instantiation", sd.n_slots, sd.n_z);
-            }
-        }
+        const bool launched = mcx_dispatch_signature<4>(sd, [&](auto nslot, auto nz, auto sig) {
+            launch_kf<decltype(nslot)::value, decltype(nz)::value, decltype(sig)::value>(a, grid, lds, route, simulate, s);
+        });
+        if (!launched) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "not fusable: (slots=%d, z=%d) has no fused instantiation", sd.n_slots, sd.n_z);
     }
     MCX_HIP(h, hipGetLastError());
     if (timed) { MCX_HIP(h, hipEventRecord(f->tev[2 * f->t_count + 1], s)); ++f->t_count; }
@@ -885,9 +1003,7 @@ extern "C" int mcx_fused_describe(const mcx_fused* f, int32_t inject, int32_t si
     o[MCX_FDESC_N_NS] = f->n_ns; o[MCX_FDESC_N_STATEFUL] = f->n_stateful; o[MCX_FDESC_N_DATES] = f->n_dates;
     o[MCX_FDESC_CVA_DATES] = f->d_cva != nullptr;
     o[MCX_FDESC_KERNEL] = r.kernel; o[MCX_FDESC_NNS] = r.nns; o[MCX_FDESC_NST] = r.nst; o[MCX_FDESC_KNPF] = r.npf;
-    std::vector<FastDate> fast(f->n_dates);
-    if (f->n_dates > 0 && hipMemcpy(fast.data(), f->d_fast, sizeof(FastDate) * fast.size(), hipMemcpyDeviceToHost) != hipSuccess) return -100;
-    for (int t = 0; t < f->n_dates; ++t) { o[MCX_FDESC_HEADER + 2 * t] = fast[t].valid; o[MCX_FDESC_HEADER + 2 * t + 1] = fast[t].flags; }
+    if (f->n_dates > 0) memcpy(o + MCX_FDESC_HEADER, f->date_desc.data(), sizeof(int32_t) * 2 * f->n_dates);
     return need;
 }
 

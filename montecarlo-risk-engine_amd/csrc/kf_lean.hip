@@ -521,28 +521,13 @@ void launch_lean(const FusedArgs& a, int full_steps, int n_cu, bool inject, bool
 int mcx_launch_kf_lean(const FusedArgs& a, const mcx_sim_desc& sd, int n_cu, bool inject, bool simulate, hipStream_t s)
 {
     int grid = -1;
-    switch (mcx_sim_signature(sd)) {
-    case SIG_VAS_CIR_E: launch_lean<2, 2, SIG_VAS_CIR_E>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-#ifndef MCX_LEAN_ONE_SIG
-    case SIG_BS_A: launch_lean<1, 1, SIG_BS_A>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-    case SIG_BS_E: launch_lean<1, 1, SIG_BS_E>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-    case SIG_HESTON_QE: launch_lean<1, 2, SIG_HESTON_QE>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-    case SIG_HESTON_E: launch_lean<1, 2, SIG_HESTON_E>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-    case SIG_VAS_E: launch_lean<1, 1, SIG_VAS_E>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-    case SIG_VAS_A: launch_lean<1, 1, SIG_VAS_A>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-    case SIG_BS_VAS_CIRDET_E: launch_lean<3, 3, SIG_BS_VAS_CIRDET_E>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-    default:
-        switch (sd.n_slots * 16 + sd.n_z) {
-        case 1 * 16 + 1: launch_lean<1, 1, SIG_GENERIC>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-        case 1 * 16 + 2: launch_lean<1, 2, SIG_GENERIC>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-        case 2 * 16 + 2: launch_lean<2, 2, SIG_GENERIC>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-        case 3 * 16 + 3: launch_lean<3, 3, SIG_GENERIC>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-        case 4 * 16 + 4: launch_lean<4, 4, SIG_GENERIC>(a, sd.n_steps, n_cu, inject, simulate, s, &grid); break;
-        default: break;
-        }
+#ifdef MCX_LEAN_ONE_SIG
+    // tools/asm_mix.py only (never defined in the product build): the one signature it measures, nothing else instantiated
+    if (mcx_sim_signature(sd) == SIG_VAS_CIR_E) launch_lean<2, 2, SIG_VAS_CIR_E>(a, sd.n_steps, n_cu, inject, simulate, s, &grid);
 #else
-    default: break;
+    mcx_dispatch_signature<4>(sd, [&](auto nslot, auto nz, auto sig) {
+        launch_lean<decltype(nslot)::value, decltype(nz)::value, decltype(sig)::value>(a, sd.n_steps, n_cu, inject, simulate, s, &grid);
+    });
 #endif
-    }
     return grid;
 }

@@ -1,6 +1,8 @@
 // mcx_device.h — device functions shared by the path kernel (k1_paths.hip) and the fused kernel (kf_fused.hip):
 // Philox4x32-10, Box-Muller, the per-model sub-step maps.  gfx950 only.
 #pragma once
+#include <type_traits>
+
 #include "mcx_internal.h"
 
 struct K1Args {
@@ -364,6 +366,39 @@ static inline int mcx_sim_signature(const mcx_sim_desc& d)
         if (k(0) == MCX_MODEL_VASICEK) return d.scheme == MCX_SCHEME_EULER ? SIG_VAS_E : d.scheme == MCX_SCHEME_ANALYTICAL ? SIG_VAS_A : SIG_GENERIC;
     }
     return SIG_GENERIC;
+}
+
+// The one map from a simulation descriptor to the <NSLOT, NZ, SIG> instantiation of a kernel family (host): calls
+// f(NSLOT, NZ, SIG), three std::integral_constant<int, ...> values, for the named signatures and for the generic (slots, z) shapes
+// (1,1), (1,2), (2,2), (3,3), (4,4) and (5,5) .. (MAXN,MAXN).  Returns false, f not called, when the family has no instantiation.
+template <int N> using mcx_int = std::integral_constant<int, N>;
+template <int MAXN, class F>
+bool mcx_dispatch_signature(const mcx_sim_desc& d, F&& f)
+{
+    static_assert(MAXN >= 4 && MAXN <= 8, "generic instantiations exist up to 4 .. 8 slots");
+    switch (mcx_sim_signature(d)) {       // specialised (compile-time model kinds) instantiations of the hot configurations
+    case SIG_VAS_CIR_E: f(mcx_int<2>(), mcx_int<2>(), mcx_int<SIG_VAS_CIR_E>()); return true;
+    case SIG_BS_A: f(mcx_int<1>(), mcx_int<1>(), mcx_int<SIG_BS_A>()); return true;
+    case SIG_BS_E: f(mcx_int<1>(), mcx_int<1>(), mcx_int<SIG_BS_E>()); return true;
+    case SIG_HESTON_QE: f(mcx_int<1>(), mcx_int<2>(), mcx_int<SIG_HESTON_QE>()); return true;
+    case SIG_HESTON_E: f(mcx_int<1>(), mcx_int<2>(), mcx_int<SIG_HESTON_E>()); return true;
+    case SIG_VAS_E: f(mcx_int<1>(), mcx_int<1>(), mcx_int<SIG_VAS_E>()); return true;
+    case SIG_VAS_A: f(mcx_int<1>(), mcx_int<1>(), mcx_int<SIG_VAS_A>()); return true;
+    case SIG_BS_VAS_CIRDET_E: f(mcx_int<3>(), mcx_int<3>(), mcx_int<SIG_BS_VAS_CIRDET_E>()); return true;
+    default: break;
+    }
+    switch (d.n_slots * 16 + d.n_z) {
+    case 1 * 16 + 1: f(mcx_int<1>(), mcx_int<1>(), mcx_int<SIG_GENERIC>()); return true;
+    case 1 * 16 + 2: f(mcx_int<1>(), mcx_int<2>(), mcx_int<SIG_GENERIC>()); return true;
+    case 2 * 16 + 2: f(mcx_int<2>(), mcx_int<2>(), mcx_int<SIG_GENERIC>()); return true;
+    case 3 * 16 + 3: f(mcx_int<3>(), mcx_int<3>(), mcx_int<SIG_GENERIC>()); return true;
+    case 4 * 16 + 4: f(mcx_int<4>(), mcx_int<4>(), mcx_int<SIG_GENERIC>()); return true;
+    case 5 * 16 + 5: if constexpr (MAXN >= 5) { f(mcx_int<5>(), mcx_int<5>(), mcx_int<SIG_GENERIC>()); return true; } return false;
+    case 6 * 16 + 6: if constexpr (MAXN >= 6) { f(mcx_int<6>(), mcx_int<6>(), mcx_int<SIG_GENERIC>()); return true; } return false;
+    case 7 * 16 + 7: if constexpr (MAXN >= 7) { f(mcx_int<7>(), mcx_int<7>(), mcx_int<SIG_GENERIC>()); return true; } return false;
+    case 8 * 16 + 8: if constexpr (MAXN >= 8) { f(mcx_int<8>(), mcx_int<8>(), mcx_int<SIG_GENERIC>()); return true; } return false;
+    default: return false;
+    }
 }
 
 // compile-time recursion over the slots (the slot index must be a constant expression for the signature lookup)

@@ -81,6 +81,9 @@ FUSED_MAX_STATEFUL = 4
 # mcx_fused_describe (include/mcx.h): MCX_ROUTE_* and the header length MCX_FDESC_HEADER
 ROUTE_NONE, ROUTE_LEAN, ROUTE_FUSED = 0, 1, 2
 FDESC_HEADER = 16
+# MCX_FD_*: flag bits of a date's straight-line record, as mcx_fused_describe reports them
+(FD_CASH, FD_EXPO, FD_CVA, FD_PROFILE, FD_CONST_NUM, FD_METRIC, FD_MERGED, FD_EXERCISE, FD_STATE_EXPO, FD_OPTION,
+ FD_EX_VPOLY) = (1 << k for k in range(11))
 # mcx_eval_book_describe (include/mcx.h): MCX_K2_* kernels, MCX_K2F_* event families, MCX_K2DESC_COUNT entries
 K2_SCALAR, K2_CHUNKED, K2_MULTI = 0, 1, 2
 K2F_DEN, K2F_EXOTIC, K2F_EXERCISE, K2F_BS_EXPO = 1, 2, 4, 8

@@ -15,11 +15,12 @@ import numpy as np
 import pytest
 
 import cases
+from mcx import _abi
 from test_cva_date_kernel import _check, _irs_book
 
 pytestmark = pytest.mark.gpu
 
-LIVE = 64 | 128 | 256      # FastDate flags: == 64 is the merged CVA increment (mcx_fused_create)
+LIVE = _abi.FD_MERGED | _abi.FD_EXERCISE | _abi.FD_STATE_EXPO      # FastDate flags: == FD_MERGED is the merged CVA increment (mcx_fused_create)
 
 
 def _controller(be, timeline_end, n_main):
@@ -101,7 +102,7 @@ def test_step_count_follows_the_last_cva_date(timeline_end, hip, oracle):
     at its last simulated date, so the untrimmed count is reached only through the general kernel.)"""
     n = 70001
     sc, res, d = _run_fused(hip, timeline_end, n)
-    live = (d["flags"] & LIVE) == 64
+    live = (d["flags"] & LIVE) == _abi.FD_MERGED
     n_dead = 1 if timeline_end == 3.0 else 5
     assert live[:-n_dead].all() and not live[-n_dead:].any(), d          # 13 quarterly dates, the last n_dead without increment
     eng = sc._main_engine

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import cases
+from mcx import _abi
 
 pytestmark = pytest.mark.gpu
 
@@ -75,7 +76,7 @@ def test_books_off_the_cva_date_kernel(kind, hip, oracle):
     d = out["route"]
     # every date straight-line: kf_lean's general date program, not the cva-date kernel and not the interpreter
     assert d["kernel"] == "lean" and d["lean"] and (d["valid"] == 1).all() and not d["cva_dates"], d
-    assert (d["flags"] & (8 if kind == "added_epe" else 128)).any(), d
+    assert (d["flags"] & (_abi.FD_PROFILE if kind == "added_epe" else _abi.FD_EXERCISE)).any(), d
     _check(out, kind)
 
 

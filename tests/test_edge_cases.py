@@ -303,3 +303,24 @@ def test_library_rejects_scheme_without_step_map_and_short_replay_buffers(hip):
             hip.eval_book(sb.book, paths)
     finally:
         hip.book_set_exercise_replay(sb.book, 0, None)
+
+
+# books mcx_fused_create refuses (the controller then runs the separate kernels), and the reason it gives
+REFUSALS = {
+    "s2f_european": "not fusable: the Schwartz two-factor spot is a derived state column",
+    # (a barrier event is refused for its monitoring and again for the monitoring dates its atoms read: the reason recorded last
+    #  for the event is the one reported)
+    "barrier": "not fusable: an event reads the state of another date (unequal swap tenors)",
+    "bs_european_exposure": "not fusable: analytic Black-Scholes exposures are evaluated by the book kernel (K2)",
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(REFUSALS))
+def test_refused_books_name_the_reason(name, hip):
+    """MCX_E_NOT_FUSABLE (the backend records the text for that code alone) and the reason: one from the argument checks, one
+    collected while the events are bucketed, one from the check that follows the date records"""
+    sc, _ = cases.make_controller(name, hip, inject=False)
+    hip.not_fusable_reason = None
+    sc.prepare()
+    assert sc._fused is None and hip.not_fusable_reason == REFUSALS[name], hip.not_fusable_reason

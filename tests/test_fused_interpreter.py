@@ -266,7 +266,7 @@ def test_two_exercise_products_hand_over_the_first_state(order, inject, hip, ora
         d = _run_case(hip, oracle, ("two_am", order, inject, n), _two_americans(order), n, plan, inject,
                       ("fused", 1, MAXS, 0 if inject else None), exercise=True)
         assert d["n_stateful"] == 2 and "sl->int->sl" in _patterns(d["valid"]), d
-        assert (d["flags"][d["valid"] == 1] & 128).all(), d     # every straight-line date is product 0's exercise
+        assert (d["flags"][d["valid"] == 1] & _abi.FD_EXERCISE).all(), d     # every straight-line date is product 0's exercise
 
 
 MIXES = {
@@ -300,7 +300,7 @@ def test_value_polynomial_fallback_inside_the_interpreter(hip, oracle, monkeypat
     for plan in ("fused", "semi"):
         d = _run_case(hip, oracle, "berm", book, 70001, plan, False, ("fused", 1, MAXS, None), exercise=True, setup=narrow)
         assert not d["lean"] and (d["valid"] == 1).all() and d["max_chunk"] == 0, d
-        assert (d["flags"] & 1024).any() and (d["flags"] & 256).any(), d
+        assert (d["flags"] & _abi.FD_EX_VPOLY).any() and (d["flags"] & _abi.FD_STATE_EXPO).any(), d
     # the paths of that run leave the verified range on some exercise date (read back from the library)
     import ctypes as C
     sc = _controller(book, hip, 70001, "fused", True, False, narrow)
@@ -335,7 +335,8 @@ def test_module_coverage():
     need_routes.add((True, False, True, True, _abi.FUSED_MAX_NS, MAXS, 0))
     assert need_routes <= SEEN["routes"], sorted(need_routes - SEEN["routes"])
     assert {(_abi.FUSED_MAX_NS, 2), (_abi.FUSED_MAX_NS, 4)} <= SEEN["n_ns"], SEEN["n_ns"]
-    flags = 1 | 2 | 4 | 8 | 16 | 32 | 64 | 128 | 256 | 512 | 1024
+    flags = (_abi.FD_CASH | _abi.FD_EXPO | _abi.FD_CVA | _abi.FD_PROFILE | _abi.FD_CONST_NUM | _abi.FD_METRIC | _abi.FD_MERGED |
+             _abi.FD_EXERCISE | _abi.FD_STATE_EXPO | _abi.FD_OPTION | _abi.FD_EX_VPOLY)
     assert SEEN["flags"] & flags == flags, hex(flags & ~SEEN["flags"])
     # an interpreted date right after a straight-line one, its chunk from the prefetch issued in the straight-line branch
     assert {("sl->int", 1), ("sl->int", 2), ("sl->int->sl", 0)} <= SEEN["patterns"], SEEN["patterns"]
