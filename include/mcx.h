@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MCX_ABI_VERSION 6   /* 6: mcx_lsm_run_batch; 5: value polynomials (mcx_book_collapse_values), mcx_book_set_exercise_replay n_rows, mcx_sim_create rejects (model, scheme) pairs without a step map; 4: mcx_unsecured_desc.n_rows, mcx_lsm_step_batch w_len (host-side bounds of every row / offset a kernel reads); 3: mcx_rng_draws, mcx_comm_* (RCCL), interpolated collateral; 2: batched LSM, tangent-book kernels, bridge RNG */
+#define MCX_ABI_VERSION 6   /* 6: mcx_lsm_run_batch, mcx_sim_describe (added without a new number: reads host memory only, changes no layout; a library of version 6 built before it lacks the symbol); 5: value polynomials (mcx_book_collapse_values), mcx_book_set_exercise_replay n_rows, mcx_sim_create rejects (model, scheme) pairs without a step map; 4: mcx_unsecured_desc.n_rows, mcx_lsm_step_batch w_len (host-side bounds of every row / offset a kernel reads); 3: mcx_rng_draws, mcx_comm_* (RCCL), interpolated collateral; 2: batched LSM, tangent-book kernels, bridge RNG */
 
 #define MCX_MAX_SLOTS   8    /* sub-models in one ModelConfig                                  */
 #define MCX_MAX_Z       8    /* total simulation dimension (correlated normals per sub-step)    */
@@ -277,6 +277,14 @@ int  mcx_generate_paths(mcx_handle* h, const mcx_sim* sim, uint64_t seed, uint64
 int  mcx_generate_paths_from_state(mcx_handle* h, const mcx_sim* sim, uint64_t seed, uint64_t path_offset, int64_t n_paths,
                                    int64_t ld, const double* d_init_state, double* d_paths,
                                    const double* d_inject_z, const double* d_inject_u, void* stream);
+
+/* Which instantiation of the path kernel mcx_generate_paths / mcx_generate_paths_from_state launches for `sim`, from the same
+ * host function that chooses the launch: out[0] = MCX_SIG_* (a specialised model signature, compile-time model kinds and scheme;
+ * MCX_SIG_GENERIC: run-time dispatch per slot), out[1] = slots, out[2] = normals per sub-step of the instantiation.  Returns 0,
+ * -1 on an invalid argument, -4 when no instantiation exists (the launch would fail with the same code).  Reads host memory only. */
+enum { MCX_SIG_GENERIC = 0, MCX_SIG_VAS_CIR_E = 1, MCX_SIG_BS_A = 2, MCX_SIG_BS_E = 3, MCX_SIG_HESTON_QE = 4, MCX_SIG_HESTON_E = 5,
+       MCX_SIG_VAS_E = 6, MCX_SIG_VAS_A = 7, MCX_SIG_BS_VAS_CIRDET_E = 8 };
+int  mcx_sim_describe(const mcx_sim* sim, int32_t* out);
 
 /* Probe of the RNG contract above (what the path kernels consume): for i < n the draw (path = path0 + i, step, draw) as
  * d_words [4][n] Philox4x32-10 output words (bit-exact against Random123 / the oracle), d_u [2][n] = (ua, ub) and

@@ -252,6 +252,19 @@ extern "C" void mcx_sim_destroy(mcx_sim* sim)
 static int generate_paths_impl(mcx_handle* h, const mcx_sim* sim, uint64_t seed, uint64_t path_offset, int64_t n_paths, int64_t ld,
                                const double* d_init_state, double* d_paths, const double* d_inject_z, const double* d_inject_u, void* stream);
 
+static_assert(SIG_GENERIC == MCX_SIG_GENERIC && SIG_VAS_CIR_E == MCX_SIG_VAS_CIR_E && SIG_BS_A == MCX_SIG_BS_A && SIG_BS_E == MCX_SIG_BS_E &&
+              SIG_HESTON_QE == MCX_SIG_HESTON_QE && SIG_HESTON_E == MCX_SIG_HESTON_E && SIG_VAS_E == MCX_SIG_VAS_E &&
+              SIG_VAS_A == MCX_SIG_VAS_A && SIG_BS_VAS_CIRDET_E == MCX_SIG_BS_VAS_CIRDET_E, "the public MCX_SIG_* are the kernels' SIG_*");
+
+extern "C" int mcx_sim_describe(const mcx_sim* sim, int32_t* out)
+{
+    if (!sim || !out) return -1;
+    const bool found = mcx_dispatch_signature<8>(sim->desc, [&](auto nslot, auto nz, auto sig) {
+        out[0] = decltype(sig)::value; out[1] = decltype(nslot)::value; out[2] = decltype(nz)::value;
+    });
+    return found ? 0 : -4;
+}
+
 extern "C" int mcx_generate_paths(mcx_handle* h, const mcx_sim* sim, uint64_t seed, uint64_t path_offset, int64_t n_paths,
                                   int64_t ld, double* d_paths, const double* d_inject_z, const double* d_inject_u, void* stream)
 {

@@ -20,6 +20,8 @@ STORAGE_MAX_KNOTS = 8
 SCHEME_EULER, SCHEME_MILSTEIN, SCHEME_ANALYTICAL, SCHEME_QE = 0, 1, 2, 3
 MODEL_BS, MODEL_HESTON, MODEL_VASICEK, MODEL_CIRPP, MODEL_CIRPP_DET, MODEL_HW, MODEL_S2F = 1, 2, 3, 4, 5, 6, 7
 FLAG_SMOOTHING = 1
+# MCX_SIG_*: the model signatures of the path kernels, as mcx_sim_describe reports them
+SIG_NAMES = ("GENERIC", "VAS_CIR_E", "BS_A", "BS_E", "HESTON_QE", "HESTON_E", "VAS_E", "VAS_A", "BS_VAS_CIRDET_E")
 LSM_MFMA, LSM_F32_CACHE = 1, 2
 EV_CASHFLOW, EV_OPTION, EV_EXERCISE, EV_EXPO_POLY, EV_EXPO_BS = 1, 2, 3, 4, 5
 

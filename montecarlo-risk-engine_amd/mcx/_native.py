@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("MCX_LIB_PATH") or os.path.join(os.path.dirname(_HERE)
 
 _EXPORTS = [
     "mcx_abi_version", "mcx_create", "mcx_destroy", "mcx_last_error", "mcx_device_info",
-    "mcx_sim_create", "mcx_sim_destroy", "mcx_generate_paths", "mcx_generate_paths_from_state", "mcx_rng_draws",
+    "mcx_sim_create", "mcx_sim_destroy", "mcx_generate_paths", "mcx_generate_paths_from_state", "mcx_sim_describe", "mcx_rng_draws",
     "mcx_comm_unique_id", "mcx_comm_init", "mcx_comm_destroy", "mcx_allreduce_f64", "mcx_allgather_f64",
     "mcx_book_create", "mcx_book_destroy", "mcx_book_set_coeffs", "mcx_eval_book", "mcx_eval_book_describe", "mcx_resolve_atoms",
     "mcx_lsm_stats", "mcx_lsm_step", "mcx_lsm_run", "mcx_lsm_solve", "mcx_lsm_step_batch", "mcx_lsm_step_batch_dev", "mcx_lsm_solve_batch", "mcx_lsm_run_batch", "mcx_book_get_coeffs", "mcx_book_set_coeffs_batch", "mcx_book_set_bridge_rng", "mcx_book_set_exercise_replay",
@@ -70,6 +70,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_tangent_lsm_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, i64, i64, i32, vp, vp]
     lib.mcx_tangent_paths_s2f.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_tangent_paths_chol.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
+    lib.mcx_sim_describe.argtypes = [C.c_void_p, C.c_void_p]
     lib.mcx_fused_num_records.argtypes = [C.c_void_p]
     lib.mcx_fused_is_straight_line.argtypes = [C.c_void_p]
     lib.mcx_fused_describe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
@@ -165,6 +166,13 @@ class HipBackend:
         out = C.c_void_p()
         self._check(self.lib.mcx_sim_create(self.h, C.byref(plan.desc), C.byref(out)), "mcx_sim_create")
         return _Owned(out, self.lib.mcx_sim_destroy, plan)
+
+    def sim_describe(self, sim) -> dict:
+        """the path-kernel instantiation mcx_generate_paths launches for `sim` (mcx_sim_describe): `signature` is the name of the
+        specialised model signature ("GENERIC": run-time dispatch), with its slots and normals per sub-step"""
+        out = np.zeros(3, dtype=np.int32)
+        self._check(self.lib.mcx_sim_describe(sim.ptr, _abi.ptr(out)), "mcx_sim_describe")
+        return dict(signature=_abi.SIG_NAMES[int(out[0])], n_slots=int(out[1]), n_z=int(out[2]))
 
     def empty_padded(self, *shape) -> torch.Tensor:
         """[..][rows][n_paths] view of a buffer whose rows have the padded leading dimension (padded_ld): the paths tensor, the

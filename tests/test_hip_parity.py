@@ -104,38 +104,36 @@ def test_philox_paths_through_the_qe_scheme(hip, oracle):
 def test_heston_qe_random_parameters_gpu_vs_oracle(smoothing, hip, oracle):
     """the QE step with its reciprocals taken in groups from one v_rcp_f64 of a product (mcx_device.h) against the oracle's IEEE
     divisions, over 24 random parameter sets that reach both branches, tiny and large variances, strong vol-of-vol and long steps:
-    the products of denominators must neither overflow nor lose the reference's eps floors.  Hard branch: a 1-ulp difference of
-    psi or u may flip a branch for a vanishing share of the paths; fuzzy branch: the smoothed scheme's variance goes negative
-     and a path may come arbitrarily close to the pole of 1/(psi + eps) — the same allowance."""
+    the products of denominators must neither overflow nor lose the reference's eps floors.
+
+    What may differ beyond rounding is accounted for per path-step (tests/test_step_kernels.py pins every step against a long-double
+    reference), so the allowance here is what the ORACLE's own paths expose, never what the GPU returns
+    (step_cases.qe_exposed_share).  Hard regime: twice the share of entries downstream of a path-step whose branch margin
+    (u - p or psi - 1.5) the oracle finds within 1e-9.  Smoothed regime: the share downstream of a psi + eps within 1e-6 relative
+    of its zero, the pole of 1 / (psi + eps) (the smoothed scheme's variance goes negative).  Both computed
+    shares are 0.0 for every one of the 24 sets (8192 paths, 4 dates): no entry may differ, in either regime."""
+    import step_cases
     from mcx.common.enums import SimulationScheme
     from mcx.engine.engine import MonteCarloEngine
-    from mcx.models.heston import HestonModel
-    rng = np.random.default_rng(20261005)
-    n, worst = 8192, 0.0
-    for case in range(24):
-        v0 = float(10.0 ** rng.uniform(-6.0, -0.5))
-        theta = float(10.0 ** rng.uniform(-6.0, -0.5))
-        kappa = float(10.0 ** rng.uniform(-2.0, 1.2))
-        sigma = float(10.0 ** rng.uniform(-2.0, 0.5))
-        rho = float(rng.uniform(-0.95, 0.95))
-        rate = float(rng.uniform(-0.02, 0.08))
-        horizon = float(10.0 ** rng.uniform(-1.0, 1.0))
-        model = HestonModel(0.0, 100.0, rate, sigma, rho, kappa, theta, v0)
-        model.perform_smoothing = smoothing
-        tl = np.linspace(horizon / 4, horizon, 4)
+    n, worst, worst_allowed = 8192, 0.0, 0.0
+    for case, q in enumerate(step_cases.qe_sweep_sets()):
+        model = step_cases.heston_qe(case, smoothing)
+        tl = np.linspace(q["horizon"] / 4, q["horizon"], 4)
         out = {}
-        steps = int(rng.integers(1, 6))
         for be in (hip, oracle):
-            eng = MonteCarloEngine(tl, SimulationScheme.QE, model, n, steps, backend=be, path_offset=1000003 * case)
+            eng = MonteCarloEngine(tl, SimulationScheme.QE, model, n, q["steps"], backend=be, path_offset=1000003 * case)
             out[be.name] = eng.generate_paths_native().cpu().numpy()
         # without smoothing every state is finite; with it the reference takes the root of a negative 2 / psi for many of these
         # parameter sets and the path is NaN from there on (13 of the 24 sets on the oracle): the same entries must be NaN here
         if not smoothing:
-            assert np.all(np.isfinite(out["hip"])) and np.all(np.isfinite(out["oracle"])), (case, v0, theta, kappa, sigma)
+            assert np.all(np.isfinite(out["hip"])) and np.all(np.isfinite(out["oracle"])), (case, q)
+        share = step_cases.qe_exposed_share(eng.plan, out["oracle"], step_cases.host_draws(eng.plan, eng.seed, eng.path_offset, n), smoothing)
+        allowed = min(share if smoothing else 2.0 * share, 2e-3)
         bad = ~np.isclose(out["hip"], out["oracle"], rtol=1e-9, atol=1e-12, equal_nan=True)
-        worst = max(worst, float(bad.mean()))
-        assert bad.mean() <= 2e-3, (case, smoothing, bad.mean(), dict(v0=v0, theta=theta, kappa=kappa, sigma=sigma, rho=rho, horizon=horizon, steps=steps))
-    assert worst <= 2e-3
+        print("QE-SWEEP", "smoothed" if smoothing else "hard", case, "differing", float(bad.mean()), "allowed", allowed)
+        worst, worst_allowed = max(worst, float(bad.mean())), max(worst_allowed, allowed)
+        assert bad.mean() <= allowed, (case, smoothing, bad.mean(), allowed, q)
+    assert worst <= worst_allowed <= 2e-3, (smoothing, worst, worst_allowed)
 
 
 def test_random_model_parameters_gpu_vs_oracle(hip, oracle):
