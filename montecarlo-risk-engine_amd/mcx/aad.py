@@ -29,18 +29,23 @@ near the exercise boundary flip their decision and add jump / (2 h N) spikes, so
 reference's autograd gradients (tests/golden/bermudan_swaption_aad.npz, american_put_aad.npz)."""
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import os
 import math
 import time
+from collections import namedtuple
+from operator import itemgetter
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import _abi
+from .maths.regression import regression_centering
 from .metrics.metric import MetricType, mean_and_error
 from .models.black_scholes import BlackScholesModel
 from .models.heston import HestonModel
-from .plan import SimPlan
+from .plan import SimPlan, UnsecuredSpec
 
 
 class TangentOption(C.Structure):
@@ -307,15 +312,6 @@ def _solve_dual_states(mom: np.ndarray, K: int, S: int, shift: float, scale: flo
     return c, dc
 
 
-def _regression_centering(x_range, x):
-    """(shift, scale, degenerate) of the explanatory atom x: z = (x - shift) * scale maps its range over all ranks to [-1, 1]"""
-    xmin, xmax = x_range[x]
-    degenerate = not (xmax > xmin)
-    shift = 0.5 * (xmin + xmax) if not degenerate else xmin
-    scale = 2.0 / (xmax - xmin) if not degenerate else 1.0
-    return shift, scale, degenerate
-
-
 def stateless_lsm_jobs(plan, x_range, expo_coeff_base, K: int):
     """the (product, regression date) pairs of the products WITHOUT exercise states of one forward-mode pass, in the order the
     per-job loop of run_with_tangent_book visits them.  plan: [(product index, product, regression schedule, [(num atom, x atom)])];
@@ -330,7 +326,7 @@ def stateless_lsm_jobs(plan, x_range, expo_coeff_base, K: int):
         for (t_reg, _r0, _r1, _prod_idx, expo_idx), (num, x) in zip(sched, atoms):
             if expo_idx is None:
                 continue
-            shift, scale, degenerate = _regression_centering(x_range, x)
+            shift, scale, degenerate = regression_centering(x_range, x)
             first = int(np.searchsorted(pdates, t_reg, side="right"))      # cashflows strictly after t_reg (controller.py:323)
             rows.append((p_i, first, num, x, shift, scale))
             keep.append((expo_coeff_base[p_i] + expo_idx * K, degenerate))
@@ -351,14 +347,25 @@ def _batch_tangent_lsm(sc) -> bool:
     return True
 
 
-def run_with_tangent_book(sc):
-    """d PV / d theta and d CVA / d theta in forward mode through pre-simulation, regression and main simulation."""
-    import copy
-    from .parallel import Shard
-    from .request_interface.request_types import AtomicRequest, AtomicRequestType
+def no_tangent_form(e) -> bool:
+    """is `e` the library's MCX_E_NOT_FUSABLE: a book the forward-mode kernels have no tangent form for?"""
+    return getattr(e, "code", None) == _abi.E_NOT_FUSABLE
+
+
+# The stages of run_with_tangent_book (DESIGN.md "Forward-mode book pass: the stages of the driver").  _BookPass: what every stage
+# of one differentiation reads; _Chunk: one group of <= TANGENT_NP parameters, their indices `sel` and their zero-padded descriptor
+# tangents; _Presim: the dual pre-simulation of a chunk and the coefficient images its regression fills; _Images: the main pass.
+_BookPass = namedtuple("_BookPass", "sc base be shard s2f chol batched rows base_coeffs")
+_Chunk = namedtuple("_Chunk", "sel dslot dinit daux dchol datoms")
+_Presim = namedtuple("_Presim", "x_range paths dpaths n coeffs dcoeffs")
+_Images = namedtuple("_Images", "paths dpaths cfs expo")
+
+
+def _tangent_book_routes(sc):
+    """Host only: every gate that holds before any GPU work, in the order their reasons are reported.  -> (s2f, chol, batched):
+    which dual path kernel serves the book, and whether the stateless products' regression is batched."""
     if sc.requires_higher_order_derivatives:
         raise _NoTangentForm("second order")
-    rm = sc.risk_metrics
     # Schwartz two-factor dual paths serve books that hold a storage; every other book keeps the route it had (no tangent form)
     s2f = hasattr(sc.model, "_cholesky_entries") and hasattr(sc.backend, "tangent_paths_s2f") \
         and any(getattr(p, "is_storage", False) for p in sc.products)
@@ -367,14 +374,300 @@ def run_with_tangent_book(sc):
     chol = not s2f and hasattr(sc.backend, "tangent_paths_chol") and _analytic_factor_form(sc.model, sc.simulation_scheme)
     if sc.simulation_scheme.name != "EULER" and not (s2f and sc.simulation_scheme.name == "ANALYTICAL") and not chol:
         raise _NoTangentForm("scheme")
-    if any(m.metric_type not in (MetricType.PV, MetricType.CVA, MetricType.EPE, MetricType.ENE, MetricType.CE, MetricType.EEPE,
-                                 MetricType.PFE) or not m._native for m in rm.metrics):
+    if any(m.metric_type not in _SCATTER or not m._native for m in sc.risk_metrics.metrics):
         raise _NoTangentForm("metric")
     batched = _batch_tangent_lsm(sc)
     if any(p.get_num_states() > 1 for p in sc.products) and not hasattr(sc.backend, "tangent_lsm_step"):
         raise _NoTangentForm("exercise products")
     if any(sc._can_skip_monte_carlo_for_product(p) for p in sc.products):
         raise _NoTangentForm("analytic shortcuts")
+    return s2f, chol, batched
+
+
+def _descriptors_like(base, model, smoothing, shape0, dtype=np.float64, complex_step=None, bump=None):
+    """the host descriptors of `base` under a copy of `model` at theta_j + i h (complex_step: (j, h)) or with theta_j replaced
+    (bump: (j, value)); the copy must keep the descriptor structure `shape0`"""
+    m = copy.deepcopy(model)
+    m.perform_smoothing = smoothing
+    if complex_step is not None:
+        _set_complex_step(m, *complex_step)
+    else:
+        _set_param(m, *bump)
+    ev, shape = _host_descriptors(base, m, dtype=dtype)
+    if shape != shape0:
+        raise _NoTangentForm("descriptor structure depends on the parameters")
+    return ev
+
+
+def descriptor_tangents(base, model, smoothing, mode=None):
+    """Host only: (d0, dd), every descriptor block of the compiled controller `base` (_host_descriptors) and its derivative
+    [...][P] with respect to the P parameters of `model`.  mode (default: the environment's MCX_DESCRIPTOR_FD, else "complex"):
+    "complex": the closed forms are analytic in the parameters, so d f / d theta = Im f(theta + i h) / h with h far below rounding —
+    ONE evaluation per parameter, no subtractive cancellation (exact to the last bits); a model whose closed forms are written
+    with real-only functions (TypeError) falls back to "4": 4-point central differences with a wide step (truncation O(h^4) ~
+    1e-12, rounding eps/h ~ 1e-13 relative).  Anything else: the 2-point formula (h = 1e-6 left 1e-5 relative noise on
+    d CVA / d sigma_cir: CIR++ sensitivities are small residuals of large cancelling terms)."""
+    d0, shape0 = _host_descriptors(base, model)
+    theta = [float(p.detach()) for p in model.get_model_params()]
+    dd = {k: np.zeros(v.shape + (len(theta),)) for k, v in d0.items()}
+    mode = os.environ.get("MCX_DESCRIPTOR_FD", "complex") if mode is None else mode
+    if mode == "complex":
+        try:
+            for j, th in enumerate(theta):
+                h = 1e-30 * max(abs(th), 1e-2)
+                ev = _descriptors_like(base, model, smoothing, shape0, np.complex128, complex_step=(j, h))
+                for k in dd:
+                    dd[k][..., j] = ev[k].imag / h
+            return d0, dd
+        except TypeError:
+            mode = "4"
+    four_point = mode == "4"
+    for j, th in enumerate(theta):
+        h = (1e-3 if four_point else 1e-4) * max(abs(th), 1e-2)
+        ev = {mult: _descriptors_like(base, model, smoothing, shape0, bump=(j, th + mult * h))
+              for mult in ((1, -1, 2, -2) if four_point else (1, -1))}
+        for k in dd:
+            if four_point:
+                dd[k][..., j] = (8.0 * (ev[1][k] - ev[-1][k]) - (ev[2][k] - ev[-2][k])) / (12.0 * h)
+            else:
+                dd[k][..., j] = (ev[1][k] - ev[-1][k]) / (2.0 * h)
+    return d0, dd
+
+
+def pad_chunk(a, sel):
+    """the columns `sel` of the trailing parameter axis of `a`, zero-padded to TANGENT_NP columns (what one dual pass carries)"""
+    return np.ascontiguousarray(np.concatenate([a[..., sel], np.zeros(a.shape[:-1] + (_abi.TANGENT_NP - len(sel),))], axis=-1))
+
+
+def _parameter_chunk(ctx, dd, sel):
+    """the padded descriptor tangents of the parameters `sel`; the atoms' go to the device, the factors' only where a route reads them"""
+    dchol = pad_chunk(dd["chol"], sel) if ctx.s2f or ctx.chol else None
+    return _Chunk(sel, pad_chunk(dd["slots"], sel), pad_chunk(dd["init"], sel), pad_chunk(dd["aux"], sel), dchol,
+                  ctx.be.from_numpy(pad_chunk(dd["atoms"], sel)))
+
+
+def _dual_paths(ctx, chunk, seed, off, n, inject_z):
+    """GPU: (paths, dpaths) of n paths from path `off` on, through the dual path kernel of the book's route"""
+    be, sim, c = ctx.be, ctx.base._sim, chunk
+    if ctx.s2f:
+        return be.tangent_paths_s2f(sim, c.dslot, c.dinit, c.daux, c.dchol, seed, off, n, inject_z)
+    if ctx.chol:
+        return be.tangent_paths_chol(sim, c.dslot, c.dinit, c.daux, c.dchol, seed, off, n, inject_z)
+    return be.tangent_paths(sim, c.dslot, c.dinit, c.daux, seed, off, n, inject_z)
+
+
+def _regress_dates(ctx, job, pre, moments, rolls: bool):
+    """Host: the per-date loop the three per-product routes share.  moments(entry, num, x, shift, scale) -> the dual moments of one
+    schedule entry summed over all ranks.  rolls: the product carries a cashflow cache backwards, so every date is asked and the
+    coefficients stay those of the base run's policy; otherwise only the dates with an exposure row are asked and their
+    coefficients are written too.  The [S][K] coefficient tangents of the exposure rows go into the images of `pre`."""
+    p_i, p, sched, atoms = job
+    S, K, NP = p.get_num_states(), ctx.base.book_plan.n_basis, _abi.TANGENT_NP
+    for entry, (num, x) in zip(sched, atoms):
+        expo_idx = entry[4]
+        if expo_idx is None and not rolls:
+            continue
+        shift, scale, degenerate = regression_centering(pre.x_range, x)
+        mom = moments(entry, num, x, shift, scale)
+        if expo_idx is None:
+            continue
+        o = ctx.base._expo_coeff_base[p_i] + expo_idx * S * K
+        if rolls:
+            dc = _solve_dual_states(mom, K, S, shift, scale, degenerate, NP)[1].reshape(NP, S * K)
+        else:
+            pre.coeffs[o:o + K], dc = _solve_dual(mom, K, shift, scale, degenerate, NP)
+        pre.dcoeffs[o:o + S * K] = dc.T
+
+
+def _regress_storage(ctx, chunk, job, pre):
+    """GPU + collectives: the storage's backward induction in dual numbers (mcx_tangent_storage_lsm_step): every step rolls at most
+    one action date from the integer grid states along the base run's policy; old and new cache alternate"""
+    p_i, p = job[:2]
+    be, S, NP = ctx.be, p.get_num_states(), _abi.TANGENT_NP
+    st = ctx.base._storage_handle(p_i)
+    W, dW = be.zeros(2, S, pre.n), be.zeros(2, NP, S, pre.n)
+    decide = be.from_numpy(pre.coeffs)
+    flags = _abi.LSM_F32_CACHE if ctx.base.reference_float32_cf_cache else 0
+    halves = [0, 1]                           # (old, new) half of the double-buffered cache
+
+    def moments(entry, num, x, shift, scale):
+        _t_reg, r0, r1 = entry[:3]
+        if r1 - r0 > 1:
+            raise RuntimeError("internal: a storage step rolls at most one action date")
+        roll, (old, new) = (r0 if r1 > r0 else -1), halves
+        mom = be.tangent_storage_lsm_step(ctx.base.book, st, roll, num, x, shift, scale, chunk.datoms, decide, pre.paths, pre.dpaths,
+                                          W[old], dW[old], W[new], dW[new], flags=flags)
+        if roll >= 0:
+            halves.reverse()
+        return ctx.shard.all_reduce_np(mom)
+    _regress_dates(ctx, job, pre, moments, rolls=True)
+
+
+def _regress_exercise(ctx, chunk, job, pre):
+    """GPU + collectives: backward induction with the cashflow cache of every hypothetical state rolled in place, in dual numbers,
+    along the frozen policy (mcx_tangent_lsm_step); the coefficient tangents of the exposure rows feed the main pass"""
+    p_i, p = job[:2]
+    be, S = ctx.be, p.get_num_states()
+    W, dW = be.zeros(S, pre.n), be.zeros(_abi.TANGENT_NP, S, pre.n)
+
+    def moments(entry, num, x, shift, scale):
+        return ctx.shard.all_reduce_np(be.tangent_lsm_step(ctx.base.book, p_i, entry[1], entry[2], num, x, shift, scale, chunk.datoms,
+                                                           pre.paths, pre.dpaths, W, dW))
+    _regress_dates(ctx, job, pre, moments, rolls=True)
+
+
+def _regress_stateless(ctx, chunk, job, pre):
+    """GPU + collectives: one mcx_tangent_lsm call per regression date of a product without exercise states"""
+    p_i, p = job[:2]
+    pdates = np.asarray([float(t) for t in p.product_timeline])
+
+    def moments(entry, num, x, shift, scale):
+        first = int(np.searchsorted(pdates, entry[0], side="right"))      # cashflows strictly after t_reg (controller.py:323)
+        return ctx.shard.all_reduce_np(ctx.be.tangent_lsm(ctx.base.book, p_i, first, num, x, shift, scale, chunk.datoms, pre.paths,
+                                                          pre.dpaths))
+    _regress_dates(ctx, job, pre, moments, rolls=False)
+
+
+def _regress_batched(ctx, chunk, plan, pre) -> int:
+    """GPU + collectives: the stateless products' (product, date) pairs in one library call and one collective for the whole moment
+    block; their coefficient slots are disjoint from those of the products with states.  -> the number of pairs"""
+    K, NP = ctx.base.book_plan.n_basis, _abi.TANGENT_NP
+    table, keep = stateless_lsm_jobs(plan, pre.x_range, ctx.base._expo_coeff_base, K)         # (centred there, once per pair)
+    if len(table):
+        moments = ctx.shard.all_reduce_np(ctx.be.tangent_lsm_batch(ctx.base.book, table, chunk.datoms, pre.paths, pre.dpaths))
+        for job, mom, (o, degenerate) in zip(table, moments, keep):
+            pre.coeffs[o:o + K], dc = _solve_dual(mom, K, float(job["shift"]), float(job["scale"]), degenerate, NP)
+            pre.dcoeffs[o:o + K] = dc.T
+    return len(table)
+
+
+def _regress_chunk(ctx, chunk, plan):
+    """GPU + collectives: dual pre-simulation and regression of one chunk.  -> (coeffs, dcoeffs [n_coeffs][NP], pairs batched):
+    the book's coefficient image and its tangents, products in ascending index"""
+    sc, base = ctx.sc, ctx.base
+    n_coeffs = len(base.book_plan.coeffs)
+    coeffs, dcoeffs = np.zeros(max(n_coeffs, 1)), np.zeros((max(n_coeffs, 1), _abi.TANGENT_NP))
+    if ctx.base_coeffs is not None:
+        # exercise decisions are taken from the PRIMAL coefficients of the base run (the reference's tape has no gradient through
+        # `should_exercise`, bermudan_option.py:122-128): every row starts from them, the exposure rows get their tangents below
+        coeffs[:n_coeffs] = ctx.base_coeffs
+    if not plan:
+        return coeffs, dcoeffs, 0
+    off, n_pre = ctx.shard.split(sc.num_paths_presim)
+    paths, dpaths = _dual_paths(ctx, chunk, 42 + sc.seed_offset, off, n_pre, sc._inject.get("pre", (None, None))[0])
+    pre = _Presim(base._explanatory_ranges(ctx.shard, plan, paths), paths, dpaths, n_pre, coeffs, dcoeffs)
+    for job in plan:
+        if job[0] in base._storage_meta:
+            _regress_storage(ctx, chunk, job, pre)
+        elif job[1].get_num_states() > 1:
+            _regress_exercise(ctx, chunk, job, pre)
+        elif not ctx.batched:
+            _regress_stateless(ctx, chunk, job, pre)
+    n_pairs = _regress_batched(ctx, chunk, plan, pre) if ctx.batched else 0
+    return coeffs, dcoeffs, n_pairs
+
+
+def _bs_exposure_slots(base, sc, sel):
+    """Host only: [n_events][2] — for the analytic Black-Scholes exposure events (EV_EXPO_BS) the tangent slot of this pass that
+    is their sigma / their rate, -1 where the chunk `sel` does not hold it and in every other row; None without such events"""
+    ev_kind = base.book_plan.events["kind"]
+    if not (ev_kind == _abi.EV_EXPO_BS).any():
+        return None
+    ev_param = np.full((len(ev_kind), 2), -1, dtype=np.int32)
+    for p_i, p in enumerate(sc.products):
+        if not (hasattr(p, "_bs_param_indices") and base._can_use_analytic_exposure_for_product(p)):
+            continue
+        _i_s, i_v, i_r = p._bs_param_indices(sc.model)
+        b0, b1 = int(base.book_plan.products["ev_begin"][p_i]), int(base.book_plan.products["ev_end"][p_i])
+        rows_bs = np.arange(b0, b1)[ev_kind[b0:b1] == _abi.EV_EXPO_BS]
+        ev_param[rows_bs, 0] = sel.index(i_v) if i_v in sel else -1
+        ev_param[rows_bs, 1] = sel.index(i_r) if i_r in sel else -1
+    return ev_param
+
+
+def _main_dual_pass(ctx, chunk, coeffs, dcoeffs):
+    """GPU: dual main simulation and dual book of one chunk -> _Images (cashflow and exposure images [1 + NP][...])"""
+    sc, base, be = ctx.sc, ctx.base, ctx.be
+    off, n_main = ctx.shard.split(sc.num_paths_mainsim)
+    paths, dpaths = _dual_paths(ctx, chunk, 43 + sc.seed_offset, off, n_main, sc._inject.get("main", (None, None))[0])
+    ev_param = _bs_exposure_slots(base, sc, chunk.sel)
+    d_coeffs, d_dcoeffs = be.from_numpy(coeffs), be.from_numpy(dcoeffs)
+    cfs, expo = be.tangent_eval(base.book, chunk.datoms, d_coeffs, d_dcoeffs, paths, dpaths, ev_param)
+    for p_i in base._storage_meta:            # a storage owns no events: its dual walk adds to the images just written
+        be.tangent_storage_eval(base.book, base._storage_handle(p_i), base._storage_ops(p_i), chunk.datoms, d_coeffs, d_dcoeffs, paths,
+                                dpaths, cfs, expo)
+    return _Images(paths, dpaths, cfs, expo)
+
+
+# ---- metric tangents: one function per metric family, writing out[eval][param] for the parameters of the chunk ------------------------
+def _mean_over_paths(ctx, vec):
+    return mean_and_error(ctx.shard.all_gather_np(ctx.be.reduce_vector(vec).view(np.float64)))[0]
+
+
+def _scatter_pv(ctx, chunk, ns, m_i, m, img, out):
+    for q, j in enumerate(chunk.sel):
+        out[0][j] = _mean_over_paths(ctx, img.cfs[1 + q, ns.i])
+
+
+def _scatter_profile(ctx, chunk, ns, m_i, m, img, out):
+    """EPE / ENE per exposure date, CE (positive part of the first exposure date, ce_metric.py), EEPE (plain time average of the EE
+    profile, eepe_metric.py) from ONE profile tangent per netting set and chunk: [dates][2][NP] means of 1[u>0] du / 1[u<0] du"""
+    if ns.prof is None:
+        ns.prof = ctx.shard.all_reduce_np(ctx.be.tangent_profiles(ctx.rows, ns.set.threshold, img.expo, ns.i, ns.delayed, ns.coll)) \
+            / float(ctx.sc.num_paths_mainsim)
+    for q, j in enumerate(chunk.sel):
+        if m.metric_type == MetricType.CE:
+            out[0][j] = float(ns.prof[0, 0, q])
+        elif m.metric_type == MetricType.EEPE:
+            out[0][j] = float(ns.prof[:, 0, q].mean())
+        else:
+            side = 0 if m.metric_type == MetricType.EPE else 1
+            for e_i in range(len(out)):
+                out[e_i][j] = float(ns.prof[e_i, side, q])
+
+
+def _scatter_pfe(ctx, chunk, ns, m_i, m, img, out):
+    """the tangent of the path that realises the exact order statistic (the reference differentiates through torch.sort): radix
+    select on the primal image, then the first path carrying that value"""
+    sc, be, shard = ctx.sc, ctx.be, ctx.shard
+    unsec = UnsecuredSpec(ctx.rows, ns.delayed, ns.set.threshold, ns.coll)
+    target = ctx.base._select_order_stats(shard, unsec, img.expo[0, ns.i], [m.q_index(sc.num_paths_mainsim)])[:, 0]
+    pick = be.tangent_pick(ctx.rows, ns.set.threshold, target, img.expo, ns.i, ns.delayed, ns.coll)
+    pick[:, 0] = np.where(pick[:, 0] >= 0, pick[:, 0] + shard.split(sc.num_paths_mainsim)[0], np.inf)          # global path index
+    allp = shard.all_gather_np(pick)                                          # [world][dates][1+NP]
+    win = np.argmin(allp[:, :, 0], axis=0)
+    for e_i in range(len(out)):
+        for q, j in enumerate(chunk.sel):
+            out[e_i][j] = float(allp[win[e_i], e_i, 1 + q])
+
+
+def _scatter_cva(ctx, chunk, ns, m_i, m, img, out):
+    if ns.set.counterparty_id is not None and m.counterparty_id != ns.set.counterparty_id:
+        return
+    surv, cond = ctx.base._cva_atoms[m_i]
+    cva = ctx.be.tangent_cva(ctx.base.book, chunk.datoms, ctx.rows, surv, cond, ns.set.threshold, m.recovery_rate, img.expo, ns.i,
+                             img.paths, img.dpaths, ns.delayed, ns.coll)
+    for q, j in enumerate(chunk.sel):
+        out[0][j] = _mean_over_paths(ctx, cva[1 + q])
+
+
+_SCATTER = {MetricType.PV: _scatter_pv, MetricType.CVA: _scatter_cva, MetricType.PFE: _scatter_pfe, MetricType.EPE: _scatter_profile,
+            MetricType.ENE: _scatter_profile, MetricType.CE: _scatter_profile, MetricType.EEPE: _scatter_profile}
+
+
+def _scatter_metric_tangents(ctx, chunk, img, grads):
+    """GPU + collectives: the chunk's columns of grads[ns][metric][eval][param], every metric by the function of its family"""
+    for ns_i, ns in enumerate(ctx.sc.netting_sets):
+        coll = ns.is_collateralized()
+        delayed = ctx.base.netting_set_delayed_exposure_indices[ns_i].numpy().astype(np.int32) if coll else None
+        view = SimpleNamespace(i=ns_i, set=ns, coll=coll, delayed=delayed, prof=None)
+        for m_i, m in enumerate(ctx.sc.risk_metrics.metrics):
+            _SCATTER[m.metric_type](ctx, chunk, view, m_i, m, img, grads[ns_i][m_i])
+
+
+def run_with_tangent_book(sc):
+    """d PV / d theta and d CVA / d theta in forward mode through pre-simulation, regression and main simulation."""
+    s2f, chol, batched = _tangent_book_routes(sc)
     t0 = time.perf_counter()
     be, shard = sc.backend, sc.shard_factory()
     NP = _abi.TANGENT_NP
@@ -382,240 +675,37 @@ def run_with_tangent_book(sc):
     res0 = base.run_simulation()
     if base.book_plan.n_basis > 4:
         raise _NoTangentForm("basis")
-    theta = [float(p.detach()) for p in sc.model.get_model_params()]
-    P = len(theta)
-    smoothing = getattr(sc.model, "perform_smoothing", False)
-
-    # derivative of every descriptor number (closed forms evaluated in float64 on the host): 4-point central differences with
-    # a wide step — truncation O(h^4) ~ 1e-12, rounding eps/h ~ 1e-13 relative.  (CIR++ sensitivities are small residuals of
-    # large cancelling terms: a 2-point formula with h = 1e-6 left 1e-5 relative noise on d CVA / d sigma_cir.)
-    d0, shape0 = _host_descriptors(base)                 # `base` is compiled: its sub-step schedule and atoms are re-evaluated
-
-    def bumped_model(j, value):
-        m = copy.deepcopy(sc.model)
-        m.perform_smoothing = smoothing
-        _set_param(m, j, value)
-        return m
-
-    dd = {k: np.zeros(v.shape + (P,)) for k, v in d0.items()}
-    # Complex step: the closed forms are analytic in the parameters, so d f / d theta = Im f(theta + i h) / h with h far below
-    # rounding — ONE evaluation per parameter, no subtractive cancellation (exact to the last bits).  Models whose closed forms
-    # are not complex-safe fall back to 4-point central differences with a wide step (truncation O(h^4) ~ 1e-12, rounding
-    # eps/h ~ 1e-13 relative; a 2-point formula with h = 1e-6 left 1e-5 relative noise on d CVA / d sigma_cir).
-    mode = os.environ.get("MCX_DESCRIPTOR_FD", "complex")
-    if mode == "complex":
-        try:
-            for j in range(P):
-                m = copy.deepcopy(sc.model)
-                m.perform_smoothing = smoothing
-                h = 1e-30 * max(abs(theta[j]), 1e-2)
-                _set_complex_step(m, j, h)
-                ev, shp = _host_descriptors(base, m, dtype=np.complex128)
-                if shp != shape0:
-                    raise _NoTangentForm("descriptor structure depends on the parameters")
-                for k in dd:
-                    dd[k][..., j] = ev[k].imag / h
-        except TypeError:                     # a closed form written with real-only functions
-            mode = "4"
-    if mode != "complex":
-        four_point = mode == "4"
-        for j in range(P):
-            h = (1e-3 if four_point else 1e-4) * max(abs(theta[j]), 1e-2)
-            ev = {}
-            for mult in ((1, -1, 2, -2) if four_point else (1, -1)):
-                ev[mult], shp = _host_descriptors(base, bumped_model(j, theta[j] + mult * h))
-                if shp != shape0:
-                    raise _NoTangentForm("descriptor structure depends on the parameters")
-            for k in dd:
-                if four_point:
-                    dd[k][..., j] = (8.0 * (ev[1][k] - ev[-1][k]) - (ev[2][k] - ev[-2][k])) / (12.0 * h)
-                else:
-                    dd[k][..., j] = (ev[1][k] - ev[-1][k]) / (2.0 * h)
+    # `base` is compiled: its sub-step schedule and atoms are re-evaluated under the bumped models
+    _d0, dd = descriptor_tangents(base, sc.model, getattr(sc.model, "perform_smoothing", False))
     t_desc = time.perf_counter() - t0
     t_pre = t_main = 0.0
-    book, sim, K = base.book, base._sim, base.book_plan.n_basis
-    n_coeffs = len(base.book_plan.coeffs)
-    n_ns, n_metrics = len(sc.netting_sets), len(rm.metrics)
-    n_eval = [len(res0.results[0][m_i]) for m_i in range(n_metrics)]
-    grads = [[[[0.0] * P for _ in range(n_eval[m_i])] for m_i in range(n_metrics)] for _ in range(n_ns)]     # [ns][metric][eval][param]
-    jobs = [(p_i, p) for p_i, p in enumerate(sc.products) if p_i in base._mc_set and base._product_requires_regression(p)]
+    P, n_coeffs = len(sc.model.get_model_params()), len(base.book_plan.coeffs)
+    grads = [[[[0.0] * P for _ in evals] for evals in res0.results[0]] for _ in sc.netting_sets]     # [ns][metric][eval][param]
+    jobs, storage_jobs = base._regression_plan()
+    plan = sorted(jobs + storage_jobs, key=itemgetter(0))                    # the coefficient images are filled in product order
     has_exercise = any(p.get_num_states() > 1 for p in sc.products)
     base_coeffs = np.asarray(be.book_get_coeffs(base.book), dtype=np.float64)[:n_coeffs] if (has_exercise and n_coeffs) else None
-    rows = base.metric_exposure_indices.numpy().astype(np.int32) if rm.requires_exposure_profiles() else np.zeros(0, dtype=np.int32)
-
-    def mean_of(vec):
-        return mean_and_error(shard.all_gather_np(be.reduce_vector(vec).view(np.float64)))[0]
-
-    storages = getattr(base, "_storage_meta", {})
-    lsm_flags = _abi.LSM_F32_CACHE if base.reference_float32_cf_cache else 0
+    rows = base.metric_exposure_indices.numpy().astype(np.int32) if sc.risk_metrics.requires_exposure_profiles() else np.zeros(0, dtype=np.int32)
+    ctx = _BookPass(sc, base, be, shard, s2f, chol, batched, rows, base_coeffs)
     n_batched = 0
-
     for c0 in range(0, P, NP):
-        sel = list(range(c0, min(c0 + NP, P)))
-        pad = lambda a: np.ascontiguousarray(np.concatenate([a[..., sel], np.zeros(a.shape[:-1] + (NP - len(sel),))], axis=-1))
-        dslot, dinit, daux = pad(dd["slots"]), pad(dd["init"]), pad(dd["aux"])
-        datoms = be.from_numpy(pad(dd["atoms"]))
-
-        def dual_paths(seed, off_, n_, inject_z):
-            if s2f:
-                return be.tangent_paths_s2f(sim, dslot, dinit, daux, pad(dd["chol"]), seed, off_, n_, inject_z)
-            if chol:
-                return be.tangent_paths_chol(sim, dslot, dinit, daux, pad(dd["chol"]), seed, off_, n_, inject_z)
-            return be.tangent_paths(sim, dslot, dinit, daux, seed, off_, n_, inject_z)
-        coeffs, dcoeffs = np.zeros(max(n_coeffs, 1)), np.zeros((max(n_coeffs, 1), NP))
-        if has_exercise and n_coeffs:
-            # exercise decisions are taken from the PRIMAL coefficients of the base run (the reference's tape has no gradient through
-            # `should_exercise`, bermudan_option.py:122-128): every row starts from them, the exposure rows get their tangents below
-            coeffs[:n_coeffs] = base_coeffs
+        chunk = _parameter_chunk(ctx, dd, list(range(c0, min(c0 + NP, P))))
         t1 = time.perf_counter()
-        if jobs:
-            off, n_pre = shard.split(sc.num_paths_presim)
-            paths_pre, dpaths_pre = dual_paths(42 + sc.seed_offset, off, n_pre, sc._inject.get("pre", (None, None))[0])
-            plan = [(p_i, p, base._regression_schedule(p_i, p)) for p_i, p in jobs]
-            plan = [(p_i, p, sched, base._regression_atoms(sched, p.asset_ids[0])) for p_i, p, sched in plan]
-            x_ids = sorted({x for _, _, _, atoms in plan for _, x in atoms})
-            g = shard.all_gather_np(be.lsm_stats(book, x_ids, paths_pre))
-            lo, hi = g[:, :, 0].min(axis=0), g[:, :, 1].max(axis=0)
-            x_range = {x: (lo[i], hi[i]) for i, x in enumerate(x_ids)}
-            for p_i, p, sched, atoms in plan:
-                S = p.get_num_states()
-                if p_i in storages:
-                    # the storage's backward induction in dual numbers (mcx_tangent_storage_lsm_step): every step rolls at most one
-                    # action date from the integer grid states along the base run's policy; old and new cache alternate
-                    st = base._storage_handle(p_i)
-                    W, dW = be.zeros(2, S, n_pre), be.zeros(2, NP, S, n_pre)
-                    decide = be.from_numpy(coeffs)
-                    cur = 0
-                    for (t_reg, r0, r1, _prod_idx, expo_idx), (num, x) in zip(sched, atoms):
-                        if r1 - r0 > 1:
-                            raise RuntimeError("internal: a storage step rolls at most one action date")
-                        xmin, xmax = x_range[x]
-                        degenerate = not (xmax > xmin)
-                        shift = 0.5 * (xmin + xmax) if not degenerate else xmin
-                        scale = 2.0 / (xmax - xmin) if not degenerate else 1.0
-                        roll = r0 if r1 > r0 else -1
-                        mom = shard.all_reduce_np(be.tangent_storage_lsm_step(book, st, roll, num, x, shift, scale, datoms, decide, paths_pre,
-                                                                              dpaths_pre, W[cur], dW[cur], W[1 - cur], dW[1 - cur], flags=lsm_flags))
-                        if roll >= 0:
-                            cur = 1 - cur
-                        if expo_idx is None:
-                            continue
-                        c, dc = _solve_dual_states(mom, K, S, shift, scale, degenerate, NP)
-                        o = base._expo_coeff_base[p_i] + expo_idx * S * K
-                        dcoeffs[o:o + S * K] = dc.reshape(NP, S * K).T
-                    del W, dW, decide
-                    continue
-                if S > 1:
-                    # backward induction with the cashflow cache of every hypothetical state rolled in dual numbers along the
-                    # frozen policy (mcx_tangent_lsm_step); the coefficient tangents of the exposure rows feed the main pass
-                    W, dW = be.zeros(S, n_pre), be.zeros(NP, S, n_pre)
-                    for (t_reg, r0, r1, _prod_idx, expo_idx), (num, x) in zip(sched, atoms):
-                        xmin, xmax = x_range[x]
-                        degenerate = not (xmax > xmin)
-                        shift = 0.5 * (xmin + xmax) if not degenerate else xmin
-                        scale = 2.0 / (xmax - xmin) if not degenerate else 1.0
-                        mom = shard.all_reduce_np(be.tangent_lsm_step(book, p_i, r0, r1, num, x, shift, scale, datoms, paths_pre,
-                                                                      dpaths_pre, W, dW))
-                        if expo_idx is None:
-                            continue
-                        c, dc = _solve_dual_states(mom, K, S, shift, scale, degenerate, NP)
-                        o = base._expo_coeff_base[p_i] + expo_idx * S * K
-                        dcoeffs[o:o + S * K] = dc.reshape(NP, S * K).T
-                    del W, dW
-                    continue
-                if batched:
-                    continue
-                pdates = np.asarray([float(t) for t in p.product_timeline])
-                for (t_reg, _r0, _r1, _prod_idx, expo_idx), (num, x) in zip(sched, atoms):
-                    if expo_idx is None:
-                        continue
-                    xmin, xmax = x_range[x]
-                    degenerate = not (xmax > xmin)
-                    shift = 0.5 * (xmin + xmax) if not degenerate else xmin
-                    scale = 2.0 / (xmax - xmin) if not degenerate else 1.0
-                    first = int(np.searchsorted(pdates, t_reg, side="right"))      # cashflows strictly after t_reg (controller.py:323)
-                    mom = shard.all_reduce_np(be.tangent_lsm(book, p_i, first, num, x, shift, scale, datoms, paths_pre, dpaths_pre))
-                    c, dc = _solve_dual(mom, K, shift, scale, degenerate, NP)
-                    o = base._expo_coeff_base[p_i] + expo_idx * K
-                    coeffs[o:o + K], dcoeffs[o:o + K] = c, dc.T
-            if batched:
-                # the stateless products' (product, date) pairs: one library call and one collective for the whole moment block;
-                # their coefficient slots are disjoint from those of the products with states, which the loop above has served
-                table, keep = stateless_lsm_jobs(plan, x_range, base._expo_coeff_base, K)
-                if len(table):
-                    moments = shard.all_reduce_np(be.tangent_lsm_batch(book, table, datoms, paths_pre, dpaths_pre))
-                    for job, mom, (o, degenerate) in zip(table, moments, keep):
-                        c, dc = _solve_dual(mom, K, float(job["shift"]), float(job["scale"]), degenerate, NP)
-                        coeffs[o:o + K], dcoeffs[o:o + K] = c, dc.T
-                    n_batched += len(table)
-            del paths_pre, dpaths_pre
+        coeffs, dcoeffs, n_pairs = _regress_chunk(ctx, chunk, plan)
+        n_batched += n_pairs
         be.synchronize()
         t2 = time.perf_counter()
         t_pre += t2 - t1
-        off, n_main = shard.split(sc.num_paths_mainsim)
-        paths, dpaths = dual_paths(43 + sc.seed_offset, off, n_main, sc._inject.get("main", (None, None))[0])
-        # analytic Black-Scholes exposure events: which tangent slot of this pass is their sigma / their rate
-        ev_param = None
-        ev_kind = base.book_plan.events["kind"]
-        if (ev_kind == _abi.EV_EXPO_BS).any():
-            ev_param = np.full((len(ev_kind), 2), -1, dtype=np.int32)
-            for p_i, p in enumerate(sc.products):
-                if hasattr(p, "_bs_param_indices") and base._can_use_analytic_exposure_for_product(p):
-                    _i_s, i_v, i_r = p._bs_param_indices(sc.model)
-                    b0, b1 = int(base.book_plan.products["ev_begin"][p_i]), int(base.book_plan.products["ev_end"][p_i])
-                    rows_bs = np.arange(b0, b1)[ev_kind[b0:b1] == _abi.EV_EXPO_BS]
-                    ev_param[rows_bs, 0] = sel.index(i_v) if i_v in sel else -1
-                    ev_param[rows_bs, 1] = sel.index(i_r) if i_r in sel else -1
-        d_coeffs, d_dcoeffs = be.from_numpy(coeffs), be.from_numpy(dcoeffs)
-        cfs, expo = be.tangent_eval(book, datoms, d_coeffs, d_dcoeffs, paths, dpaths, ev_param)
-        for p_i in storages:                  # a storage owns no events: its dual walk adds to the images just written
-            be.tangent_storage_eval(book, base._storage_handle(p_i), base._storage_ops(p_i), datoms, d_coeffs, d_dcoeffs, paths, dpaths, cfs, expo)
-        for ns_i, ns in enumerate(sc.netting_sets):
-            prof = None
-            coll = ns.is_collateralized()
-            delayed = base.netting_set_delayed_exposure_indices[ns_i].numpy().astype(np.int32) if coll else None
-            for m_i, m in enumerate(rm.metrics):
-                if m.metric_type == MetricType.PV:
-                    for q, j in enumerate(sel):
-                        grads[ns_i][m_i][0][j] = mean_of(cfs[1 + q, ns_i])
-                elif m.metric_type in (MetricType.EPE, MetricType.ENE, MetricType.CE, MetricType.EEPE):
-                    if prof is None:            # [dates][2][NP] sums of 1[u>0] du / 1[u<0] du over all ranks
-                        prof = shard.all_reduce_np(be.tangent_profiles(rows, ns.threshold, expo, ns_i, delayed, coll)) / float(sc.num_paths_mainsim)
-                    for q, j in enumerate(sel):
-                        if m.metric_type == MetricType.CE:           # positive part of the first exposure date (ce_metric.py)
-                            grads[ns_i][m_i][0][j] = float(prof[0, 0, q])
-                        elif m.metric_type == MetricType.EEPE:       # plain time average of the EE profile (eepe_metric.py)
-                            grads[ns_i][m_i][0][j] = float(prof[:, 0, q].mean())
-                        else:
-                            side = 0 if m.metric_type == MetricType.EPE else 1
-                            for e_i in range(n_eval[m_i]):
-                                grads[ns_i][m_i][e_i][j] = float(prof[e_i, side, q])
-                elif m.metric_type == MetricType.PFE:
-                    # the tangent of the path that realises the exact order statistic (the reference differentiates through
-                    # torch.sort): radix select on the primal image, then the first path carrying that value
-                    from .plan import UnsecuredSpec
-                    unsec = UnsecuredSpec(rows, delayed, ns.threshold, coll)
-                    target = base._select_order_stats(shard, unsec, expo[0, ns_i], [m.q_index(sc.num_paths_mainsim)])[:, 0]
-                    pick = be.tangent_pick(rows, ns.threshold, target, expo, ns_i, delayed, coll)
-                    pick[:, 0] = np.where(pick[:, 0] >= 0, pick[:, 0] + off, np.inf)          # global path index
-                    allp = shard.all_gather_np(pick)                                          # [world][dates][1+NP]
-                    win = np.argmin(allp[:, :, 0], axis=0)
-                    for e_i in range(n_eval[m_i]):
-                        for q, j in enumerate(sel):
-                            grads[ns_i][m_i][e_i][j] = float(allp[win[e_i], e_i, 1 + q])
-                elif not (ns.counterparty_id is not None and m.counterparty_id != ns.counterparty_id):
-                    surv, cond = base._cva_atoms[m_i]
-                    out = be.tangent_cva(book, datoms, rows, surv, cond, ns.threshold, m.recovery_rate, expo, ns_i, paths, dpaths, delayed, coll)
-                    for q, j in enumerate(sel):
-                        grads[ns_i][m_i][0][j] = mean_of(out[1 + q])
-        del paths, dpaths, cfs, expo
+        img = _main_dual_pass(ctx, chunk, coeffs, dcoeffs)
+        _scatter_metric_tangents(ctx, chunk, img, grads)
+        del img                                                               # the large dual tensors go before the next chunk's
         be.synchronize()
         t_main += time.perf_counter() - t2
     sc.sim_plan, sc.last_state = base.sim_plan, base.last_state
     sc.timings = dict(total=time.perf_counter() - t0, tangent=True, forward_mode_passes=(P + NP - 1) // NP,
                       base_run_and_descriptor_derivatives=t_desc, presim_and_regression=t_pre, main=t_main,
                       batched_lsm_jobs=n_batched)
-    g = [[[tuple(ev) for ev in grads[ns_i][m_i]] for m_i in range(n_metrics)] for ns_i in range(n_ns)]
+    g = [[[tuple(ev) for ev in per_metric] for per_metric in per_ns] for per_ns in grads]
     return sc._package([[[tuple(v) for v in evals] for evals in per_metric] for per_metric in res0.results], g, [])
 
 

@@ -24,7 +24,7 @@ from ..common.enums import SimulationScheme
 from ..common.packages import FLOAT, device
 from ..engine.engine import MonteCarloEngine
 from ..helpers.host_threads import single_threaded_host
-from ..maths.regression import PolyomialRegression, RegressionFunction
+from ..maths.regression import PolyomialRegression, RegressionFunction, regression_centering
 from ..metrics.metric import Metric, MetricType, mean_and_error
 from ..metrics.risk_metrics import PathwisePrimitive, RiskMetrics
 from ..models.model import Model
@@ -59,13 +59,10 @@ def storage_lsm_dates(S: int, K: int, sched, atoms, x_range, reg_base: int, expo
     for j, ((t_reg, r0, r1, prod_idx, expo_idx), (num, x)) in enumerate(zip(sched, atoms)):
         if r1 - r0 > 1:
             raise RuntimeError("internal: a storage step rolls at most one action date")
-        xmin, xmax = x_range[x]
-        degenerate = not (xmax > xmin)
         d = dates[j]
+        d["shift"], d["scale"], degenerate = regression_centering(x_range, x)
         d["roll_date"], d["num_atom"], d["x_atom"], d["degenerate"] = (r0 if r1 > r0 else -1), num, x, int(degenerate)
-        d["shift"] = 0.5 * (xmin + xmax) if not degenerate else xmin
-        d["scale"] = 2.0 / (xmax - xmin) if not degenerate else 1.0
-        d["x0"] = xmin
+        d["x0"] = x_range[x][0]
         d["coeff_off"][0] = -1 if prod_idx is None else reg_base + prod_idx * S * K
         d["coeff_off"][1] = -1 if expo_idx is None else expo_base + expo_idx * S * K
     return dates
@@ -583,6 +580,27 @@ class SimulationController:
             cache[key] = hit
         return hit
 
+    def _regression_plan(self):
+        """(jobs, storage_jobs): per Monte-Carlo product that needs a regression, in product order, (product index, product,
+        regression schedule, [(numeraire atom, explanatory atom)]); the storages are listed apart"""
+        jobs, storage_jobs = [], []
+        for p_i, p in enumerate(self.products):
+            if p_i not in self._mc_set or not self._product_requires_regression(p):
+                continue
+            sched = self._regression_schedule(p_i, p)
+            (storage_jobs if p_i in self._storage_meta else jobs).append((p_i, p, sched, self._regression_atoms(sched, p.asset_ids[0])))
+        return jobs, storage_jobs
+
+    def _explanatory_ranges(self, shard: Shard, plan, paths):
+        """{x atom: (min, max) over the paths of all ranks} of every explanatory variable of `plan` (conditioning of the monomial
+        basis; exact-degeneracy detection)"""
+        x_ids = sorted({x for _, _, _, atoms in plan for _, x in atoms})
+        if not x_ids:
+            return {}
+        g = shard.all_gather_np(self.backend.lsm_stats(self.book, x_ids, paths))
+        lo, hi = g[:, :, 0].min(axis=0), g[:, :, 1].max(axis=0)
+        return {x: (lo[i], hi[i]) for i, x in enumerate(x_ids)}
+
     def _perform_regression(self, shard: Shard, sim_plan: SimPlan, sim):
         be = self.backend
         off, n_local = shard.split(self.num_paths_presim)
@@ -594,26 +612,14 @@ class SimulationController:
         paths = eng.generate_paths_native()
         self.last_state["paths_pre"] = paths
         K = self.regression_function.get_degree()
-        comp = self._comp
-        jobs, storage_jobs = [], []
-        for p_i, p in enumerate(self.products):
-            if p_i not in self._mc_set or not self._product_requires_regression(p):
-                continue
-            sched = self._regression_schedule(p_i, p)
-            (storage_jobs if p_i in self._storage_meta else jobs).append((p_i, p, sched, self._regression_atoms(sched, p.asset_ids[0])))
+        jobs, storage_jobs = self._regression_plan()
         self._book_ready()               # (everything above ran beside a big book's upload)
         self._collapse_values(shard, paths)
         self._set_bridge_rng(eng.seed, off, "bridge_pre")
         self._set_exercise_replay("pre", n_local)
         if len(self._comp.atoms) != len(self.book_plan.atoms):
             raise RuntimeError("internal: regression atoms must be registered before the book is frozen")
-        # range of every explanatory variable (conditioning of the monomial basis; exact-degeneracy detection)
-        x_ids = sorted({x for _, _, _, atoms in jobs + storage_jobs for _, x in atoms})
-        if x_ids:
-            mm = be.lsm_stats(self.book, x_ids, paths)
-            g = shard.all_gather_np(mm)
-            lo, hi = g[:, :, 0].min(axis=0), g[:, :, 1].max(axis=0)
-            x_range = {x: (lo[i], hi[i]) for i, x in enumerate(x_ids)}
+        x_range = self._explanatory_ranges(shard, jobs + storage_jobs, paths)
         lsm_flags = (_abi.LSM_MFMA if self.use_mfma else 0) | (_abi.LSM_F32_CACHE if self.reference_float32_cf_cache else 0)
         if storage_jobs:
             if self.batch_storage_lsm and len(storage_jobs) >= 2 and hasattr(be, "storage_lsm_run_batch"):
@@ -635,13 +641,10 @@ class SimulationController:
                 continue
             W.zero_()
             for (t_reg, r0, r1, prod_idx, expo_idx), (num, x) in zip(sched, atoms):
-                xmin, xmax = x_range[x]
-                degenerate = not (xmax > xmin)
-                shift = 0.5 * (xmin + xmax) if not degenerate else xmin
-                scale = 2.0 / (xmax - xmin) if not degenerate else 1.0
+                shift, scale, degenerate = regression_centering(x_range, x)
                 mom = be.lsm_step(self.book, p_i, r0, r1, num, x, shift, scale, paths, W, flags=lsm_flags)
                 shard.all_reduce_(mom)
-                coeffs = solve_normal_equations(mom.detach().cpu().numpy(), K, S, shift, scale, degenerate, xmin)
+                coeffs = solve_normal_equations(mom.detach().cpu().numpy(), K, S, shift, scale, degenerate, x_range[x][0])
                 if prod_idx is not None:
                     p.regression_coeffs[prod_idx] = torch.from_numpy(coeffs)
                     be.book_set_coeffs(self.book, self._reg_coeff_base[p_i] + prod_idx * S * K, coeffs)
@@ -793,13 +796,10 @@ class SimulationController:
         (the caller then runs the per-date loop with the host solver, which falls back to lstsq)."""
         dates = np.zeros(len(sched), dtype=_abi.LSM_DATE_DTYPE)
         for j, ((t_reg, r0, r1, prod_idx, expo_idx), (num, x)) in enumerate(zip(sched, atoms)):
-            xmin, xmax = x_range[x]
-            degenerate = not (xmax > xmin)
             d = dates[j]
+            d["shift"], d["scale"], degenerate = regression_centering(x_range, x)
             d["roll_begin"], d["roll_end"], d["num_atom"], d["x_atom"], d["degenerate"] = r0, r1, num, x, int(degenerate)
-            d["shift"] = 0.5 * (xmin + xmax) if not degenerate else xmin
-            d["scale"] = 2.0 / (xmax - xmin) if not degenerate else 1.0
-            d["x0"] = xmin
+            d["x0"] = x_range[x][0]
             d["coeff_off"][0] = -1 if prod_idx is None else self._reg_coeff_base[p_i] + prod_idx * S * K
             d["coeff_off"][1] = -1 if expo_idx is None else self._expo_coeff_base[p_i] + expo_idx * S * K
         if shard is not None and shard.device_collectives:
@@ -1407,6 +1407,7 @@ class SimulationController:
         """a book that holds a storage is differentiated in forward mode or not at all: the reference's tape holds the storage
         policy fixed, while a bump-and-revalue run would difference across decision flips (replaying S x dates x N decisions is
         not built), and second-order differences of first-order passes inherit the same problem"""
+        from ..aad import no_tangent_form
         why = None
         if not hasattr(self.backend, "tangent_storage_eval"):
             why = "the backend has no mcx_tangent_storage_* entry points"
@@ -1420,7 +1421,7 @@ class SimulationController:
             except no_form as e:
                 why = f"the forward-mode pass cannot take this book ({e})"
             except RuntimeError as e:                           # MCX_E_NOT_FUSABLE from the library: no tangent form
-                if getattr(e, "code", None) != _abi.E_NOT_FUSABLE:
+                if not no_tangent_form(e):
                     raise
                 why = f"the forward-mode kernels cannot take this book ({e})"
         raise NotImplementedError(f"sensitivities through the storage policy are not implemented for this configuration: {why}")
@@ -1428,7 +1429,7 @@ class SimulationController:
     @single_threaded_host()
     def run_simulation(self) -> SimulationResults:
         if self.differentiate:
-            from ..aad import (_NoTangentForm, analytic_controller, run_analytic_with_autograd, run_with_bumps,
+            from ..aad import (_NoTangentForm, analytic_controller, no_tangent_form, run_analytic_with_autograd, run_with_bumps,
                                run_with_tangent_book, run_with_tangents, tangent_kernels_apply)
             if analytic_controller(self):
                 return run_analytic_with_autograd(self)             # PVMetric(ANALYTICAL): autograd on the closed form
@@ -1445,7 +1446,7 @@ class SimulationController:
                 except _NoTangentForm:
                     pass
                 except RuntimeError as e:                       # MCX_E_NOT_FUSABLE from the library: no tangent form
-                    if "(-10)" not in str(e):
+                    if not no_tangent_form(e):
                         raise
             return run_with_bumps(self)
         t0 = time.perf_counter()

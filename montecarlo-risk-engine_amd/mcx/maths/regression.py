@@ -22,3 +22,13 @@ class PolyomialRegression(RegressionFunction):  # (sic) the reference's spelling
 
 
 PolynomialRegression = PolyomialRegression
+
+
+def regression_centering(x_range, x):
+    """(shift, scale, degenerate) of the explanatory atom x: z = (x - shift) * scale maps its range over all ranks to [-1, 1];
+    degenerate: every path at one value (a regression at the calibration date).  x_range: {x atom: (min, max)}"""
+    xmin, xmax = x_range[x]
+    degenerate = not (xmax > xmin)
+    shift = 0.5 * (xmin + xmax) if not degenerate else xmin
+    scale = 2.0 / (xmax - xmin) if not degenerate else 1.0
+    return shift, scale, degenerate

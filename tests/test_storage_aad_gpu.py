@@ -261,19 +261,13 @@ def test_s2f_dual_paths_against_complex_step(name, hip):
     d_z = hip.from_numpy(np.ascontiguousarray(np.transpose(z, (0, 2, 1))))
     n = z.shape[1]
     cs = T.ComplexStep(sc, plan, z)
-    d0, shape0 = aad._host_descriptors(sc)
     P = cs.P
-    dd = {k: np.zeros(v.shape + (P,)) for k, v in d0.items()}
-    for j in range(P):
-        ev, shp = aad._host_descriptors(sc, cs.models[j], dtype=np.complex128)
-        assert shp == shape0
-        for k in dd:
-            dd[k][..., j] = ev[k].imag / cs.h[j]
+    _, dd = aad.descriptor_tangents(sc, sc.model, False, mode="complex")      # the driver's descriptor tangents, [...][P]
     primal = hip.generate_paths(sim, 43, 0, n, inject_z=d_z).cpu().numpy()
     assert np.allclose(primal, cs.paths, rtol=1e-11, atol=1e-13)
     for c0 in range(0, P, NP):
         sel = list(range(c0, min(c0 + NP, P)))
-        pad = lambda a: np.ascontiguousarray(np.concatenate([a[..., sel], np.zeros(a.shape[:-1] + (NP - len(sel),))], axis=-1))
+        pad = lambda a: aad.pad_chunk(a, sel)
         paths, dpaths = hip.tangent_paths_s2f(sim, pad(dd["slots"]), pad(dd["init"]), pad(dd["aux"]), pad(dd["chol"]), 43, 0, n, d_z)
         assert np.array_equal(paths.cpu().numpy(), primal), (name, "the primal image is mcx_generate_paths'")
         got = dpaths.cpu().numpy()

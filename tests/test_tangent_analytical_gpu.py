@@ -10,6 +10,7 @@ driven by mcx.aad.run_with_tangent_book).
   5. end to end against the reference's autograd (fixtures of tests/analytical_aad_cases.py); the fallback of a book the forward
      pass still cannot take; three emulated ranks."""
 import copy
+import types
 
 import numpy as np
 import pytest
@@ -43,17 +44,12 @@ def _sim_numbers(model, plan, dtype=np.float64):
 
 
 def _derivatives(model, plan):
-    """d (slots, init, aux, chol) / d theta_j for every parameter, by complex step: [..., P]"""
-    P = len(model.get_model_params())
-    d0 = _sim_numbers(model, plan)
-    dd = {k: np.zeros(v.shape + (P,)) for k, v in d0.items()}
-    for j in range(P):
-        m = copy.deepcopy(model)
-        h = 1e-30 * max(abs(float(model.get_model_params()[j].detach())), 1e-2)
-        aad._set_complex_step(m, j, h)
-        ev = _sim_numbers(m, plan, np.complex128)
-        for k in dd:
-            dd[k][..., j] = ev[k].imag / h
+    """d (slots, init, aux, chol) / d theta_j for every parameter, by complex step: [..., P] — the driver's own descriptor tangents
+    on a bare simulation (a book without atoms)"""
+    bare = types.SimpleNamespace(sim_plan=plan, _comp=types.SimpleNamespace(atoms=[], atom_src=[]))
+    d0, dd = aad.descriptor_tangents(bare, model, False, mode="complex")
+    want = _sim_numbers(model, plan)
+    assert all(np.array_equal(d0[k], want[k]) for k in want)
     return dd
 
 
@@ -89,8 +85,7 @@ def _restated_paths(model, plan, z, j, h):
 def _chunks(dd, P):
     for c0 in range(0, P, NP):
         sel = list(range(c0, min(c0 + NP, P)))
-        pad = lambda a: np.ascontiguousarray(np.concatenate([a[..., sel], np.zeros(a.shape[:-1] + (NP - len(sel),))], axis=-1))
-        yield sel, {k: pad(v) for k, v in dd.items()}
+        yield sel, {k: aad.pad_chunk(v, sel) for k, v in dd.items()}
 
 
 @pytest.fixture(scope="module")

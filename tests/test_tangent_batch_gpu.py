@@ -33,12 +33,6 @@ def _mixed_cva_book(hip, degree):
     return sc
 
 
-def _plan_of(sc):
-    jobs = [(p_i, p) for p_i, p in enumerate(sc.products) if p_i in sc._mc_set and sc._product_requires_regression(p)]
-    plan = [(p_i, p, sc._regression_schedule(p_i, p)) for p_i, p in jobs]
-    return [(p_i, p, sched, sc._regression_atoms(sched, p.asset_ids[0])) for p_i, p, sched in plan]
-
-
 def _dual_inputs(sc, hip, n, ld, seed):
     """Philox dual paths of n paths in [T][D][ld] tensors whose columns >= n are NaN, random descriptor tangents, and the job table
     of every (stateless product, regression date) pair plus one job with an empty cash range"""
@@ -52,7 +46,7 @@ def _dual_inputs(sc, hip, n, ld, seed):
     h_datoms = rng.normal(0.0, 0.3, (len(sc.book_plan.atoms), 5, NP))
     h_datoms[:, 3:] *= 0.1                                                  # (tangents of the exponent's coefficients)
     datoms = hip.from_numpy(h_datoms)
-    lsm_plan = _plan_of(sc)
+    lsm_plan, _ = sc._regression_plan()
     x_ids = sorted({x for _, _, _, atoms in lsm_plan for _, x in atoms})
     stats = hip.lsm_stats(sc.book, x_ids, paths)
     x_range = {x: (stats[i, 0], stats[i, 1]) for i, x in enumerate(x_ids)}

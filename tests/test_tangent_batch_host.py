@@ -17,20 +17,13 @@ from mcx import _abi, _native
 from test_oracle_golden import check_lsm_sensitivities
 
 
-def _plan_of(sc):
-    """the regression plan run_with_tangent_book builds from its compiled base controller"""
-    jobs = [(p_i, p) for p_i, p in enumerate(sc.products) if p_i in sc._mc_set and sc._product_requires_regression(p)]
-    plan = [(p_i, p, sc._regression_schedule(p_i, p)) for p_i, p in jobs]
-    return [(p_i, p, sched, sc._regression_atoms(sched, p.asset_ids[0])) for p_i, p, sched in plan]
-
-
 def test_job_table_is_what_the_per_job_loop_passes_on_mixed_cva(oracle):
     from mcx.aad import stateless_lsm_jobs
     sc, _ = cases.make_controller("mixed_cva", oracle)
     sc.run_simulation()
-    plan = _plan_of(sc)
+    plan, storage_plan = sc._regression_plan()              # what run_with_tangent_book regresses on (no storage in this book)
     K = sc.book_plan.n_basis
-    assert len(plan) == 4 and K == 3
+    assert len(plan) == 4 and K == 3 and not storage_plan
     x_ids = sorted({x for _, _, _, atoms in plan for _, x in atoms})
     # ranges as lsm_stats would return them, the first atom degenerate (every path at one value, as at the calibration date)
     x_range = {x: ((0.25 * x - 1.0, 0.25 * x + 0.5 + 0.125 * k) if k else (1.5, 1.5)) for k, x in enumerate(x_ids)}

@@ -16,7 +16,6 @@ import cases
 from mcx import _abi
 from mcx._native import McxError
 from mcx.plan import SimPlan
-from test_tangent_batch_gpu import _plan_of
 
 pytestmark = pytest.mark.gpu
 NP = _abi.TANGENT_NP
@@ -52,7 +51,7 @@ def _book_inputs(build, hip, n, seed):
     bp = sc.book_plan
     h_datoms = rng.normal(0.0, 0.3, (len(bp.atoms), 5, NP))
     h_datoms[:, 3:] *= 0.1
-    lsm_plan = _plan_of(sc)
+    lsm_plan, _ = sc._regression_plan()
     x_ids = sorted({x for _, _, _, atoms in lsm_plan for _, x in atoms})
     stats = hip.lsm_stats(sc.book, x_ids, paths)
     table, _ = stateless_lsm_jobs(lsm_plan, {x: (stats[i, 0], stats[i, 1]) for i, x in enumerate(x_ids)}, sc._expo_coeff_base, bp.n_basis)
