@@ -437,9 +437,22 @@ int  mcx_tangent_european(mcx_handle* h, const mcx_sim* sim, const mcx_tangent_o
  *   d_datoms [n_atoms][5][NP] = d(a, d, b, c0, c1)                                                          (book, device)
  * Tangent tensors carry the parameter index outermost: d_dpaths [NP][T][D][ld], d_cfs [1+NP][n_ns][ld] (index 0 = value),
  * d_expo [1+NP][n_ns][n_rows][ld].  Scope: EULER with BS / Vasicek / CIR++ slots, ANALYTICAL with BS / Vasicek slots
- * (mcx_tangent_paths_chol); cashflow, plain option, exercise and polynomial-exposure events; otherwise MCX_E_NOT_FUSABLE (the caller
- * falls back to bump-and-revalue). */
+ * (mcx_tangent_paths_chol); cashflow, plain option, exercise and polynomial-exposure events; option events in the payoff modes
+ * aux[0] = 1..5 (geometric, control variate, binary, barrier, barrier with bridge) in mcx_tangent_lsm, mcx_tangent_lsm_batch and
+ * mcx_tangent_eval while the book is armed with mcx_book_set_payoff_tangents; otherwise MCX_E_NOT_FUSABLE (the caller falls back
+ * to bump-and-revalue). */
 #define MCX_TANGENT_NP 4
+/* Arms (d_dpayoff != NULL) or disarms (NULL: the state after mcx_book_create) the dual payoff forms of the book's option events in
+ * the modes 1..5.  d_dpayoff [n_events][MCX_TANGENT_NP], device memory of the caller that stays valid while the book is armed: row q
+ * is the tangent of the ONE host-computed payoff number of event q — d aux[1], the closed-form geometric price, for mode 2;
+ * d c, c = -2 / (sigma^2 maturity / n_obs) parked at coeff_off, for mode 5; zero in every other row.  The spots, the numeraire and
+ * the strike take their tangents from d_datoms / d_dpaths as everywhere; the bridge uniforms carry none and are the numbers the
+ * primal kernels use (mcx_book_set_bridge_rng: set it to the simulation the dual paths belong to).  While armed,
+ * mcx_tangent_lsm, mcx_tangent_lsm_batch and mcx_tangent_eval accept these events through a second instantiation of their kernels,
+ * selected only when an event the call visits holds such a mode: every other call runs the code it ran before.  Disarmed they
+ * refuse them with MCX_E_NOT_FUSABLE; mcx_tangent_lsm_step always does (exercise products emit none).  Synchronises the stream. */
+int  mcx_book_set_payoff_tangents(mcx_handle* h, mcx_book* book, const double* d_dpayoff /* [n_events][MCX_TANGENT_NP], device; NULL = off */,
+                                  void* stream);
 int  mcx_tangent_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
                        uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths, double* d_dpaths, int64_t ld,
                        const double* d_inject_z, void* stream);

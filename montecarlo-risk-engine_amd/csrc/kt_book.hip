@@ -15,7 +15,8 @@
 // Scope: EULER scheme with Black-Scholes / Vasicek / CIR++ (stochastic and deterministic) slots, ANALYTICAL scheme with Black-Scholes /
 // Vasicek slots (mcx_tangent_paths_chol: the Cholesky factor of the per-dt covariance carries a tangent); cashflow, plain option and
 // exercise events, polynomial (also state-indexed) and analytic Black-Scholes exposures; thresholds and MPoR collateral in the
-// metric kernels.  Anything else keeps the common-random-number bump path.
+// metric kernels; option events in the payoff modes 1-5 (geometric, control variate, binary, barrier, bridge) in kt_eval and
+// kt_lsm_batch while the book is armed (mcx_book_set_payoff_tangents).  Anything else keeps the common-random-number bump path.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -274,9 +275,126 @@ __device__ __forceinline__ DN kt_term_sum(const KTBook& b, const DevEvent& e, in
     return val;
 }
 
-// normalised dual cashflow of one stateless cash event (CASHFLOW or plain OPTION)
-__device__ __forceinline__ DN kt_cash_event(const KTBook& b, const DevEvent& e, const DevEventIds& id, int64_t i)
+// ---- payoff forms in dual numbers: MCX_EV_OPTION in the aggregation modes 1-5 ---------------------------------------------------
+// Each form restates its primal (k2_book.hip dev_cash_event, mcx_device.h dev_barrier_event) operation for operation, so the value
+// image is the primal's, and follows the reference's tape: the indicators are fuzzy (clamp: the gradient passes on the closed band,
+// dclamp), torch.max / torch.min over the monitored spots hand the gradient to the FIRST extremal spot in monitoring order, the
+// bridge uniforms carry no tangent.  The one host-computed number of an event — the closed-form geometric price aux[1] of mode 2, the
+// bridge constant c = -2 / (sigma^2 maturity / n_obs) of mode 5 — takes its tangent from row q of `dpayoff`
+// (mcx_book_set_payoff_tangents).  Compiled only into the EXOTIC instantiations of the kernels: the others keep their code.
+struct KTPayoff {
+    const double* __restrict__ coeffs;     // the book's coefficient array: (c, draw id) of a bridge event at its coeff_off
+    const double* __restrict__ dpayoff;    // [n_events][NP]
+    const DevBridge* __restrict__ bridge;  // RNG state of the bridge draws (mcx_book_set_bridge_rng): the primal kernels' numbers
+};
+
+__device__ __forceinline__ DN kt_wfma(double w, const DN& a, const DN& acc)       // acc + w a, every image one multiply-add
 {
+    DN r;
+    r.v = fma(w, a.v, acc.v);
+#pragma unroll
+    for (int q = 0; q < NP; ++q) r.d[q] = fma(w, a.d[q], acc.d[q]);
+    return r;
+}
+__device__ __forceinline__ DN kt_divc(const DN& a, double c)                      // a / c with the primal's true division in the value
+{
+    DN r;
+    r.v = a.v / c;
+    const double ic = 1.0 / c;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) r.d[q] = a.d[q] * ic;
+    return r;
+}
+// fuzzy indicator with eps = 0.05 (maths.py:8) as the primal writes it: clamp((x + 0.05) / 0.1, 0, 1)
+__device__ __forceinline__ DN kt_fuzzy(const DN& x) { return dclamp(kt_divc(x + 0.05, 0.1), 0.0, 1.0); }
+// barrier indicator of one level (dev_barrier_ind): 1 up-and-out, 2 down-and-out, 3 up-and-in, 4 down-and-in
+__device__ __forceinline__ DN kt_barrier_ind(int type, double level, const DN& mx, const DN& mn)
+{
+    const DN ind = (type & 1) ? kt_fuzzy(level - mx) : kt_fuzzy(mn - level);
+    return type <= 2 ? ind : 1.0 - ind;
+}
+
+__device__ __forceinline__ DN kt_barrier_event(const KTBook& b, const KTPayoff& px, const DevEvent& e, const DevEventIds& id, int q, int64_t i)
+{
+    const int types = (int)e.aux[3];
+    const int t1 = types & 7, t2 = types >> 3;
+    const bool with_bridge = e.aux[0] == 5.0;
+    DN mx = dconst<NP>(-1.0e300), mn = dconst<NP>(1.0e300), keep1 = dconst<NP>(1.0), keep2 = dconst<NP>(1.0);
+    DN prev1 = dconst<NP>(0.0), prev2 = dconst<NP>(0.0), c = dconst<NP>(0.0);
+    int draw_id = 0;
+    DevBridge br = {0, 0, nullptr, 0};
+    const double* __restrict__ inj = nullptr;
+    if (with_bridge) {
+        c = ld_dual(ldk(px.coeffs + e.coeff_off), px.dpayoff + (int64_t)q * NP);
+        draw_id = (int)ldk(px.coeffs + e.coeff_off + 1);
+        br = ldk_struct(px.bridge);
+        if (br.inject) inj = br.inject[draw_id];
+    }
+    for (int j = e.term_begin; j < e.term_end; ++j) {
+        const DN s = kt_atom(b, ldk_struct(&b.terms[j]).atom, ldk(b.term_atom + j), i);
+        if (s.v > mx.v) mx = s;                              // strict: the first extremal spot keeps the gradient
+        if (s.v < mn.v) mn = s;
+        if (with_bridge) {
+            const DN cur1 = dlog(kt_divc(s, e.aux[1])), cur2 = t2 ? dlog(kt_divc(s, e.aux[2])) : dconst<NP>(0.0);
+            if (j > e.term_begin) {
+                const int k = j - e.term_begin - 1;          // interval index
+                for (int bi = 0; bi < (t2 ? 2 : 1); ++bi) {
+                    const DN p = dexp(c * (bi ? prev2 * cur2 : prev1 * cur1));
+                    double u;
+                    if (inj) u = inj[(int64_t)(2 * k + bi) * br.ld + i];
+                    else {
+                        uint32_t w0, w1, w2, w3;
+                        const uint64_t path = br.path_offset + (uint64_t)i;
+                        philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), (uint32_t)k, 0x80000000u | (uint32_t)(2 * draw_id + bi),
+                                      (uint32_t)br.seed, (uint32_t)(br.seed >> 32), w0, w1, w2, w3);
+                        u = u53(w0, w1);
+                    }
+                    const DN miss = 1.0 - kt_fuzzy(p - u);   // 1 - compute_degree_of_truth(p - u, True)
+                    if (bi) keep2 = keep2 * miss; else keep1 = keep1 * miss;
+                }
+            }
+            prev1 = cur1; prev2 = cur2;
+        }
+    }
+    DN pay = dmax0((kt_atom(b, e.x, id.x, i) - e.strike) * e.sign) * kt_barrier_ind(t1, e.aux[1], mx, mn);
+    if (with_bridge) pay = pay * ((t1 <= 2) ? keep1 : 1.0 - keep1);       // out: never hit; in: hit at least once
+    if (t2) {
+        pay = pay * kt_barrier_ind(t2, e.aux[2], mx, mn);
+        if (with_bridge) pay = pay * ((t2 <= 2) ? keep2 : 1.0 - keep2);
+    }
+    return pay / kt_atom(b, e.num, id.num, i);
+}
+
+// modes 1 (geometric aggregate), 2 (arithmetic with the geometric control variate), 3 (binary); 4 / 5 above
+__device__ __forceinline__ DN kt_payoff_event(const KTBook& b, const KTPayoff& px, const DevEvent& e, const DevEventIds& id, int q, int64_t i)
+{
+    if (e.aux[0] == 4.0 || e.aux[0] == 5.0) return kt_barrier_event(b, px, e, id, q, i);
+    const DN num = kt_atom(b, e.num, id.num, i);
+    const bool binary = e.aux[0] == 3.0;
+    DN val = dconst<NP>(0.0), glog = dconst<NP>(0.0);
+    for (int j = e.term_begin; j < e.term_end; ++j) {
+        const DevTerm tm = ldk_struct(&b.terms[j]);
+        const DN av = kt_atom(b, tm.atom, ldk(b.term_atom + j), i);
+        if (binary) { val = kt_wfma(tm.w, av, val); continue; }
+        val = val + av * tm.w;
+        glog = kt_wfma(tm.w, dlog(av + 1e-10), glog);                     // basket_option.py:62-65
+    }
+    if (binary) {                                                         // binary_option.py:38-43
+        const DN dot = dclamp(kt_divc(val - e.strike + e.aux[2], 2.0 * e.aux[2]), 0.0, 1.0);
+        return ((e.sign > 0.0 ? dot : 1.0 - dot) * e.aux[1]) / num;
+    }
+    const DN geo = dmax0((dexp(glog) - e.strike) * e.sign);
+    if (e.aux[0] == 1.0) return geo / num;
+    const DN imm = dmax0((val - e.strike) * e.sign);                      // basket_option.py:72-78
+    return (imm - geo + ld_dual(e.aux[1], px.dpayoff + (int64_t)q * NP)) / num;
+}
+
+// normalised dual cashflow of one stateless cash event q (CASHFLOW or OPTION; the payoff modes only where EXOTIC)
+template <bool EXOTIC = false>
+__device__ __forceinline__ DN kt_cash_event(const KTBook& b, const DevEvent& e, const DevEventIds& id, int64_t i, const KTPayoff* px = nullptr,
+                                            int q = 0)
+{
+    if (EXOTIC && e.kind == MCX_EV_OPTION && e.aux[0] != 0.0) return kt_payoff_event(b, *px, e, id, q, i);
     const DN num = kt_atom(b, e.num, id.num, i);
     DN own;
     const DN val = kt_term_sum(b, e, i, own);
@@ -441,13 +559,22 @@ struct KTLBatchArgs {
     const KTLJob* __restrict__ jobs;           // [gridDim.y] the jobs of this launch
     double* __restrict__ partials;             // [gridDim.y][gridDim.x][(1+NP)][NM]
 };
+// the arguments of a kernel's EXOTIC instantiation: the plain ones, then the payoff state.  The plain instantiation keeps the plain
+// record, and with it the layout of its kernel arguments
+template <class Args> struct KTWithPayoff { Args a; KTPayoff px; };
+template <class Args, bool EXOTIC> using KTArgsOf = std::conditional_t<EXOTIC, KTWithPayoff<Args>, Args>;
+template <class Args> __device__ __forceinline__ const Args& kt_plain(const Args& a) { return a; }
+template <class Args> __device__ __forceinline__ const Args& kt_plain(const KTWithPayoff<Args>& x) { return x.a; }
+template <class Args> __device__ __forceinline__ const KTPayoff* kt_payoff_of(const Args&) { return nullptr; }
+template <class Args> __device__ __forceinline__ const KTPayoff* kt_payoff_of(const KTWithPayoff<Args>& x) { return &x.px; }
 
 // grid (tiles, jobs): block (t, j) takes the paths t, t + tiles, ... of job j in blocks of MCX_BLOCK, so the order of every sum of
 // a job depends on the path count alone, not on the jobs around it.  The job is wave-uniform: its record arrives through scalar
 // loads, as the events do.
-template <int K>
-__global__ __launch_bounds__(MCX_BLOCK) void kt_lsm_batch(const KTLBatchArgs a)
+template <int K, bool EXOTIC>
+__global__ __launch_bounds__(MCX_BLOCK) void kt_lsm_batch(const KTArgsOf<KTLBatchArgs, EXOTIC> ax)
 {
+    const KTLBatchArgs& a = kt_plain(ax);
     constexpr int NM = (2 * K - 1) + K;
     const KTLJob j = ldk_struct(&a.jobs[blockIdx.y]);
     double acc[1 + NP][NM];
@@ -458,7 +585,7 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_lsm_batch(const KTLBatchArgs a)
     for (int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x; i < a.b.n; i += (int64_t)gridDim.x * MCX_BLOCK) {
         DN total[1] = {dconst<NP>(0.0)};
         for (int q = j.ev_first; q < j.ev_end; ++q)                                       // controller.py:333-352 without the cache
-            total[0] = total[0] + kt_cash_event(a.b, ldk_struct(&a.b.events[q]), ldk_struct(&a.b.ev_ids[q]), i);
+            total[0] = total[0] + kt_cash_event<EXOTIC>(a.b, ldk_struct(&a.b.events[q]), ldk_struct(&a.b.ev_ids[q]), i, kt_payoff_of(ax), q);
         const DN num = kt_atom(a.b, j.num, j.num_id, i);                                   // :368
         const DN z = (kt_atom(a.b, j.x, j.x_id, i) - j.shift) * j.scale;
         kt_moments_add<K, 1>(acc, z, num, total);
@@ -478,8 +605,10 @@ struct KTEArgs {
     int32_t n_products, n_ns, n_rows, pad;
 };
 
-__global__ __launch_bounds__(MCX_BLOCK) void kt_eval(const KTEArgs a)
+template <bool EXOTIC>
+__global__ __launch_bounds__(MCX_BLOCK) void kt_eval(const KTArgsOf<KTEArgs, EXOTIC> ax)
 {
+    const KTEArgs& a = kt_plain(ax);
     const int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x;
     if (i >= a.b.n) return;
     const int K = a.b.n_basis;
@@ -492,7 +621,7 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_eval(const KTEArgs a)
             const DevEvent e = ldk_struct(&a.b.events[q]);
             const DevEventIds id = ldk_struct(&a.b.ev_ids[q]);
             if (e.kind <= MCX_EV_OPTION) {
-                acc = acc + kt_cash_event(a.b, e, id, i);
+                acc = acc + kt_cash_event<EXOTIC>(a.b, e, id, i, kt_payoff_of(ax), q);
             } else if (e.kind == MCX_EV_EXERCISE) {
                 // decision from the primal values, tangent through the taken branch only (bermudan_option.py:93-131)
                 const KTExercise ev = kt_exercise_value(a.b, e, id, i);
@@ -696,14 +825,20 @@ int fill_book(mcx_handle* h, const mcx_book* b, const double* d_datoms, const do
 }
 
 // does event e have a tangent form?  `allowed`: the kinds the caller's kernel handles, one bit (1 << MCX_EV_*) each.  Of those,
-// options in plain mode and exercise events under the Bermudan (0) or FlexiCall (1) rule, neither over per-term denominators
-// (kt_term_sum's `own` is read by CASHFLOW events only).  The callers word their own messages.
+// options in plain mode — in the payoff modes 1-5 where the caller's kernel has them AND the book is armed with their host tangents
+// (KT_PAYOFF_MODES; mcx_book_set_payoff_tangents) — and exercise events under the Bermudan (0) or FlexiCall (1) rule, neither over
+// per-term denominators (kt_term_sum's `own` is read by CASHFLOW events only).  The callers word their own messages.
 enum KTForm { KT_FORM_OK = 0, KT_FORM_NONE, KT_FORM_TERM_DEN };
 constexpr unsigned KT_CASH_KINDS = 1u << MCX_EV_CASHFLOW | 1u << MCX_EV_OPTION;
+constexpr unsigned KT_PAYOFF_MODES = 1u << 31;
+bool kt_payoff_mode(const DevEvent& e) { return e.kind == MCX_EV_OPTION && e.aux[0] != 0.0; }
 KTForm kt_tangent_form(const mcx_book* b, const DevEvent& e, unsigned allowed)
 {
     if (e.kind < 0 || e.kind > MCX_EV_EXPO_BS || !(allowed >> e.kind & 1u)) return KT_FORM_NONE;
-    if (e.kind == MCX_EV_OPTION && e.aux[0] != 0.0) return KT_FORM_NONE;
+    if (kt_payoff_mode(e)) {
+        const bool known = e.aux[0] == 1.0 || e.aux[0] == 2.0 || e.aux[0] == 3.0 || e.aux[0] == 4.0 || e.aux[0] == 5.0;
+        if (!((allowed & KT_PAYOFF_MODES) && b->d_dpayoff && known)) return KT_FORM_NONE;
+    }
     if (e.kind == MCX_EV_EXERCISE && e.aux[0] != 0.0 && e.aux[0] != 1.0) return KT_FORM_NONE;
     if (e.kind == MCX_EV_OPTION || e.kind == MCX_EV_EXERCISE)
         for (int j = e.term_begin; j < e.term_end; ++j)
@@ -731,7 +866,7 @@ int ktl_check_job(mcx_handle* h, const mcx_book* b, const mcx_tangent_lsm_job& q
     if (pr.n_states != 1) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: stateless products only", who);
     const int n_cf = pr.cf_end - pr.cf_begin;
     if (q.first_event < 0 || q.first_event > n_cf) MCX_FAIL(h, -2, "%s: first_event out of range", who);
-    if (int rc = kt_check_cash_events(h, b, pr.cf_begin, pr.cf_end, KT_CASH_KINDS, who)) return rc;
+    if (int rc = kt_check_cash_events(h, b, pr.cf_begin, pr.cf_end, KT_CASH_KINDS | KT_PAYOFF_MODES, who)) return rc;
     if (q.num_atom < 0 || q.num_atom >= b->n_atoms || q.x_atom < 0 || q.x_atom >= b->n_atoms) MCX_FAIL(h, -2, "%s: atom out of range", who);
     memset(out, 0, sizeof(*out));
     out->num = mcx_flat_atom(b->h_atoms[q.num_atom]); out->x = mcx_flat_atom(b->h_atoms[q.x_atom]); out->num_id = q.num_atom; out->x_id = q.x_atom;
@@ -785,11 +920,20 @@ int ktl_run(mcx_handle* h, const mcx_book* b, const mcx_tangent_lsm_job* h_jobs,
     double* d_out = (double*)mcx_scratch(h, 3, out_bytes);
     if (!d_jobs || !d_out) return -100;
     a.partials = h->d_ws;
+    // the payoff forms are compiled into a second instantiation, taken only when an event some job visits holds one
+    bool exotic = false;
+    for (int j = 0; j < n_jobs && !exotic; ++j)
+        for (int q = jobs[j].ev_first; q < jobs[j].ev_end && !exotic; ++q) exotic = kt_payoff_mode(b->h_events[q]);
+    KTWithPayoff<KTLBatchArgs> ax;
+    memset(&ax, 0, sizeof(ax));
+    ax.px.coeffs = b->d_coeffs; ax.px.dpayoff = b->d_dpayoff; ax.px.bridge = b->d_bridge;
     int rc = 0;
     for (size_t j0 = 0; j0 < (size_t)n_jobs && rc == 0; j0 += per_launch) {
         const size_t nj = std::min(per_launch, (size_t)n_jobs - j0);
         a.jobs = d_jobs + j0;
-        MCX_DISPATCH(KK, K, 4, hipLaunchKernelGGL((kt_lsm_batch<KK>), dim3((unsigned)tiles, (unsigned)nj), dim3(MCX_BLOCK), 0, s, a));
+        ax.a = a;
+        if (exotic) { MCX_DISPATCH(KK, K, 4, hipLaunchKernelGGL((kt_lsm_batch<KK, true>), dim3((unsigned)tiles, (unsigned)nj), dim3(MCX_BLOCK), 0, s, ax)); }
+        else { MCX_DISPATCH(KK, K, 4, hipLaunchKernelGGL((kt_lsm_batch<KK, false>), dim3((unsigned)tiles, (unsigned)nj), dim3(MCX_BLOCK), 0, s, a)); }
         rc = mcx_sum_partials(h, h->d_ws, (int)nj, tiles, count, d_out + j0 * count, s);
     }
     // the stream is drained before returning, also after a failed launch; h_moments is written by the one copy only
@@ -948,12 +1092,14 @@ extern "C" int mcx_tangent_eval(mcx_handle* h, const mcx_book* b, const double* 
 {
     if (!h || !b || !d_datoms || !d_coeffs || !d_dcoeffs || !d_paths || !d_dpaths || !d_cfs || !d_expo) return -1;
     if (n_paths <= 0) return 0;
+    bool exotic = false;                                   // an event of a payoff mode: the second instantiation of the kernel
     for (int p = 0; p < b->n_products; ++p) {
         const DevProduct& pr = b->h_products[p];
-        const unsigned allowed = KT_CASH_KINDS | 1u << MCX_EV_EXPO_POLY | (h_ev_param ? 1u << MCX_EV_EXPO_BS : 0u) |
+        const unsigned allowed = KT_CASH_KINDS | KT_PAYOFF_MODES | 1u << MCX_EV_EXPO_POLY | (h_ev_param ? 1u << MCX_EV_EXPO_BS : 0u) |
                                  (pr.n_states > 1 ? 1u << MCX_EV_EXERCISE : 0u);
         for (int q = pr.ev_begin; q < pr.ev_end; ++q) {
             const DevEvent& e = b->h_events[q];
+            exotic = exotic || kt_payoff_mode(e);
             const KTForm f = kt_tangent_form(b, e, allowed);
             if (f == KT_FORM_NONE) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_eval: event %d (kind %d) has no tangent form", q, e.kind);
             if (f == KT_FORM_TERM_DEN) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "mcx_tangent_eval: option over per-term denominators");
@@ -969,9 +1115,23 @@ extern "C" int mcx_tangent_eval(mcx_handle* h, const mcx_book* b, const double* 
     MCX_HIP(h, hipMemsetAsync(d_expo, 0, sizeof(double) * (size_t)(1 + NP) * b->n_netting_sets * n_rows * ld, s));
     a.products = b->d_products; a.coeffs = d_coeffs; a.dcoeffs = d_dcoeffs; a.cfs = d_cfs; a.expo = d_expo; a.n_products = b->n_products;
     a.n_ns = b->n_netting_sets; a.n_rows = n_rows;
-    hipLaunchKernelGGL(kt_eval, dim3((unsigned)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK)), dim3(MCX_BLOCK), 0, s, a);
+    const dim3 grid((unsigned)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK));
+    if (exotic) {
+        KTWithPayoff<KTEArgs> ax;
+        memset(&ax, 0, sizeof(ax));
+        ax.a = a; ax.px.coeffs = b->d_coeffs; ax.px.dpayoff = b->d_dpayoff; ax.px.bridge = b->d_bridge;
+        hipLaunchKernelGGL(kt_eval<true>, grid, dim3(MCX_BLOCK), 0, s, ax);
+    } else hipLaunchKernelGGL(kt_eval<false>, grid, dim3(MCX_BLOCK), 0, s, a);
     MCX_HIP(h, hipGetLastError());
     MCX_HIP(h, hipStreamSynchronize(s));
+    return 0;
+}
+
+extern "C" int mcx_book_set_payoff_tangents(mcx_handle* h, mcx_book* b, const double* d_dpayoff, void* stream)
+{
+    if (!h || !b) return -1;
+    MCX_HIP(h, hipStreamSynchronize((hipStream_t)stream));      // no call in flight reads the rows that are replaced
+    b->d_dpayoff = d_dpayoff;
     return 0;
 }
 

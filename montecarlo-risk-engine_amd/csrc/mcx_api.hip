@@ -208,7 +208,7 @@ extern "C" int mcx_book_create(mcx_handle* h, const mcx_book_desc* d, mcx_book**
     b->d_bridge = nullptr; b->d_bridge_inject = nullptr;
     b->ex_mode = 0; b->d_ex_bits = nullptr; b->ex_ld = 0;
     b->d_vpoly = nullptr; b->d_vcoef = nullptr;
-    b->d_event_ids = nullptr; b->d_term_atom = nullptr;
+    b->d_event_ids = nullptr; b->d_term_atom = nullptr; b->d_dpayoff = nullptr;
     b->h_event_vpoly.assign((size_t)d->n_events, -1);
     auto upload = [&](void** dst, const void* src, size_t bytes) -> bool {        // false: the error is in h->err; the caller frees
         hipError_t e = hipMalloc(dst, bytes ? bytes : 8);

@@ -145,6 +145,9 @@ struct mcx_book {
     // by the first forward-mode call that needs them (mcx_book_tangent_ids) and freed with the book
     mutable DevEventIds* d_event_ids;     // [n_events]
     mutable int32_t* d_term_atom;         // [n_terms]
+    // tangents of the host-computed payoff numbers of the events, [n_events][MCX_TANGENT_NP] on the device, owned by the caller
+    // (mcx_book_set_payoff_tangents); nullptr: the forward-mode entry points refuse the payoff modes 1-5
+    const double* d_dpayoff;
     // exercise decisions recorded (1) / replayed (2) by K2 and K3 (mcx_book_set_exercise_replay): [n_events][ex_ld] bytes
     int ex_mode;
     uint8_t* d_ex_bits;

@@ -22,7 +22,7 @@ _EXPORTS = [
     "mcx_sim_create", "mcx_sim_destroy", "mcx_generate_paths", "mcx_generate_paths_from_state", "mcx_sim_describe", "mcx_rng_draws",
     "mcx_comm_unique_id", "mcx_comm_init", "mcx_comm_destroy", "mcx_allreduce_f64", "mcx_allgather_f64",
     "mcx_book_create", "mcx_book_destroy", "mcx_book_set_coeffs", "mcx_eval_book", "mcx_eval_book_describe", "mcx_resolve_atoms",
-    "mcx_lsm_stats", "mcx_lsm_step", "mcx_lsm_run", "mcx_lsm_solve", "mcx_lsm_step_batch", "mcx_lsm_step_batch_dev", "mcx_lsm_solve_batch", "mcx_lsm_run_batch", "mcx_book_get_coeffs", "mcx_book_set_coeffs_batch", "mcx_book_set_bridge_rng", "mcx_book_set_exercise_replay",
+    "mcx_lsm_stats", "mcx_lsm_step", "mcx_lsm_run", "mcx_lsm_solve", "mcx_lsm_step_batch", "mcx_lsm_step_batch_dev", "mcx_lsm_solve_batch", "mcx_lsm_run_batch", "mcx_book_get_coeffs", "mcx_book_set_coeffs_batch", "mcx_book_set_bridge_rng", "mcx_book_set_exercise_replay", "mcx_book_set_payoff_tangents",
     "mcx_fused_is_straight_line", "mcx_tangent_paths", "mcx_tangent_paths_chol", "mcx_tangent_lsm", "mcx_tangent_lsm_batch", "mcx_tangent_lsm_step", "mcx_tangent_eval", "mcx_tangent_cva", "mcx_tangent_profiles", "mcx_tangent_pick",
     "mcx_box_muller", "mcx_tangent_european", "mcx_fused_create", "mcx_fused_destroy", "mcx_fused_num_records", "mcx_fused_run", "mcx_fused_eval_paths", "mcx_fused_run_device", "mcx_fused_eval_paths_device", "mcx_fused_set_timing", "mcx_fused_kernel_times", "mcx_fused_describe",
     "mcx_value_poly_fit", "mcx_book_collapse_values", "mcx_book_value_poly_info", "mcx_rows_minmax",
@@ -68,6 +68,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_tangent_storage_lsm_step.argtypes = [vp, vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp, i32, vp]
     lib.mcx_tangent_storage_eval.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i64, vp]
     lib.mcx_tangent_lsm_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, i64, i64, i32, vp, vp]
+    lib.mcx_book_set_payoff_tangents.argtypes = [vp, vp, vp, vp]
     lib.mcx_tangent_paths_s2f.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_tangent_paths_chol.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_sim_describe.argtypes = [C.c_void_p, C.c_void_p]
@@ -284,6 +285,16 @@ class HipBackend:
             table = arr
         self._check(self.lib.mcx_book_set_bridge_rng(self.h, book.ptr, C.c_uint64(seed), C.c_uint64(path_offset), table,
                                                      C.c_int64(ld), self._stream()), "mcx_book_set_bridge_rng")
+
+    def book_set_payoff_tangents(self, book, dpayoff: torch.Tensor | None):
+        """arm (dpayoff [n_events][NP] on the device: tangents of the host-computed payoff numbers) or disarm (None) the dual
+        payoff forms of the book's option events in the modes 1-5 (mcx_book_set_payoff_tangents); the tensor is kept alive here"""
+        if dpayoff is not None:
+            assert dpayoff.is_cuda and dpayoff.is_contiguous() and dpayoff.dtype == torch.float64
+            assert tuple(dpayoff.shape) == (len(book.plan.events), _abi.TANGENT_NP)
+        self._check(self.lib.mcx_book_set_payoff_tangents(self.h, book.ptr, _vp(dpayoff.data_ptr()) if dpayoff is not None else None,
+                                                          self._stream()), "mcx_book_set_payoff_tangents")
+        book.payoff_tangents = dpayoff
 
     def eval_book(self, book, paths: torch.Tensor):
         plan = book.plan
@@ -503,15 +514,18 @@ class HipBackend:
         return out
 
     def tangent_eval(self, book, datoms: torch.Tensor, coeffs: torch.Tensor, dcoeffs: torch.Tensor, paths: torch.Tensor,
-                     dpaths: torch.Tensor, ev_param: np.ndarray | None = None):
+                     dpaths: torch.Tensor, ev_param: np.ndarray | None = None, n_paths: int | None = None, out=None):
+        """n_paths: the paths of the [T][D][ld] tensors that count (default: all ld of them); out: (cfs, expo) to write into"""
         plan = book.plan
-        n = paths.shape[2]
+        ld = paths.shape[2]
+        n = ld if n_paths is None else int(n_paths)
         NP = _abi.TANGENT_NP
-        cfs = self.empty(1 + NP, plan.n_netting_sets, n)
-        expo = self.empty(1 + NP, plan.n_netting_sets, max(plan.n_expo_rows, 1), n)
+        assert n <= ld
+        cfs, expo = out if out is not None else (self.empty(1 + NP, plan.n_netting_sets, ld),
+                                                 self.empty(1 + NP, plan.n_netting_sets, max(plan.n_expo_rows, 1), ld))
         self._check(self.lib.mcx_tangent_eval(
             self.h, book.ptr, _vp(datoms.data_ptr()), _vp(coeffs.data_ptr()), _vp(dcoeffs.data_ptr()), _vp(paths.data_ptr()),
-            _vp(dpaths.data_ptr()), C.c_int64(n), C.c_int64(n), C.c_int32(paths.shape[0]), _vp(cfs.data_ptr()),
+            _vp(dpaths.data_ptr()), C.c_int64(n), C.c_int64(ld), C.c_int32(paths.shape[0]), _vp(cfs.data_ptr()),
             _vp(expo.data_ptr()), _abi.ptr(np.ascontiguousarray(ev_param, dtype=np.int32)) if ev_param is not None else None,
             self._stream()), "mcx_tangent_eval")
         return cfs, expo

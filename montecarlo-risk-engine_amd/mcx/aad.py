@@ -355,7 +355,7 @@ def no_tangent_form(e) -> bool:
 # The stages of run_with_tangent_book (DESIGN.md "Forward-mode book pass: the stages of the driver").  _BookPass: what every stage
 # of one differentiation reads; _Chunk: one group of <= TANGENT_NP parameters, their indices `sel` and their zero-padded descriptor
 # tangents; _Presim: the dual pre-simulation of a chunk and the coefficient images its regression fills; _Images: the main pass.
-_BookPass = namedtuple("_BookPass", "sc base be shard s2f chol batched rows base_coeffs")
+_BookPass = namedtuple("_BookPass", "sc base be shard s2f chol batched rows base_coeffs dpayoff", defaults=(None,))   # dpayoff: tangent_payoffs only
 _Chunk = namedtuple("_Chunk", "sel dslot dinit daux dchol datoms")
 _Presim = namedtuple("_Presim", "x_range paths dpaths n coeffs dcoeffs")
 _Images = namedtuple("_Images", "paths dpaths cfs expo")
@@ -432,6 +432,61 @@ def descriptor_tangents(base, model, smoothing, mode=None):
             else:
                 dd[k][..., j] = (ev[1][k] - ev[-1][k]) / (2.0 * h)
     return d0, dd
+
+
+def payoff_number_tangent(product, model, smoothing=False):
+    """Host only: d product._payoff_number / d theta, [P] — differentiated like every other descriptor number: ONE complex-step
+    evaluation per parameter where the closed form is complex-safe (it returns a complex number at theta_j + i h), otherwise the
+    4-point central differences of descriptor_tangents' fallback (real-only closed forms: the normal CDF of the geometric price)"""
+    theta = [float(p.detach()) for p in model.get_model_params()]
+    out = np.zeros(len(theta))
+
+    def at(**kw):
+        m = copy.deepcopy(model)
+        m.perform_smoothing = smoothing
+        if "step" in kw:
+            _set_complex_step(m, *kw["step"])
+        else:
+            _set_param(m, *kw["bump"])
+        return product._payoff_number(m)
+
+    for j, th in enumerate(theta):
+        h = 1e-30 * max(abs(th), 1e-2)
+        v = at(step=(j, h))
+        if isinstance(v, complex):
+            out[j] = v.imag / h
+            continue
+        h = 1e-3 * max(abs(th), 1e-2)
+        f = {mult: float(at(bump=(j, th + mult * h))) for mult in (1, -1, 2, -2)}
+        out[j] = (8.0 * (f[1] - f[-1]) - (f[2] - f[-2])) / (12.0 * h)
+    return out
+
+
+def payoff_tangents(base, model, smoothing=False):
+    """Host only: [n_events][P], row q = the derivative of the one host-computed payoff number of event q of the compiled
+    controller `base` (mode 2: the closed-form geometric price in aux[1]; mode 5: the bridge constant parked at coeff_off); zero
+    in every other row.  What mcx_book_set_payoff_tangents takes, P columns wide (pad_chunk cuts it per pass)"""
+    ev, prods = base.book_plan.events, base.book_plan.products
+    out = np.zeros((len(ev), len(model.get_model_params())))
+    for p_i, p in enumerate(base.products):
+        row = None
+        # a product's payoff event stands twice in the book: among the events of the main pass and among its cash events (LSM)
+        for q in [*range(int(prods["ev_begin"][p_i]), int(prods["ev_end"][p_i])), *range(int(prods["cf_begin"][p_i]), int(prods["cf_end"][p_i]))]:
+            if ev["kind"][q] == _abi.EV_OPTION and ev["aux"][q][0] in (2.0, 5.0):
+                if p._payoff_number(model) is None:
+                    raise _NoTangentForm("payoff number")
+                if row is None:
+                    row = payoff_number_tangent(p, model, smoothing)
+                out[q] = row
+    return out
+
+
+def payoff_forms_armed(sc, be) -> bool:
+    """does this differentiation arm the book's dual payoff forms?  SimulationController.tangent_payoffs on a backend with the
+    entry point — and no storage in the book: the payoff forms next to a storage's dual walk have not been compared with anything,
+    so such a book keeps the library's refusal, and with it the NotImplementedError of storage books"""
+    return bool(getattr(sc, "tangent_payoffs", False)) and hasattr(be, "book_set_payoff_tangents") \
+        and not any(getattr(p, "is_storage", False) for p in sc.products)
 
 
 def pad_chunk(a, sel):
@@ -555,6 +610,8 @@ def _regress_chunk(ctx, chunk, plan):
         return coeffs, dcoeffs, 0
     off, n_pre = ctx.shard.split(sc.num_paths_presim)
     paths, dpaths = _dual_paths(ctx, chunk, 42 + sc.seed_offset, off, n_pre, sc._inject.get("pre", (None, None))[0])
+    if ctx.dpayoff is not None:               # the bridge uniforms of the pre-simulation's paths (controller._perform_regression)
+        base._set_bridge_rng(42 + sc.seed_offset, off, "bridge_pre")
     pre = _Presim(base._explanatory_ranges(ctx.shard, plan, paths), paths, dpaths, n_pre, coeffs, dcoeffs)
     for job in plan:
         if job[0] in base._storage_meta:
@@ -590,6 +647,8 @@ def _main_dual_pass(ctx, chunk, coeffs, dcoeffs):
     sc, base, be = ctx.sc, ctx.base, ctx.be
     off, n_main = ctx.shard.split(sc.num_paths_mainsim)
     paths, dpaths = _dual_paths(ctx, chunk, 43 + sc.seed_offset, off, n_main, sc._inject.get("main", (None, None))[0])
+    if ctx.dpayoff is not None:               # back to the main simulation's bridge uniforms: the seed and path range of these paths
+        base._set_bridge_rng(43 + sc.seed_offset, off, "bridge_main")
     ev_param = _bs_exposure_slots(base, sc, chunk.sel)
     d_coeffs, d_dcoeffs = be.from_numpy(coeffs), be.from_numpy(dcoeffs)
     cfs, expo = be.tangent_eval(base.book, chunk.datoms, d_coeffs, d_dcoeffs, paths, dpaths, ev_param)
@@ -686,21 +745,33 @@ def run_with_tangent_book(sc):
     has_exercise = any(p.get_num_states() > 1 for p in sc.products)
     base_coeffs = np.asarray(be.book_get_coeffs(base.book), dtype=np.float64)[:n_coeffs] if (has_exercise and n_coeffs) else None
     rows = base.metric_exposure_indices.numpy().astype(np.int32) if sc.risk_metrics.requires_exposure_profiles() else np.zeros(0, dtype=np.int32)
-    ctx = _BookPass(sc, base, be, shard, s2f, chol, batched, rows, base_coeffs)
+    # SimulationController.tangent_payoffs: the payoff modes 1-5 in dual numbers.  The book is armed per chunk with the tangents of
+    # the events' host-computed numbers and disarmed at the end, also on an exception; without the flag (or the entry point) it is
+    # never armed, the library refuses such a book and the caller falls back to bump-and-revalue (payoff_forms_armed)
+    dpayoff = None
+    if payoff_forms_armed(sc, be):
+        dpayoff = payoff_tangents(base, sc.model, getattr(sc.model, "perform_smoothing", False))
+    ctx = _BookPass(sc, base, be, shard, s2f, chol, batched, rows, base_coeffs, dpayoff)
     n_batched = 0
-    for c0 in range(0, P, NP):
-        chunk = _parameter_chunk(ctx, dd, list(range(c0, min(c0 + NP, P))))
-        t1 = time.perf_counter()
-        coeffs, dcoeffs, n_pairs = _regress_chunk(ctx, chunk, plan)
-        n_batched += n_pairs
-        be.synchronize()
-        t2 = time.perf_counter()
-        t_pre += t2 - t1
-        img = _main_dual_pass(ctx, chunk, coeffs, dcoeffs)
-        _scatter_metric_tangents(ctx, chunk, img, grads)
-        del img                                                               # the large dual tensors go before the next chunk's
-        be.synchronize()
-        t_main += time.perf_counter() - t2
+    try:
+        for c0 in range(0, P, NP):
+            chunk = _parameter_chunk(ctx, dd, list(range(c0, min(c0 + NP, P))))
+            if dpayoff is not None:
+                be.book_set_payoff_tangents(base.book, be.from_numpy(pad_chunk(dpayoff, chunk.sel)))
+            t1 = time.perf_counter()
+            coeffs, dcoeffs, n_pairs = _regress_chunk(ctx, chunk, plan)
+            n_batched += n_pairs
+            be.synchronize()
+            t2 = time.perf_counter()
+            t_pre += t2 - t1
+            img = _main_dual_pass(ctx, chunk, coeffs, dcoeffs)
+            _scatter_metric_tangents(ctx, chunk, img, grads)
+            del img                                                           # the large dual tensors go before the next chunk's
+            be.synchronize()
+            t_main += time.perf_counter() - t2
+    finally:
+        if dpayoff is not None:
+            be.book_set_payoff_tangents(base.book, None)
     sc.sim_plan, sc.last_state = base.sim_plan, base.last_state
     sc.timings = dict(total=time.perf_counter() - t0, tangent=True, forward_mode_passes=(P + NP - 1) // NP,
                       base_run_and_descriptor_derivatives=t_desc, presim_and_regression=t_pre, main=t_main,

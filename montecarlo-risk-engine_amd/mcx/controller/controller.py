@@ -164,6 +164,10 @@ class SimulationController:
         self.batch_tangent_lsm = None
         self.storage_lsm_route = None        # "batch" / "single": the route the last storage pre-simulation took
         self.forward_mode = True     # differentiate=True: dual-number pass where it exists, bump-and-revalue otherwise
+        # differentiate=True: True arms the dual payoff forms of binary, barrier, geometric and control-variate options
+        # (mcx_book_set_payoff_tangents, mcx/aad.py payoff_tangents); False: a book that holds one keeps bump-and-revalue.  A book
+        # that also holds a storage is never armed and stays refused (aad.payoff_forms_armed)
+        self.tangent_payoffs = False
         # The reference compiles nothing: every run_simulation() sees the current state of its products / metrics.  Re-using the
         # compiled descriptors and the uploaded book of the previous run is an opt-in for callers that re-run an UNCHANGED
         # controller (bench.py, tools/run_configs.py); invalidate() drops the cache after a mutation.

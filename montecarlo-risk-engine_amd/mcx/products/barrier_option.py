@@ -58,6 +58,14 @@ class BarrierOption(Product):
     def _n_extra_coeffs(self) -> int:
         return 2 if self.use_brownian_bridge else 0
 
+    def _payoff_number(self, model):
+        """the bridge constant c of the crossing probability exp(c ln(S_k/B) ln(S_k+1/B)), c = -2 / (sigma^2 * maturity /
+        n_observations) (barrier_option.py:146); complex-safe in sigma"""
+        if not self.use_brownian_bridge:
+            return None
+        sigma = model._pf(1)
+        return -2.0 / (sigma * sigma * (self._T / len(self.modeling_timeline)))
+
     def _cash_events(self, ctx):
         if self.barrier_option_type1 not in _CODE:
             raise NotImplementedError(f"Barrier type {self.barrier_option_type1} not supported.")
@@ -71,9 +79,7 @@ class BarrierOption(Product):
             from ..models.black_scholes import BlackScholesModel
             if not isinstance(ctx.model, BlackScholesModel):
                 raise NotImplementedError("the Brownian-bridge correction reads model.get_volatility() of a single-asset Black-Scholes model")
-            sigma = ctx.model._pf(1)
-            # crossing probability exp(-2 ln(S_k/B) ln(S_k+1/B) / (sigma^2 * maturity / n_observations))   (barrier_option.py:146)
-            params = (-2.0 / (sigma * sigma * (self._T / len(obs))), float(ctx.current_product))
+            params = (self._payoff_number(ctx.model), float(ctx.current_product))
         sign = 1.0 if self.option_type == OptionType.CALL else -1.0
         # the maturity spot is the LAST monitored value (paths[:, -1], :70): read it at the last observation date
         return [CashEvent(_abi.EV_OPTION, self._T, terms, strike=self._K, sign=sign, aux=aux, x_asset=self.get_asset_id(),

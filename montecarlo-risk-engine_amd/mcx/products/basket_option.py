@@ -59,6 +59,13 @@ class BasketOption(Product):
             aux = (1.0 if self.basket_option_type == BasketOptionType.GEOMETRIC else 0.0, 0.0, 0.0, 0.0)
         return [CashEvent(_abi.EV_OPTION, self._T, terms, strike=self._K, sign=self._sign(), aux=aux)]
 
+    def _payoff_number(self, model):
+        """the closed-form geometric price an arithmetic payoff with the control variate adds (aux[1] of its event): a function of
+        every spot, every volatility and the rate through real-only code, hence a plain float"""
+        if not (self.use_variation_reduction and self.basket_option_type == BasketOptionType.ARITHMETIC):
+            return None
+        return float(self.compute_pv_analytically(model))
+
     # ---- host evaluation (API parity) ------------------------------------------------------------------------------
     def compute_payoff(self, spots: torch.Tensor, basket_option_type: BasketOptionType) -> torch.Tensor:
         zero = torch.tensor(0.0, dtype=FLOAT, device=spots.device)

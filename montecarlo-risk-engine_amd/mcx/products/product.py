@@ -115,6 +115,12 @@ class Product:
         """doubles this product parks in the coefficient array besides regression coefficients"""
         return 0
 
+    def _payoff_number(self, model):
+        """the ONE host-computed number the payoff event of this product carries besides its atoms, evaluated under `model` —
+        what the forward-mode pass differentiates per event (mcx/aad.py payoff_tangents); None: the payoff has none.  Written
+        with `model._pf` it is complex-safe and gets a complex-step derivative; a plain float gets 4-point differences"""
+        return None
+
     def supports_analytic_pv(self, model) -> bool:
         return False
 
