@@ -812,6 +812,26 @@ int  mcx_tangent_paths_s2f(mcx_handle* h, const mcx_sim* sim, const double* h_ds
                            const double* h_dchol, uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths,
                            double* d_dpaths, int64_t ld, const double* d_inject_z, void* stream);
 
+/* mcx_tangent_paths_heston: mcx_tangent_paths for a single MCX_MODEL_HESTON slot under EULER or QE (kt_book.hip kt_paths_heston): two
+ * normals and, under QE, one uniform per sub-step, on K1's Philox counters.  MCX_FLAG_SMOOTHING is read from the slot and the
+ * simulation flags as K1 reads it.  The value image is K1's arithmetic.  EULER: the variance draw is row 1 of L z with
+ * L = chol([[1, rho], [rho, 1]]), whose tangent is h_dchol; QE: the per-step constants carry their tangents in h_daux, h_dchol is
+ * not read.  Returns -1 for a NULL argument (h_dchol under EULER included), -2 for ld < n_paths, -3 for d_inject_z without
+ * d_inject_u under QE, MCX_E_NOT_FUSABLE (with the reason in mcx_last_error) for any other slot kind, slot count or scheme; a refused
+ * call enqueues nothing and writes nothing.  Synchronises the stream. */
+int  mcx_tangent_paths_heston(mcx_handle* h, const mcx_sim* sim,
+                              const double* h_dslot,   /* [1][MCX_SLOT_NPARAM][NP] */
+                              const double* h_dinit,   /* [2][NP] */
+                              const double* h_daux,    /* [n_steps][1][MCX_AUX][NP] */
+                              const double* h_dchol,   /* [n_chol][2][2][NP]; EULER: required; QE: ignored, may be NULL */
+                              uint64_t seed, uint64_t path_offset, int64_t n_paths,
+                              double* d_paths,         /* [T][2][ld]  (log S, v) */
+                              double* d_dpaths,        /* [NP][T][2][ld] */
+                              int64_t ld,
+                              const double* d_inject_z /* [n_steps][2][ld], nullable */,
+                              const double* d_inject_u /* [n_steps][ld], QE only */,
+                              void* stream);
+
 /* Multi-GPU exchange (paths shard over the GPUs of a node, one process per GPU; the only data that crosses
  * GPUs are accumulator records, LSM moments and select histograms).  RCCL over xGMI, loaded at run time (librccl.so.1 — the
  * library has no link-time dependency on it).  A caller without torch.distributed creates the id on rank 0

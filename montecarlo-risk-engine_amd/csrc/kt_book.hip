@@ -13,7 +13,8 @@
 //   kt_lsm_step : the same for products with exercise rights (Bermudan / American / FlexiCall): the cashflow cache rolled back
 //              along the FROZEN exercise policy in dual numbers, moments per hypothetical state
 // Scope: EULER scheme with Black-Scholes / Vasicek / CIR++ (stochastic and deterministic) slots, ANALYTICAL scheme with Black-Scholes /
-// Vasicek slots (mcx_tangent_paths_chol: the Cholesky factor of the per-dt covariance carries a tangent); cashflow, plain option and
+// Vasicek slots (mcx_tangent_paths_chol: the Cholesky factor of the per-dt covariance carries a tangent), a single Heston slot under
+// EULER or QE (mcx_tangent_paths_heston); cashflow, plain option and
 // exercise events, polynomial (also state-indexed) and analytic Black-Scholes exposures; thresholds and MPoR collateral in the
 // metric kernels; option events in the payoff modes 1-5 (geometric, control variate, binary, barrier, bridge) in kt_eval and
 // kt_lsm_batch while the book is armed (mcx_book_set_payoff_tangents).  Anything else keeps the common-random-number bump path.
@@ -233,6 +234,131 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_paths_chol(const KTPCholArgs ca)
         }
         const int st = sp.store_idx;
         if (st >= 0) ktp_store<NSLOT>(a, st, i, reg);
+    }
+}
+
+// The next variance of one Andersen QE step as a function of TWO numbers, vn = G(m, s2) (+ the draws u, z1), heston.py:185-236, in dual
+// numbers with two directions (d/dm, d/ds2): the caller's parameter tangents follow by the chain rule, d vn = G_m d m + G_s2 d s2 —
+// the ~30 operations of G carry 2 tangent components whatever the number of parameters.  Operation for operation the primal step
+// (mcx_device.h step_slot): the seven reciprocals in three groups from one v_rcp_f64 each, the two roots of b2 as one, every
+// denominator with the reference's eps, the NaN of a negative psi put in by hand.  A RESTATEMENT of the block in kt_heston
+// (kt_tangent.hip:201-235): called from there as a shared function it changed that kernel's register allocation.
+__device__ __forceinline__ Dual<2> ktp_qe_next_variance(double m, double s2, double u, double z1, bool fuzzy)
+{
+    const double eps = 1e-12;
+    Dual<2> M, S2;
+    M.v = m; M.d[0] = 1.0; M.d[1] = 0.0;
+    S2.v = s2; S2.d[0] = 0.0; S2.d[1] = 1.0;
+    const double omu = fmax(1.0 - u, eps);
+    const Dual<2> d1 = M * M + eps, d5 = M + eps;
+    const double d15 = d1.v * d5.v;
+    const double ra = mcx_rcp(d15 * omu);
+    const double r_omu = ra * d15, ra6 = ra * omu;
+    const Dual<2> psi = ddiv_r(S2, d1, ra6 * d5.v);
+    const Dual<2> d2 = psi + eps, d4 = psi + 1.0;
+    const double rb = mcx_rcp(d2.v * d4.v);
+    const Dual<2> invpsi = drcp_r(d2, rb * d4.v);
+    const Dual<2> t = dclamp_min(invpsi * 2.0 - 1.0, 0.0);
+    Dual<2> root = dsqrt(invpsi * 2.0 * t);
+    if (invpsi.v < 0.0) root.v = __builtin_nan("");          // torch.sqrt(2 / psi) of a negative psi (mcx_device.h, QE step)
+    const Dual<2> b2 = dclamp_min(invpsi * 2.0 - 1.0 + root, 0.0);
+    const Dual<2> b = dsqrt(b2);
+    const Dual<2> pp = dclamp(ddiv_r(psi - 1.0, d4, rb * d2.v), 0.0, 1.0 - 1e-6);
+    const Dual<2> beta = ddiv_r(1.0 - pp, d5, ra6 * d1.v);
+    const Dual<2> d3 = 1.0 + b2, d7 = beta + eps;
+    const double rc = mcx_rcp(d3.v * d7.v);
+    const Dual<2> aa = ddiv_r(M, d3, rc * d7.v);
+    const Dual<2> bz = b + z1;
+    const Dual<2> v1 = aa * bz * bz;
+    const Dual<2> omp = dclamp_min(1.0 - pp, eps);
+    const Dual<2> v_tail = ddiv_r(dlog(omp * r_omu), d7, rc * d3.v);
+    const Dual<2> w_mass = ddegree(u - pp, fuzzy, 0.3);
+    const Dual<2> v2 = w_mass * v_tail;
+    const Dual<2> w = ddegree(psi - 1.5, fuzzy, 0.5);
+    return (1.0 - w) * v1 + w * v2;
+}
+
+// kt_paths for a single Heston slot: state (log S, v), two normals per sub-step and, under QE, one uniform — K1's draws on K1's
+// counters.  The tangent images run the step maps of step_slot (mcx_device.h) in dual numbers, operation for operation:
+//   EULER (heston.py:109-121): the variance draw is row 1 of L z, L = chol([[1, rho], [rho, 1]]) — a dual row, value from k.chol and
+//     tangent from dchol (the reference's tape differentiates through the factorisation); clamps pass the gradient on the closed side;
+//   QE (heston.py:161-253): the aux row [E, K0, K1, K2, K3, K4, c1, c2] and its tangent row arrive through scalar loads, the map
+//     vn = G(m, s2) runs in Dual<2> (ktp_qe_next_variance) and the NP tangents follow by the chain rule.
+// The value image is not taken from the dual chain: step_slot itself advances the primal state, so image 0 is K1's arithmetic to the
+// bit (under -ffp-contract=on the dual operators round product and sum separately where step_slot's expressions fuse them) and the
+// frozen exercise policy of a dual pass sees the base run's values.  The price is a second evaluation of the step's value (~290
+// instructions under QE) and, with Philox draws, 161 VGPRs / 3 waves per SIMD.  Within a step the clamp and indicator MASKS of the
+// tangents are still taken from the dual chain's own unfused values, which start from the exact primal state but may differ from
+// the stored value in the last bits (and dclamp_min keeps a NaN where the primal's `b2u < 0 ? 0 : b2u` does too, by another route):
+// a path within rounding of a kink could carry the tangent of the other side.  That is the tie every float64 evaluation has at a
+// kink; the tests keep their inputs 1e-9 away from every one of them.  Initial state and stores as kt_paths (ktp_store).
+template <bool QE, bool INJECT>
+__global__ __launch_bounds__(MCX_BLOCK) void kt_paths_heston(const KTPCholArgs ca)
+{
+    const KTPArgs& a = ca.p;
+    const K1Args& k = a.k1;
+    __shared__ double bm_lds[INJECT ? 2 : MCX_BM_LDS_DOUBLES];
+    const double* tab = nullptr;
+    if (!INJECT) { mcx_bm_load(bm_lds); tab = bm_lds; }
+    const int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x;
+    if (i >= k.n) return;
+    const int c0 = k.slots[0].state_off;
+    DN reg[2];                                                                // (log S, v)
+    reg[0] = ld_dual(k.init_state[c0], a.dinit + (int64_t)c0 * NP);
+    reg[1] = ld_dual(k.init_state[c0 + 1], a.dinit + (int64_t)(c0 + 1) * NP);
+    for (int t = 0; t < k.n_initial_store; ++t) ktp_store<1>(a, t, i, reg);
+    const double* __restrict__ p = k.slots[0].p;                              // [spot, sigma_v, rate, rho, kappa, theta, v0]
+    const double* __restrict__ dp = a.dslot;
+    const int flags = k.flags | k.slots[0].flags;
+    const uint64_t path = k.path_offset + (uint64_t)i;
+#pragma unroll 1
+    for (int step = 0; step < k.n_steps; ++step) {
+        const mcx_step sp = ldk_struct(&k.steps[step]);
+        double z0, z1, u = 0.0;
+        if (INJECT) {
+            z0 = k.inject_z[((int64_t)step * 2 + 0) * k.ld + i];
+            z1 = k.inject_z[((int64_t)step * 2 + 1) * k.ld + i];
+            if (QE) u = k.inject_u[(int64_t)step * k.ld + i];
+        } else {
+            double ua;
+            draw_pair<true>(k.seed, path, (uint32_t)step, 0u, ua, z0, z1, tab);
+            if (QE) { double t0, t1; draw_pair(k.seed, path, (uint32_t)step, 1u, u, t0, t1); }
+        }
+        const double dt = sp.dt, sq = sp.sqrt_dt;
+        const double* __restrict__ ax = k.aux + (int64_t)step * MCX_AUX;
+        // row 1 of the ONE factor of an EULER / QE run (sim_apply: L00 = 1 exactly, QE's factor is the identity)
+        const double l10 = ldk(k.chol + 2), l11 = ldk(k.chol + 3);
+        double s0 = reg[0].v, s1 = reg[1].v;                                  // image 0: the primal step itself
+        step_slot<MCX_MODEL_HESTON, QE ? MCX_SCHEME_QE : MCX_SCHEME_EULER>(k.slots[0], k.scheme, flags, dt, sq, AuxPtr{ax}, s0, s1, z0,
+                                                                           fma(l11, z1, l10 * z0), u);
+        const DN rate = ld_dual(p[2], dp + 2 * NP), theta = ld_dual(p[5], dp + 5 * NP);
+        const DN v = reg[1];
+        DN vn;
+        if constexpr (!QE) {
+            const DN sigma = ld_dual(p[1], dp + 1 * NP), kappa = ld_dual(p[4], dp + 4 * NP);
+            const DN zc1 = ktp_fma(ld_dual(l11, ca.dchol + 3 * NP), z1, ld_dual(l10, ca.dchol + 2 * NP) * z0);
+            const DN sv = dsqrt(dclamp_min(v, 0.0));
+            reg[0] = reg[0] + (rate - v * 0.5) * dt + sv * (sq * z0);
+            vn = dclamp_min(v + kappa * (theta - v) * dt + sigma * sv * sq * zc1, 0.0);
+        } else {
+            const double* __restrict__ dax = a.daux + (int64_t)step * MCX_AUX * NP;
+            auto aux = [&](int e) __attribute__((always_inline)) { return ld_dual(ldk(ax + e), dax + e * NP); };
+            const double eps = 1e-12;
+            const DN m = theta + (v - theta) * aux(0);
+            const DN s2 = v * aux(6) + aux(7);
+            const Dual<2> vn2 = ktp_qe_next_variance(m.v, s2.v, u, z1, (flags & MCX_FLAG_SMOOTHING) != 0);
+            vn.v = vn2.v;
+#pragma unroll
+            for (int q = 0; q < NP; ++q) vn.d[q] = fma(vn2.d[0], m.d[q], vn2.d[1] * s2.d[q]);
+            const DN var_int = dclamp_min(aux(4) * v + aux(5) * vn, 0.0);     // (K4 v_next counts: the primal reads aux[5])
+            const DN vol = dsqrt(dclamp_min(var_int, eps));
+            reg[0] = reg[0] + rate * dt + aux(1) + aux(2) * v + aux(3) * vn + vol * z0;
+        }
+        reg[1] = vn;
+        reg[0].v = s0;
+        reg[1].v = s1;
+        const int st = sp.store_idx;
+        if (st >= 0) ktp_store<1>(a, st, i, reg);
     }
 }
 
@@ -1026,6 +1152,54 @@ extern "C" int mcx_tangent_paths_chol(mcx_handle* h, const mcx_sim* sim, const d
 {
     return ktp_paths(h, sim, h_dslot, h_dinit, h_daux, h_dchol, seed, path_offset, n_paths, d_paths, d_dpaths, ld, d_inject_z, stream,
                      "mcx_tangent_paths_chol", true);
+}
+
+// every check comes before the first upload: a refused call enqueues nothing and writes nothing
+extern "C" int mcx_tangent_paths_heston(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                                        const double* h_dchol, uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths,
+                                        double* d_dpaths, int64_t ld, const double* d_inject_z, const double* d_inject_u, void* stream)
+{
+    const char* who = "mcx_tangent_paths_heston";
+    if (!h || !sim || !h_dslot || !h_dinit || !h_daux || !d_paths || !d_dpaths) return -1;
+    const mcx_sim_desc& sd = sim->desc;
+    const bool euler = sd.scheme == MCX_SCHEME_EULER, qe = sd.scheme == MCX_SCHEME_QE;
+    if (euler && !h_dchol) return -1;
+    if (n_paths <= 0) return 0;
+    if (ld < n_paths) MCX_FAIL(h, -2, "%s: ld < n_paths", who);
+    if (sd.n_slots != 1 || sd.slots[0].kind != MCX_MODEL_HESTON || sd.n_z != 2 || sd.n_state != 2 || sd.slots[0].state_off != 0)
+        MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: a single Heston slot expected (%d slots, slot 0 of model kind %d)", who, (int)sd.n_slots,
+                 sd.n_slots > 0 ? (int)sd.slots[0].kind : 0);
+    if (!euler && !qe) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: scheme %d: EULER or QE scheme only", who, (int)sd.scheme);
+    if (qe && sd.n_uniform != 1) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: one uniform per sub-step expected under QE", who);
+    if (qe && d_inject_z && !d_inject_u) MCX_FAIL(h, -3, "%s: inject_u required with inject_z under QE", who);
+    if (sd.n_chol < 1) MCX_FAIL(h, -2, "%s: no Cholesky factor", who);
+    for (int k = 0; k < sd.n_steps; ++k) {                // the kernel reads factor 0 (one factor per EULER / QE run) and stores by store_idx
+        const mcx_step& sp = sim->h_steps[k];
+        if (sp.chol_idx != 0 || sp.store_idx >= sd.n_dates) MCX_FAIL(h, -2, "%s: step %d out of range", who, k);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    KTPCholArgs ac;
+    memset(&ac, 0, sizeof(ac));
+    KTPArgs& a = ac.p;
+    mcx_fill_k1_args(sim, seed, path_offset, n_paths, ld, d_paths, d_inject_z, d_inject_u, &a.k1);
+    a.dslot = (const double*)mcx_upload_table(h, 0, h_dslot, sizeof(double) * (size_t)MCX_SLOT_NPARAM * NP, s);
+    a.dinit = (const double*)mcx_upload_table(h, 1, h_dinit, sizeof(double) * (size_t)2 * NP, s);
+    a.daux = (const double*)mcx_upload_table(h, 2, h_daux, sizeof(double) * (size_t)sd.n_steps * MCX_AUX * NP, s);
+    if (!a.dslot || !a.dinit || !a.daux) return -100;
+    if (euler) {
+        ac.dchol = (const double*)mcx_upload_table(h, 3, h_dchol, sizeof(double) * (size_t)sd.n_chol * 4 * NP, s);
+        if (!ac.dchol) return -100;
+    }
+    a.dpaths = d_dpaths; a.pstride = (int64_t)sd.n_dates * 2 * ld; a.n_slots = 1;
+    const int grid = (int)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK);
+    const bool inj = d_inject_z != nullptr;
+    if (qe && inj) hipLaunchKernelGGL((kt_paths_heston<true, true>), dim3(grid), dim3(MCX_BLOCK), 0, s, ac);
+    else if (qe) hipLaunchKernelGGL((kt_paths_heston<true, false>), dim3(grid), dim3(MCX_BLOCK), 0, s, ac);
+    else if (inj) hipLaunchKernelGGL((kt_paths_heston<false, true>), dim3(grid), dim3(MCX_BLOCK), 0, s, ac);
+    else hipLaunchKernelGGL((kt_paths_heston<false, false>), dim3(grid), dim3(MCX_BLOCK), 0, s, ac);
+    MCX_HIP(h, hipGetLastError());
+    MCX_HIP(h, hipStreamSynchronize(s));
+    return 0;
 }
 
 extern "C" int mcx_tangent_lsm(mcx_handle* h, const mcx_book* b, int32_t product, int32_t first_event, int32_t num_atom, int32_t x_atom,

@@ -28,7 +28,7 @@ _EXPORTS = [
     "mcx_value_poly_fit", "mcx_book_collapse_values", "mcx_book_value_poly_info", "mcx_rows_minmax",
     "mcx_storage_create", "mcx_storage_destroy", "mcx_storage_lsm_step", "mcx_storage_lsm_run", "mcx_storage_eval",
     "mcx_storage_lsm_step_batch", "mcx_storage_lsm_solve_batch", "mcx_storage_lsm_run_batch",
-    "mcx_tangent_storage_lsm_step", "mcx_tangent_storage_eval", "mcx_tangent_paths_s2f",
+    "mcx_tangent_storage_lsm_step", "mcx_tangent_storage_eval", "mcx_tangent_paths_s2f", "mcx_tangent_paths_heston",
     "mcx_reduce_vector", "mcx_reduce_profiles", "mcx_reduce_cva", "mcx_unsecured", "mcx_select_hist", "mcx_select_hist_dev", "mcx_select_narrow", "mcx_select_bracket", "mcx_select_hist_rows",
 ]
 
@@ -71,6 +71,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_book_set_payoff_tangents.argtypes = [vp, vp, vp, vp]
     lib.mcx_tangent_paths_s2f.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_tangent_paths_chol.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
+    lib.mcx_tangent_paths_heston.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp, vp]
     lib.mcx_sim_describe.argtypes = [C.c_void_p, C.c_void_p]
     lib.mcx_fused_num_records.argtypes = [C.c_void_p]
     lib.mcx_fused_is_straight_line.argtypes = [C.c_void_p]
@@ -461,6 +462,31 @@ class HipBackend:
             self.h, sim.ptr, _abi.ptr(a[0]), _abi.ptr(a[1]), _abi.ptr(a[2]), _abi.ptr(dchol) if dchol is not None else None, seed,
             path_offset, n_paths, paths.data_ptr(), dpaths.data_ptr(), n_paths if ld is None else ld,
             inject_z.data_ptr() if inject_z is not None else None, self._stream()), "mcx_tangent_paths_chol")
+        return paths, dpaths
+
+    def tangent_paths_heston(self, sim, dslot: np.ndarray, dinit: np.ndarray, daux: np.ndarray, dchol: np.ndarray | None, seed: int,
+                             path_offset: int, n_paths: int, inject_z=None, inject_u=None, out=None, ld: int | None = None):
+        """tangent_paths for a single Heston slot under EULER or QE (mcx_tangent_paths_heston): two normals and, under QE, one uniform
+        per sub-step.  dchol [n_chol][2][2][NP]: the tangent of chol([[1, rho], [rho, 1]]), read under EULER only (QE: may be None).
+        inject_z [n_steps][2][ld], inject_u [n_steps][ld].  out: (paths, dpaths) to write into instead of fresh tensors; ld: the
+        leading dimension of the tensors, injected draws included, when it is not n_paths"""
+        plan = sim.plan
+        NP = _abi.TANGENT_NP
+        paths, dpaths = out if out is not None else (self.empty(plan.n_dates, plan.n_state, n_paths),
+                                                     self.empty(NP, plan.n_dates, plan.n_state, n_paths))
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (dslot, dinit, daux)]
+        assert a[0].shape == (1, _abi.SLOT_NPARAM, NP) and a[1].shape == (2, NP) and a[2].shape == (plan.n_steps, 1, _abi.AUX, NP)
+        if dchol is not None:
+            dchol = np.ascontiguousarray(dchol, dtype=np.float64)
+            assert dchol.shape == (len(plan.chol), 2, 2, NP)
+        width = n_paths if ld is None else ld
+        for t, rows in ((inject_z, (plan.n_steps, 2)), (inject_u, (plan.n_steps,))):
+            assert t is None or (t.stride(-1) == 1 and tuple(t.shape[:-1]) == rows and _ld(t) == width and t.shape[-1] == n_paths)
+        self._check(self.lib.mcx_tangent_paths_heston(
+            self.h, sim.ptr, _abi.ptr(a[0]), _abi.ptr(a[1]), _abi.ptr(a[2]), _abi.ptr(dchol) if dchol is not None else None, seed,
+            path_offset, n_paths, paths.data_ptr(), dpaths.data_ptr(), width,
+            inject_z.data_ptr() if inject_z is not None else None, inject_u.data_ptr() if inject_u is not None else None,
+            self._stream()), "mcx_tangent_paths_heston")
         return paths, dpaths
 
     def tangent_lsm(self, book, product: int, first_event: int, num_atom: int, x_atom: int, shift: float, scale: float,

@@ -13,6 +13,8 @@ Sensitivities through the LSM regression (CVA / PV of stateless books under BS /
 `run_with_tangent_book` drives csrc/kt_book.hip (dual paths -> dual normal equations -> dual book -> dual CVA).  So do books under
 the ANALYTICAL scheme whose slots are Black-Scholes or Vasicek: there the Cholesky factor of the per-dt covariance depends on the
 parameters, the models give it in closed form (`Model._analytic_factor_entries`) and mcx_tangent_paths_chol carries its tangent.
+With `SimulationController.tangent_heston` a book under a single HestonModel (EULER or QE, no storage) whose metrics go through
+exposures or exercise takes the same pass on the dual paths of mcx_tangent_paths_heston (`heston_route`).
 
 Every other configuration (`run_with_bumps`): sensitivities through the LSM regression — CVA / EPE / PFE greeks, SURVEY §8f
 rank 1, reference test `tests/pytests/test_cva_large_netting_set_aad_vs_fd.py` — are computed by CENTRAL DIFFERENCES WITH
@@ -355,24 +357,36 @@ def no_tangent_form(e) -> bool:
 # The stages of run_with_tangent_book (DESIGN.md "Forward-mode book pass: the stages of the driver").  _BookPass: what every stage
 # of one differentiation reads; _Chunk: one group of <= TANGENT_NP parameters, their indices `sel` and their zero-padded descriptor
 # tangents; _Presim: the dual pre-simulation of a chunk and the coefficient images its regression fills; _Images: the main pass.
-_BookPass = namedtuple("_BookPass", "sc base be shard s2f chol batched rows base_coeffs dpayoff", defaults=(None,))   # dpayoff: tangent_payoffs only
+# dpayoff: tangent_payoffs only; heston: the book's dual paths come from mcx_tangent_paths_heston (heston_route)
+_BookPass = namedtuple("_BookPass", "sc base be shard s2f chol batched rows base_coeffs dpayoff heston", defaults=(None, False))
 _Chunk = namedtuple("_Chunk", "sel dslot dinit daux dchol datoms")
 _Presim = namedtuple("_Presim", "x_range paths dpaths n coeffs dcoeffs")
 _Images = namedtuple("_Images", "paths dpaths cfs expo")
 
 
+def heston_route(sc) -> bool:
+    """Host only: do the book's dual paths come from mcx_tangent_paths_heston (csrc/kt_book.hip kt_paths_heston)?  Only with
+    SimulationController.tangent_heston on a backend with the binding, for a single HestonModel (not a ModelConfig with a Heston
+    leaf) under EULER or QE, and a book without a storage.  Every other Heston book keeps the route it had."""
+    return bool(getattr(sc, "tangent_heston", False)) and hasattr(sc.backend, "tangent_paths_heston") \
+        and isinstance(sc.model, HestonModel) and sc.simulation_scheme.name in ("EULER", "QE") \
+        and not any(getattr(p, "is_storage", False) for p in sc.products)
+
+
 def _tangent_book_routes(sc):
     """Host only: every gate that holds before any GPU work, in the order their reasons are reported.  -> (s2f, chol, batched):
-    which dual path kernel serves the book, and whether the stateless products' regression is batched."""
+    which dual path kernel serves the book, and whether the stateless products' regression is batched.  (The Heston route is
+    heston_route: it only widens the scheme gate here.)"""
     if sc.requires_higher_order_derivatives:
         raise _NoTangentForm("second order")
     # Schwartz two-factor dual paths serve books that hold a storage; every other book keeps the route it had (no tangent form)
     s2f = hasattr(sc.model, "_cholesky_entries") and hasattr(sc.backend, "tangent_paths_s2f") \
+        and all(sp.kind == _abi.MODEL_S2F for sp in sc.model._slots()) \
         and any(getattr(p, "is_storage", False) for p in sc.products)
     # ANALYTICAL: the factor of the per-dt covariance depends on the parameters; mcx_tangent_paths_chol carries its tangent for
     # Black-Scholes and Vasicek slots whose models give it in closed form
     chol = not s2f and hasattr(sc.backend, "tangent_paths_chol") and _analytic_factor_form(sc.model, sc.simulation_scheme)
-    if sc.simulation_scheme.name != "EULER" and not (s2f and sc.simulation_scheme.name == "ANALYTICAL") and not chol:
+    if sc.simulation_scheme.name != "EULER" and not (s2f and sc.simulation_scheme.name == "ANALYTICAL") and not chol and not heston_route(sc):
         raise _NoTangentForm("scheme")
     if any(m.metric_type not in _SCATTER or not m._native for m in sc.risk_metrics.metrics):
         raise _NoTangentForm("metric")
@@ -486,7 +500,8 @@ def payoff_forms_armed(sc, be) -> bool:
     entry point — and no storage in the book: the payoff forms next to a storage's dual walk have not been compared with anything,
     so such a book keeps the library's refusal, and with it the NotImplementedError of storage books"""
     return bool(getattr(sc, "tangent_payoffs", False)) and hasattr(be, "book_set_payoff_tangents") \
-        and not any(getattr(p, "is_storage", False) for p in sc.products)
+        and not any(getattr(p, "is_storage", False) for p in sc.products) \
+        and not heston_route(sc)             # the payoff forms on Heston dual paths: not compared either
 
 
 def pad_chunk(a, sel):
@@ -496,14 +511,17 @@ def pad_chunk(a, sel):
 
 def _parameter_chunk(ctx, dd, sel):
     """the padded descriptor tangents of the parameters `sel`; the atoms' go to the device, the factors' only where a route reads them"""
-    dchol = pad_chunk(dd["chol"], sel) if ctx.s2f or ctx.chol else None
+    dchol = pad_chunk(dd["chol"], sel) if ctx.s2f or ctx.chol or ctx.heston else None
     return _Chunk(sel, pad_chunk(dd["slots"], sel), pad_chunk(dd["init"], sel), pad_chunk(dd["aux"], sel), dchol,
                   ctx.be.from_numpy(pad_chunk(dd["atoms"], sel)))
 
 
-def _dual_paths(ctx, chunk, seed, off, n, inject_z):
-    """GPU: (paths, dpaths) of n paths from path `off` on, through the dual path kernel of the book's route"""
+def _dual_paths(ctx, chunk, seed, off, n, inject_z, inject_u=None):
+    """GPU: (paths, dpaths) of n paths from path `off` on, through the dual path kernel of the book's route.  inject_u: the injected
+    uniforms of the same simulation (pre-simulation or main), which only the Heston QE step consumes"""
     be, sim, c = ctx.be, ctx.base._sim, chunk
+    if ctx.heston:
+        return be.tangent_paths_heston(sim, c.dslot, c.dinit, c.daux, c.dchol, seed, off, n, inject_z, inject_u)
     if ctx.s2f:
         return be.tangent_paths_s2f(sim, c.dslot, c.dinit, c.daux, c.dchol, seed, off, n, inject_z)
     if ctx.chol:
@@ -609,7 +627,7 @@ def _regress_chunk(ctx, chunk, plan):
     if not plan:
         return coeffs, dcoeffs, 0
     off, n_pre = ctx.shard.split(sc.num_paths_presim)
-    paths, dpaths = _dual_paths(ctx, chunk, 42 + sc.seed_offset, off, n_pre, sc._inject.get("pre", (None, None))[0])
+    paths, dpaths = _dual_paths(ctx, chunk, 42 + sc.seed_offset, off, n_pre, *sc._inject.get("pre", (None, None)))
     if ctx.dpayoff is not None:               # the bridge uniforms of the pre-simulation's paths (controller._perform_regression)
         base._set_bridge_rng(42 + sc.seed_offset, off, "bridge_pre")
     pre = _Presim(base._explanatory_ranges(ctx.shard, plan, paths), paths, dpaths, n_pre, coeffs, dcoeffs)
@@ -646,7 +664,7 @@ def _main_dual_pass(ctx, chunk, coeffs, dcoeffs):
     """GPU: dual main simulation and dual book of one chunk -> _Images (cashflow and exposure images [1 + NP][...])"""
     sc, base, be = ctx.sc, ctx.base, ctx.be
     off, n_main = ctx.shard.split(sc.num_paths_mainsim)
-    paths, dpaths = _dual_paths(ctx, chunk, 43 + sc.seed_offset, off, n_main, sc._inject.get("main", (None, None))[0])
+    paths, dpaths = _dual_paths(ctx, chunk, 43 + sc.seed_offset, off, n_main, *sc._inject.get("main", (None, None)))
     if ctx.dpayoff is not None:               # back to the main simulation's bridge uniforms: the seed and path range of these paths
         base._set_bridge_rng(43 + sc.seed_offset, off, "bridge_main")
     ev_param = _bs_exposure_slots(base, sc, chunk.sel)
@@ -751,7 +769,7 @@ def run_with_tangent_book(sc):
     dpayoff = None
     if payoff_forms_armed(sc, be):
         dpayoff = payoff_tangents(base, sc.model, getattr(sc.model, "perform_smoothing", False))
-    ctx = _BookPass(sc, base, be, shard, s2f, chol, batched, rows, base_coeffs, dpayoff)
+    ctx = _BookPass(sc, base, be, shard, s2f, chol, batched, rows, base_coeffs, dpayoff, heston_route(sc))
     n_batched = 0
     try:
         for c0 in range(0, P, NP):

@@ -168,6 +168,10 @@ class SimulationController:
         # (mcx_book_set_payoff_tangents, mcx/aad.py payoff_tangents); False: a book that holds one keeps bump-and-revalue.  A book
         # that also holds a storage is never armed and stays refused (aad.payoff_forms_armed)
         self.tangent_payoffs = False
+        # differentiate=True: True sends a book under a single HestonModel (EULER or QE, no storage) whose sensitivities go through
+        # exposures or exercise through the forward-mode book pass on mcx_tangent_paths_heston (mcx/aad.py heston_route); False: such
+        # a book keeps bump-and-revalue.  European PV books go to the fused tangent kernel either way
+        self.tangent_heston = False
         # The reference compiles nothing: every run_simulation() sees the current state of its products / metrics.  Re-using the
         # compiled descriptors and the uploaded book of the previous run is an opt-in for callers that re-run an UNCHANGED
         # controller (bench.py, tools/run_configs.py); invalidate() drops the cache after a mutation.

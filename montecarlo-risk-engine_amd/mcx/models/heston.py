@@ -3,8 +3,6 @@ params (gradient order) = [spot, volatility(vol-of-vol), rate, rho, kappa, theta
 state = [log S, v]; two normals (+ one uniform under QE) per sub-step."""
 from __future__ import annotations
 
-import math
-
 import torch
 
 from .. import _abi
@@ -12,7 +10,7 @@ from ..common.enums import SimulationScheme
 from ..common.packages import FLOAT, device
 from ..request_interface.request_types import AtomicRequestType as RT
 from .black_scholes import deterministic_rate_atom
-from .model import AtomCoef, Model, SlotSpec
+from .model import AtomCoef, Model, SlotSpec, cexp, clog, csqrt
 
 
 class HestonModel(Model):
@@ -53,12 +51,21 @@ class HestonModel(Model):
         rho = self._pf(3)
         return torch.tensor([[1.0, rho], [rho, 1.0]], dtype=FLOAT, device=device)
 
+    def _cholesky_entries(self, scheme, delta_t):
+        """the factor of the correlation matrix in closed form: [[1, 0], [rho, sqrt(1 - rho^2)]] under EULER, the identity under QE
+        (independent draws).  Complex-safe: rho is a model parameter, so under EULER the factor carries a tangent (mcx/aad.py;
+        csrc/kt_book.hip kt_paths_heston) — the reference's tape differentiates through torch.linalg.cholesky."""
+        if scheme == SimulationScheme.QE:
+            return [[1.0, 0.0], [0.0, 1.0]]
+        rho = self._pf(3)
+        return [[1.0, 0.0], [rho, csqrt(1.0 - rho * rho)]]
+
     def _slots(self):
         flags = _abi.FLAG_SMOOTHING if self.perform_smoothing else 0
         return [SlotSpec(_abi.MODEL_HESTON, [self._pf(i) for i in range(7)], 2, 2, flags)]
 
     def _initial_state(self):
-        return [math.log(self._pf(0)), self._pf(6)]
+        return [clog(self._pf(0)), self._pf(6)]
 
     def _n_uniform(self, scheme):
         return 1 if scheme == SimulationScheme.QE else 0
@@ -67,7 +74,7 @@ class HestonModel(Model):
         if scheme != SimulationScheme.QE:
             return [[]]
         sigma, rho, kappa, theta = self._pf(1), self._pf(3), self._pf(4), self._pf(5)
-        E = math.exp(-kappa * dt)
+        E = cexp(-kappa * dt)
         g1, g2 = 1.0, 0.0                                            # heston.py:151-152
         K0 = -rho * kappa * theta / sigma * dt
         K1 = (kappa * rho / sigma - 0.5) * g1 * dt - rho / sigma

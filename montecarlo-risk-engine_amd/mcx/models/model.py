@@ -31,6 +31,10 @@ def csqrt(x):
     return cmath.sqrt(x) if isinstance(x, complex) else math.sqrt(x)
 
 
+def clog(x):
+    return cmath.log(x) if isinstance(x, complex) else math.log(x)
+
+
 def scaled_correlation_factor(owner, vols, correlation: torch.Tensor, delta_t: float):
     """the lower factor of the covariance S rho S dt of n Black-Scholes assets in closed form: sigma_i sqrt(dt) (L_rho)_ij, with L_rho
     the factor of the correlation matrix — real and parameter-free, computed once and kept on `owner`.  `vols` may be complex
