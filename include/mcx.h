@@ -602,6 +602,33 @@ int  mcx_lsm_run_batch(mcx_handle* h, mcx_book* book, const mcx_lsm_job* h_jobs,
                        const int32_t* h_step_begin, const int32_t* h_step_states, int32_t n_steps,
                        const double* d_paths, int64_t n_paths, int64_t ld, double* d_W, int64_t ld_w, int64_t w_len,
                        int32_t* h_flag, int32_t flags, void* stream);
+/* Date-batched LSM for the products WITHOUT exercise rights (n_states == 1): their roll reads no regression coefficient, so once
+ * the cache is rolled in order the systems of all dates are independent, and one launch forms the moments of every (product, date)
+ * pair of a book.  h_jobs holds the mcx_lsm_job records in CHAIN-major order: a chain is the run of consecutive jobs of one product
+ * in the order the induction walks them (schedule order); all jobs of a chain share `product` and `w_offset` (one private [ld_w]
+ * cache row per chain), and chain c is h_jobs[h_chain_begin[c] .. h_chain_begin[c+1]) — h_chain_begin [n_chains + 1] ascends from 0
+ * to n_jobs.  Each block walks the dates of its chain over a fixed set of paths, so no block waits for another.
+ * The moments of job j are, bit for bit, those mcx_lsm_step_batch returns for that job when the steps are issued in schedule order
+ * on the same cache (same tiling: one block per 256 paths, at most 64; same summation order), and the cache ends up the same.
+ *   mcx_lsm_dates_moments  d_moments [n_jobs][NM], NM = (2K-1) + K, on the device, stream-ordered, no synchronisation (the caller
+ *                          all-reduces them once and solves with mcx_lsm_solve_batch).  n_paths == 0 writes zeros without a launch.
+ *   mcx_lsm_dates_run      the same plus the solves of h_solve [n_jobs] and the coefficient scatter, one synchronisation at the end:
+ *                          without a communicator the moment launch and one finish + solve launch; with a communicator of several
+ *                          ranks (mcx_comm_init) the moments of ALL jobs are all-reduced in ONE collective before the solves.
+ *                          *h_flag != 0: some system was numerically singular (its coefficients were not written), as mcx_lsm_run_batch.
+ * Both check everything before the first launch and refuse with -2: every index of a job that mcx_lsm_step_batch checks, a product
+ * with n_states != 1, a chain whose jobs differ in product or w_offset, a chain table that does not start at 0, does not ascend or
+ * does not end at n_jobs, ld or ld_w below n_paths, a coefficient offset outside the book.  -3: MCX_LSM_MFMA in flags (there is no
+ * MFMA form) or an unsupported basis size.  MCX_LSM_F32_CACHE is honoured.  A table is split over whole chains into launches of at
+ * most 65,535 chains and 64 MiB of per-block partial sums (the results do not depend on the split); MCX_LSM_DATES_MAX_CHAINS(n) in
+ * flags lowers the chain limit of a launch to n (1 <= n < 32768: tests, tuning). */
+#define MCX_LSM_DATES_MAX_CHAINS(n) ((int32_t)(n) << 16)
+int  mcx_lsm_dates_moments(mcx_handle* h, const mcx_book* book, const mcx_lsm_job* h_jobs, int32_t n_jobs, const int32_t* h_chain_begin,
+                           int32_t n_chains, const double* d_paths, int64_t n_paths, int64_t ld, double* d_W, int64_t ld_w,
+                           int64_t w_len, double* d_moments, int32_t flags, void* stream);
+int  mcx_lsm_dates_run(mcx_handle* h, mcx_book* book, const mcx_lsm_job* h_jobs, const mcx_lsm_solve_job* h_solve, int32_t n_jobs,
+                       const int32_t* h_chain_begin, int32_t n_chains, const double* d_paths, int64_t n_paths, int64_t ld,
+                       double* d_W, int64_t ld_w, int64_t w_len, int32_t* h_flag, int32_t flags, void* stream);
 int  mcx_book_get_coeffs(mcx_handle* h, const mcx_book* book, int64_t offset, int64_t count, double* h_out, void* stream);
 /* coeffs[h_offsets[j] + q] = h_values[j * len + q], q < len, for n blocks in one call (the batched form of mcx_book_set_coeffs) */
 int  mcx_book_set_coeffs_batch(mcx_handle* h, mcx_book* book, const int64_t* h_offsets, int32_t n, int32_t len,

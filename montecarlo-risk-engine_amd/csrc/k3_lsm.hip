@@ -314,6 +314,49 @@ __global__ void k3_finish_batch(const double* __restrict__ partials, int nm, int
     out[(int64_t)job * ld_out + q] = s;
 }
 
+// ---- date-batched step (products without exercise rights) ------------------------------------------------------------------
+// For S = 1 the roll reads no regression coefficient, so the systems of all dates of a product are independent once the cache has
+// been rolled in order.  A CHAIN is the run of consecutive jobs of one product in schedule order (they share w_off); block
+// (bx, c) walks the jobs of chain chain0 + c in order and forms, for every job, the partial k3_step_batch<K, 1> writes for that job
+// at gridDim.x = blocks_per_chain: the same paths per lane in the same order (the grid-stride loop below), the same shuffle
+// reduction and the same order of the four wave rows.  Path i is rolled by the same thread at every date (W stays in global
+// memory as k3_roll uses it, program order within the thread), so the blocks of a chain never wait for each other.
+// k3_block_reduce holds ONE row buffer and one barrier (one use per kernel); here the rows alternate between two buffers: date
+// d + 2 writes the rows of date d only after the barrier of date d + 1, which thread q reaches after it has summed those of date d.
+// partials: [job - job0][blocks_per_chain][NM], job0 = the first job of the launch.
+template <int K>
+__global__ __launch_bounds__(MCX_BLOCK) void k3_dates(const K3Args a_in, const K3Job* __restrict__ jobs, const int32_t* __restrict__ chain_begin,
+                                                      int chain0, int job0, int blocks_per_chain)
+{
+    constexpr int NM = (2 * K - 1) + K;
+    __shared__ double etab[MCX_EXP_LDS_DOUBLES];
+    __shared__ double rows[2][4][NM];
+    mcx_exp_tab_load(etab);
+    __syncthreads();
+    const int lane = threadIdx.x & (MCX_WAVE - 1), wv = threadIdx.x >> 6;
+    const int j_begin = ldk(chain_begin + chain0 + blockIdx.y), j_end = ldk(chain_begin + chain0 + blockIdx.y + 1);
+    for (int j = j_begin; j < j_end; ++j) {
+        K3Args a = a_in;
+        a.etab = etab;
+        const K3Job jb = ldk_struct(&jobs[j]);
+        a.events += jb.ev_off; a.ev_base = jb.ev_off; a.roll_begin = jb.roll_begin; a.roll_end = jb.roll_end; a.W += jb.w_off;
+        a.shift = jb.shift; a.scale = jb.scale; a.num = jb.num; a.x = jb.x;
+        double acc[NM];
+#pragma unroll
+        for (int q = 0; q < NM; ++q) acc[q] = 0.0;
+        for (int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * MCX_BLOCK) k3_accumulate<K, 1>(a, i, acc);
+        double (&buf)[4][NM] = rows[(j - j_begin) & 1];
+#pragma unroll
+        for (int q = 0; q < NM; ++q) {
+            const double r = wave_sum(acc[q]);
+            if (lane == 0) buf[wv][q] = r;
+        }
+        __syncthreads();
+        double* __restrict__ dst = a.partials + ((int64_t)(j - job0) * blocks_per_chain + blockIdx.x) * NM;
+        if (threadIdx.x < NM) dst[threadIdx.x] = (buf[0][threadIdx.x] + buf[1][threadIdx.x]) + (buf[2][threadIdx.x] + buf[3][threadIdx.x]);
+    }
+}
+
 __global__ void k3_scatter_coeffs(const int64_t* __restrict__ offsets, const double* __restrict__ values, int len, double* __restrict__ coeffs)
 {
     const int j = blockIdx.x;
@@ -471,6 +514,14 @@ int k3_launch_batch(int K, int S, const K3Args& a, const K3Job* d_jobs, dim3 gri
 {
     int rc = -1;
     K3_DISPATCH(K, S, hipLaunchKernelGGL((k3_step_batch<KK, SS>), grid, dim3(MCX_BLOCK), 0, s, a, d_jobs, (int)grid.x); rc = 0);
+    return rc;
+}
+
+// one date-batched moment launch: grid (blocks per chain, chains [chain0, chain0 + grid.y)).  -1: no instantiation for K
+int k3_launch_dates(int K, const K3Args& a, const K3Job* d_jobs, const int32_t* d_chain_begin, int chain0, int job0, dim3 grid, hipStream_t s)
+{
+    int rc = -1;
+    MCX_DISPATCH(KK, K, 6, hipLaunchKernelGGL((k3_dates<KK>), grid, dim3(MCX_BLOCK), 0, s, a, d_jobs, d_chain_begin, chain0, job0, (int)grid.x); rc = 0);
     return rc;
 }
 
@@ -861,6 +912,155 @@ extern "C" int mcx_lsm_run_batch(mcx_handle* h, mcx_book* b, const mcx_lsm_job* 
     if (rc == 0 && hipMemcpyAsync(h_flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess) rc = -100;
     if (hipStreamSynchronize(s) != hipSuccess && rc == 0) rc = -100;
     if (rc != 0) { if (rc == -100) h->err = "mcx_lsm_run_batch: HIP error"; return rc; }
+    return 0;
+}
+
+// ---- date-batched induction of the products without exercise rights (k3_dates) ---------------------------------------------------
+namespace {
+// the partial buffer [jobs of a launch][blocks_per_chain][NM] of a date-batched launch never exceeds this; a table that needs more
+// goes in several launches over whole chains (chains are independent: the launches need no order among themselves)
+constexpr size_t K3_DATES_PART_CAP = (size_t)64 << 20;
+constexpr int K3_DATES_MAX_CHAINS = 65535;         // gridDim.y
+
+struct K3DatesPlan {
+    std::vector<K3Job> jobs;
+    std::vector<int32_t> launch;                   // first chain of every launch, then n_chains
+    int K = 0, NM = 0, bpc = 1;
+    size_t part_bytes = 0;                         // of the widest launch
+};
+
+// everything a date-batched call dereferences, checked on the host before the first launch; the device records and the launches
+int k3_dates_plan(mcx_handle* h, const mcx_book* b, const mcx_lsm_job* h_jobs, int32_t n_jobs, const int32_t* h_chain_begin, int32_t n_chains,
+                  int64_t n_paths, int64_t ld, int64_t ld_w, int64_t w_len, int32_t flags, const char* who, K3DatesPlan& p)
+{
+    p.K = b->n_basis; p.NM = (2 * p.K - 1) + p.K;
+    if (flags & MCX_LSM_MFMA) MCX_FAIL(h, -3, "%s: no MFMA form of the date-batched step", who);
+    if (p.K < 1 || p.K > 6) MCX_FAIL(h, -3, "%s: unsupported basis size %d", who, p.K);
+    if (ld < n_paths || ld_w < n_paths) MCX_FAIL(h, -2, "%s: leading dimension < n_paths", who);
+    if (n_chains < 1 || h_chain_begin[0] != 0) MCX_FAIL(h, -2, "%s: chain table must start at job 0", who);
+    for (int c = 0; c < n_chains; ++c)
+        if (h_chain_begin[c + 1] < h_chain_begin[c]) MCX_FAIL(h, -2, "%s: chain table not ascending at chain %d", who, c);
+    if (h_chain_begin[n_chains] != n_jobs) MCX_FAIL(h, -2, "%s: chain table must end at n_jobs", who);
+    p.jobs.resize((size_t)n_jobs);
+    for (int c = 0; c < n_chains; ++c)
+        for (int j = h_chain_begin[c]; j < h_chain_begin[c + 1]; ++j) {
+            if (int rc = k3_check_job(h, b, h_jobs[j], j, 1, ld_w, w_len, who, p.jobs[j])) return rc;
+            const mcx_lsm_job& first = h_jobs[h_chain_begin[c]];
+            if (h_jobs[j].product != first.product || h_jobs[j].w_offset != first.w_offset)
+                MCX_FAIL(h, -2, "%s: job %d differs from its chain %d in product or w_offset", who, j, c);
+        }
+    p.bpc = n_paths > 0 ? mcx_grid_for(n_paths, MCX_BLOCK, 64) : 1;       // the batched route's rule (bit-equal partials)
+    const size_t job_bytes = sizeof(double) * (size_t)p.bpc * p.NM;
+    const int64_t cap_jobs = (int64_t)(K3_DATES_PART_CAP / job_bytes);
+    const int hook = (flags >> 16) & 0x7FFF;                               // MCX_LSM_DATES_MAX_CHAINS(n)
+    const int cap_chains = hook > 0 && hook < K3_DATES_MAX_CHAINS ? hook : K3_DATES_MAX_CHAINS;
+    int64_t cur_jobs = 0, widest = 0;
+    int cur_chains = 0;
+    p.launch.assign(1, 0);
+    for (int c = 0; c < n_chains; ++c) {
+        const int64_t len = h_chain_begin[c + 1] - h_chain_begin[c];
+        if (len > cap_jobs) MCX_FAIL(h, -2, "%s: chain %d of %lld jobs exceeds the partial buffer of one launch", who, c, (long long)len);
+        if (cur_chains == cap_chains || cur_jobs + len > cap_jobs) { p.launch.push_back(c); cur_jobs = 0; cur_chains = 0; }
+        cur_jobs += len; cur_chains += 1;
+        if (cur_jobs > widest) widest = cur_jobs;
+    }
+    p.launch.push_back(n_chains);
+    p.part_bytes = job_bytes * (size_t)(widest > 0 ? widest : 1);
+    return 0;
+}
+
+// the launches of a plan on the stream: per launch k3_dates, then either k3_finish_batch into d_mom [n_jobs][NM] (d_solves == nullptr)
+// or k3_finish_solve_batch.  d_jobs / d_chain_begin: the uploaded tables, d_part: >= p.part_bytes
+int k3_dates_enqueue(const K3DatesPlan& p, K3Args a, const int32_t* h_chain_begin, const K3Job* d_jobs, const int32_t* d_chain_begin,
+                     double* d_part, double* d_mom, const K3Solve* d_solves, double* d_coeffs, int32_t* d_flag, hipStream_t s)
+{
+    a.partials = d_part;
+    for (size_t l = 0; l + 1 < p.launch.size(); ++l) {
+        const int c0 = p.launch[l], nc = p.launch[l + 1] - c0;
+        const int j0 = h_chain_begin[c0], nj = h_chain_begin[c0 + nc] - j0;
+        if (nj <= 0) continue;
+        if (int rc = k3_launch_dates(p.K, a, d_jobs, d_chain_begin, c0, j0, dim3(p.bpc, nc), s)) return rc;
+        if (d_solves) hipLaunchKernelGGL(k3_finish_solve_batch, dim3((nj + 63) / 64), dim3(64), 0, s, d_part, p.bpc, d_solves + j0, nj, p.K, 1, d_coeffs, d_flag);
+        else hipLaunchKernelGGL(k3_finish_batch, dim3(nj), dim3(64), 0, s, d_part, p.NM, p.bpc, d_mom + (size_t)j0 * p.NM, p.NM);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -100;
+}
+}  // namespace
+
+extern "C" int mcx_lsm_dates_moments(mcx_handle* h, const mcx_book* b, const mcx_lsm_job* h_jobs, int32_t n_jobs, const int32_t* h_chain_begin,
+                                     int32_t n_chains, const double* d_paths, int64_t n_paths, int64_t ld, double* d_W, int64_t ld_w,
+                                     int64_t w_len, double* d_moments, int32_t flags, void* stream)
+{
+    const char* who = "mcx_lsm_dates_moments";
+    if (!h || !b || !h_jobs || !h_chain_begin || !d_paths || !d_W || !d_moments) return -1;
+    if (n_jobs <= 0) return 0;
+    K3DatesPlan p;
+    if (int rc = k3_dates_plan(h, b, h_jobs, n_jobs, h_chain_begin, n_chains, n_paths, ld, ld_w, w_len, flags, who, p)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (n_paths <= 0) { MCX_HIP(h, hipMemsetAsync(d_moments, 0, sizeof(double) * (size_t)n_jobs * p.NM, s)); return 0; }
+    K3Args a;
+    if (int rc = k3_fill_args(h, b, d_paths, n_paths, ld, d_W, ld_w, flags, who, a)) return rc;
+    // [jobs | chain table] in one upload that outlives the call (the ring, or scratch slot 1 completed before returning)
+    const size_t job_bytes = sizeof(K3Job) * (size_t)n_jobs, chain_bytes = sizeof(int32_t) * ((size_t)n_chains + 1);
+    std::vector<unsigned char> tab(job_bytes + chain_bytes);
+    memcpy(tab.data(), p.jobs.data(), job_bytes);
+    memcpy(tab.data() + job_bytes, h_chain_begin, chain_bytes);
+    double* d_part = (double*)mcx_scratch(h, 2, p.part_bytes);
+    if (!d_part) return -100;
+    const unsigned char* d_tab = (const unsigned char*)mcx_upload_table(h, 1, tab.data(), tab.size(), s);
+    if (!d_tab) return -100;
+    const int rc = k3_dates_enqueue(p, a, h_chain_begin, (const K3Job*)d_tab, (const int32_t*)(d_tab + job_bytes), d_part, d_moments, nullptr,
+                                    nullptr, nullptr, s);
+    if (rc != 0) MCX_FAIL(h, -100, "%s: HIP error: %s", who, hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+extern "C" int mcx_lsm_dates_run(mcx_handle* h, mcx_book* b, const mcx_lsm_job* h_jobs, const mcx_lsm_solve_job* h_solve, int32_t n_jobs,
+                                 const int32_t* h_chain_begin, int32_t n_chains, const double* d_paths, int64_t n_paths, int64_t ld,
+                                 double* d_W, int64_t ld_w, int64_t w_len, int32_t* h_flag, int32_t flags, void* stream)
+{
+    const char* who = "mcx_lsm_dates_run";
+    if (!h || !b || !h_jobs || !h_solve || !h_chain_begin || !d_paths || !d_W || !h_flag) return -1;
+    *h_flag = 0;
+    if (n_jobs <= 0) return 0;
+    K3DatesPlan p;
+    if (int rc = k3_dates_plan(h, b, h_jobs, n_jobs, h_chain_begin, n_chains, n_paths, ld, ld_w, w_len, flags, who, p)) return rc;
+    std::vector<K3Solve> solves((size_t)n_jobs);
+    for (int j = 0; j < n_jobs; ++j)
+        if (int rc = k3_fill_solve(h, b, h_solve[j], 1, who, "job", j, solves[j])) return rc;
+    K3Args a;
+    if (int rc = k3_fill_args(h, b, d_paths, n_paths, ld, d_W, ld_w, flags, who, a)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const bool multi = h->comm && h->comm_ranks > 1;
+    const bool apart = multi || n_paths <= 0;          // moments in a block of their own: all-reduced once, or zero without a launch
+    const size_t n_mom = apart ? (size_t)n_jobs * p.NM : 0;
+    const size_t job_bytes = sizeof(K3Job) * (size_t)n_jobs, solve_bytes = sizeof(K3Solve) * (size_t)n_jobs,
+                 chain_bytes = sizeof(int32_t) * ((size_t)n_chains + 1);
+    unsigned char* d_tab = (unsigned char*)mcx_scratch(h, 1, job_bytes + solve_bytes + chain_bytes);
+    double* d_part = (double*)mcx_scratch(h, 2, p.part_bytes);
+    double* d_mom = (double*)mcx_scratch(h, 3, sizeof(double) * (n_mom + 1));
+    if (!d_tab || !d_part || !d_mom) return -100;
+    int32_t* d_flag = (int32_t*)(d_mom + n_mom);
+    // the tables in one device buffer, copied before the first launch (the call synchronises before the host vectors die)
+    MCX_HIP(h, hipMemcpyAsync(d_tab, p.jobs.data(), job_bytes, hipMemcpyHostToDevice, s));
+    MCX_HIP(h, hipMemcpyAsync(d_tab + job_bytes, solves.data(), solve_bytes, hipMemcpyHostToDevice, s));
+    MCX_HIP(h, hipMemcpyAsync(d_tab + job_bytes + solve_bytes, h_chain_begin, chain_bytes, hipMemcpyHostToDevice, s));
+    MCX_HIP(h, hipMemsetAsync(d_flag, 0, sizeof(int32_t), s));
+    const K3Job* d_jobs = (const K3Job*)d_tab;
+    const K3Solve* d_solves = (const K3Solve*)(d_tab + job_bytes);
+    const int32_t* d_chain_begin = (const int32_t*)(d_tab + job_bytes + solve_bytes);
+    int rc = 0;
+    if (n_paths <= 0) {                                 // a rank without paths still takes part in the all-reduce
+        if (hipMemsetAsync(d_mom, 0, sizeof(double) * n_mom, s) != hipSuccess) rc = -100;
+    } else rc = k3_dates_enqueue(p, a, h_chain_begin, d_jobs, d_chain_begin, d_part, d_mom, apart ? nullptr : d_solves, b->d_coeffs, d_flag, s);
+    if (rc == 0 && multi) rc = mcx_allreduce_f64(h, d_mom, (int64_t)n_mom, stream);               // ONE collective, stream-ordered
+    if (rc == 0 && apart) {
+        hipLaunchKernelGGL(k3_solve_batch, dim3((n_jobs + 63) / 64), dim3(64), 0, s, d_mom, d_solves, n_jobs, p.K, 1, b->d_coeffs, d_flag);
+        if (hipGetLastError() != hipSuccess) rc = -100;
+    }
+    if (rc == 0 && hipMemcpyAsync(h_flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess) rc = -100;
+    if (hipStreamSynchronize(s) != hipSuccess && rc == 0) rc = -100;
+    if (rc != 0) { if (rc == -100 || rc == -1) h->err = "mcx_lsm_dates_run: HIP error"; return rc; }
     return 0;
 }
 

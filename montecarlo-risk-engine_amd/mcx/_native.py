@@ -22,7 +22,7 @@ _EXPORTS = [
     "mcx_sim_create", "mcx_sim_destroy", "mcx_generate_paths", "mcx_generate_paths_from_state", "mcx_sim_describe", "mcx_rng_draws",
     "mcx_comm_unique_id", "mcx_comm_init", "mcx_comm_destroy", "mcx_allreduce_f64", "mcx_allgather_f64",
     "mcx_book_create", "mcx_book_destroy", "mcx_book_set_coeffs", "mcx_eval_book", "mcx_eval_book_describe", "mcx_resolve_atoms",
-    "mcx_lsm_stats", "mcx_lsm_step", "mcx_lsm_run", "mcx_lsm_solve", "mcx_lsm_step_batch", "mcx_lsm_step_batch_dev", "mcx_lsm_solve_batch", "mcx_lsm_run_batch", "mcx_book_get_coeffs", "mcx_book_set_coeffs_batch", "mcx_book_set_bridge_rng", "mcx_book_set_exercise_replay", "mcx_book_set_payoff_tangents",
+    "mcx_lsm_stats", "mcx_lsm_step", "mcx_lsm_run", "mcx_lsm_solve", "mcx_lsm_step_batch", "mcx_lsm_step_batch_dev", "mcx_lsm_solve_batch", "mcx_lsm_run_batch", "mcx_lsm_dates_moments", "mcx_lsm_dates_run", "mcx_book_get_coeffs", "mcx_book_set_coeffs_batch", "mcx_book_set_bridge_rng", "mcx_book_set_exercise_replay", "mcx_book_set_payoff_tangents",
     "mcx_fused_is_straight_line", "mcx_tangent_paths", "mcx_tangent_paths_chol", "mcx_tangent_lsm", "mcx_tangent_lsm_batch", "mcx_tangent_lsm_step", "mcx_tangent_eval", "mcx_tangent_cva", "mcx_tangent_profiles", "mcx_tangent_pick",
     "mcx_box_muller", "mcx_tangent_european", "mcx_fused_create", "mcx_fused_destroy", "mcx_fused_num_records", "mcx_fused_run", "mcx_fused_eval_paths", "mcx_fused_run_device", "mcx_fused_eval_paths_device", "mcx_fused_set_timing", "mcx_fused_kernel_times", "mcx_fused_describe",
     "mcx_value_poly_fit", "mcx_book_collapse_values", "mcx_book_value_poly_info", "mcx_rows_minmax",
@@ -68,6 +68,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_tangent_storage_lsm_step.argtypes = [vp, vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp, i32, vp]
     lib.mcx_tangent_storage_eval.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64, i32, vp, vp, i64, vp]
     lib.mcx_tangent_lsm_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, i64, i64, i32, vp, vp]
+    lib.mcx_lsm_dates_moments.argtypes = [vp, vp, vp, i32, vp, i32, vp, i64, i64, vp, i64, i64, vp, i32, vp]
+    lib.mcx_lsm_dates_run.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, i64, i64, vp, i64, i64, vp, i32, vp]
     lib.mcx_book_set_payoff_tangents.argtypes = [vp, vp, vp, vp]
     lib.mcx_tangent_paths_s2f.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_tangent_paths_chol.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
@@ -106,6 +108,29 @@ def padded_ld(n_paths: int) -> int:
     pass — on the same HBM channel and bank for a given path: measured 0.410 ms at ld = 2^20 against 0.351 ms at 2^20 + 512 for the
     same 2^20-path pass (tools/gpu_r3w.sh).  512 doubles (4 KiB) are added whenever the stride is a multiple of 32 KiB."""
     return n_paths + 512 if n_paths >= 16384 and n_paths % 4096 == 0 else n_paths
+
+
+class EmptyPaths:
+    """[n_dates][n_state][0] paths with a valid device pointer: the share of a rank that received no path (2 pre-simulation paths
+    on 3 ranks).  Such a rank still takes part in every collective with zero moments, and the library looks at the pointer before
+    it looks at the path count, but an empty torch tensor has no data pointer: this is the buffer of a one-path tensor, narrowed."""
+
+    is_cuda = True
+
+    def __init__(self, t: torch.Tensor):
+        self.t, self.shape, self.device = t, (t.shape[0], t.shape[1], 0), t.device
+
+    def data_ptr(self) -> int:
+        return self.t.data_ptr()
+
+    def stride(self, k=None):
+        return self.t.stride() if k is None else self.t.stride(k)
+
+    def dim(self) -> int:
+        return 3
+
+    def cpu(self):
+        return self.t.cpu()[..., :0]
 
 
 class HipBackend:
@@ -188,6 +213,8 @@ class HipBackend:
                        out: torch.Tensor | None = None, init_state: torch.Tensor | None = None) -> torch.Tensor:
         """init_state [n_state][n_paths]: start every path from its own state (mcx_generate_paths_from_state)"""
         plan = sim.plan
+        if out is None and n_paths == 0:
+            return EmptyPaths(self.zeros(plan.n_dates, plan.n_state, 1))
         if out is None:
             # (the library reads injected draws / start states with the leading dimension of the paths: those runs stay unpadded)
             pad = inject_z is None and inject_u is None and init_state is None
@@ -601,7 +628,7 @@ class HipBackend:
     def rows_minmax(self, x: torch.Tensor) -> np.ndarray:
         """[rows][2] (min, max) of every row of a 2-D view of `x` (last dimension = paths)"""
         n = x.shape[-1]
-        rows = x.numel() // n
+        rows = int(np.prod(x.shape[:-1]))
         ld = _ld(x)
         out = np.zeros((rows, 2))
         self._check(self.lib.mcx_rows_minmax(self.h, _vp(x.data_ptr()), C.c_int32(rows), C.c_int64(n), C.c_int64(ld), _abi.ptr(out), self._stream()),
@@ -711,6 +738,43 @@ class HipBackend:
             self.h, book.ptr, _abi.ptr(jobs), _abi.ptr(sj), _abi.ptr(sb), _abi.ptr(ss), C.c_int32(len(ss)), _vp(paths.data_ptr()),
             C.c_int64(n), C.c_int64(_ld(paths)), _vp(W.data_ptr()), C.c_int64(ld_w), C.c_int64(W.numel()), C.byref(flag), C.c_int32(int(flags)),
             self._stream()), "mcx_lsm_run_batch")
+        return int(flag.value)
+
+    @staticmethod
+    def _dates_tables(jobs, chain_begin, flags: int, max_chains: int):
+        jobs = np.ascontiguousarray(jobs, dtype=_abi.LSM_JOB_DTYPE)
+        cb = np.ascontiguousarray(chain_begin, dtype=np.int32)
+        assert cb.ndim == 1 and len(cb) >= 1 and 0 <= int(max_chains) < 32768
+        return jobs, cb, int(flags) | (int(max_chains) << 16)
+
+    def lsm_dates_moments(self, book, jobs: np.ndarray, chain_begin: np.ndarray, paths: torch.Tensor, W: torch.Tensor, ld_w: int,
+                          flags: int = 0, max_chains: int = 0) -> torch.Tensor:
+        """moments of every (stateless product, date) system of a chain-major job table in one launch (mcx_lsm_dates_moments): chain c
+        = jobs[chain_begin[c]:chain_begin[c+1]], one product and one [ld_w] cache row of W per chain -> [n_jobs][NM] device tensor,
+        stream-ordered.  max_chains: at most that many chains per launch (0: the library's limits; the result does not depend on it)"""
+        jobs, cb, flags = self._dates_tables(jobs, chain_begin, flags, max_chains)
+        n = paths.shape[2]
+        K = book.plan.n_basis
+        out = self.empty(len(jobs), (2 * K - 1) + K)
+        self._check(self.lib.mcx_lsm_dates_moments(
+            self.h, book.ptr, _abi.ptr(jobs), C.c_int32(len(jobs)), _abi.ptr(cb), C.c_int32(len(cb) - 1), _vp(paths.data_ptr()), C.c_int64(n),
+            C.c_int64(_ld(paths)), _vp(W.data_ptr()), C.c_int64(ld_w), C.c_int64(W.numel()), _vp(out.data_ptr()), C.c_int32(flags),
+            self._stream()), "mcx_lsm_dates_moments")
+        return out
+
+    def lsm_dates_run(self, book, jobs: np.ndarray, solve_jobs: np.ndarray, chain_begin: np.ndarray, paths: torch.Tensor, W: torch.Tensor,
+                      ld_w: int, flags: int = 0, max_chains: int = 0) -> int:
+        """the whole induction of the stateless products in one call (mcx_lsm_dates_run): the moments of lsm_dates_moments, one
+        all-reduce under a communicator, the solves and the coefficient scatter -> singular-system flag"""
+        jobs, cb, flags = self._dates_tables(jobs, chain_begin, flags, max_chains)
+        sj = np.ascontiguousarray(solve_jobs, dtype=_abi.LSM_SOLVE_JOB_DTYPE)
+        assert len(jobs) == len(sj)
+        n = paths.shape[2]
+        flag = C.c_int32(0)
+        self._check(self.lib.mcx_lsm_dates_run(
+            self.h, book.ptr, _abi.ptr(jobs), _abi.ptr(sj), C.c_int32(len(jobs)), _abi.ptr(cb), C.c_int32(len(cb) - 1), _vp(paths.data_ptr()),
+            C.c_int64(n), C.c_int64(_ld(paths)), _vp(W.data_ptr()), C.c_int64(ld_w), C.c_int64(W.numel()), C.byref(flag), C.c_int32(flags),
+            self._stream()), "mcx_lsm_dates_run")
         return int(flag.value)
 
     # ---- K6: gas storage ------------------------------------------------------------------------------------------

@@ -143,7 +143,7 @@ def _clone_controller(sc, model, float32_cache, objects=None):
     clone = SimulationController(ns, model, rm, sc.num_paths_mainsim,
                                  sc.num_paths_presim, sc.num_steps, sc.simulation_scheme, differentiate=False,
                                  regression_function=sc.regression_function, backend=sc.backend, use_mfma=sc.use_mfma)
-    for attr in ("seed_offset", "allow_fused", "main_plan", "materialize", "_inject"):
+    for attr in ("seed_offset", "allow_fused", "main_plan", "materialize", "_inject", "date_batched_lsm"):
         setattr(clone, attr, getattr(sc, attr))
     clone.reference_float32_cf_cache = float32_cache
     return clone

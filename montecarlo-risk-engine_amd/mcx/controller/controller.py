@@ -100,6 +100,115 @@ def storage_lsm_job_table(dates_of, S_of, ld_w: int):
     return jobs, step_begin, job_of, int(base[-1])
 
 
+def lsm_job_classes(jobs, S_of, w_off, x_range, reg_base, expo_base):
+    """The regression jobs (p_i, product, schedule, atoms) grouped into classes that share (schedule, explanatory asset, state
+    count): their members differ only in their ids and offsets, so a job table takes one vectorised block per class instead of a
+    Python iteration per (product, date).  w_off[j]: cache offset of job j; reg_base / expo_base: per product index, the bases of
+    its two coefficient blocks.  -> list of per-class dicts (per-step lists, per-member arrays)"""
+    pi_all = np.fromiter((job[0] for job in jobs), dtype=np.int64, count=len(jobs))
+    reg_all = np.asarray(reg_base, dtype=np.int64)[pi_all]
+    expo_all = np.asarray(expo_base, dtype=np.int64)[pi_all]
+    w_off = np.asarray(w_off)
+    classes: dict = {}
+    for j, (p_i, p, sched, atoms) in enumerate(jobs):
+        classes.setdefault((id(sched), id(atoms), S_of[j]), []).append(j)
+    cls = []
+    for (_, _, S), members in classes.items():
+        _, _, sched, atoms = jobs[members[0]]
+        L = len(sched)
+        lo = np.array([x_range[x][0] for _, x in atoms]); hi = np.array([x_range[x][1] for _, x in atoms])
+        deg = ~(hi > lo)
+        m_ = np.asarray(members)
+        cls.append(dict(S=S, L=L, members=m_, p_i=pi_all[m_].astype(np.int32), w_off=w_off[m_],
+                        reg_base=reg_all[m_], expo_base=expo_all[m_],
+                        r0=[s[1] for s in sched], r1=[s[2] for s in sched],
+                        prod_idx=[-1 if s[3] is None else s[3] for s in sched],
+                        expo_idx=[-1 if s[4] is None else s[4] for s in sched],
+                        num=[a_[0] for a_ in atoms], x=[a_[1] for a_ in atoms], xmin=lo, deg=deg,
+                        shift=np.where(deg, lo, 0.5 * (lo + hi)), scale=np.where(deg, 1.0, 2.0 / np.where(deg, 1.0, hi - lo))))
+    return cls
+
+
+def lsm_fill_class(jt, sj, cl, dest, col, row, K: int):
+    """rows `dest` of the job table jt / solve table sj from class cl; col(v): one value per step -> the rows' order, row(v): one
+    value per member -> the rows' order; the coefficient targets as a [step][member] matrix go through col/row's common layout"""
+    S = cl["S"]
+    jt["product"][dest], jt["w_offset"][dest] = row(cl["p_i"]), row(cl["w_off"])
+    jt["roll_begin"][dest], jt["roll_end"][dest] = col(cl["r0"]), col(cl["r1"])
+    jt["num_atom"][dest], jt["x_atom"][dest] = col(cl["num"]), col(cl["x"])
+    jt["shift"][dest] = sj["shift"][dest] = col(cl["shift"])
+    jt["scale"][dest] = sj["scale"][dest] = col(cl["scale"])
+    sj["x0"][dest], sj["degenerate"][dest] = col(cl["xmin"]), col(cl["deg"], np.int32)
+    pr, ex = col(cl["prod_idx"], np.int64), col(cl["expo_idx"], np.int64)
+    t_prod = np.where(pr >= 0, row(cl["reg_base"]) + pr * (S * K), -1)
+    t_expo = np.where(ex >= 0, row(cl["expo_base"]) + ex * (S * K), -1)
+    sj["coeff_off"][dest, 0] = np.where(pr >= 0, t_prod, t_expo)      # at most two targets per system, the product block first
+    sj["coeff_off"][dest, 1] = np.where(pr >= 0, t_expo, -1)
+
+
+def lsm_step_tables(jobs, x_range, reg_base, expo_base, n_local: int, K: int):
+    """The job / solve tables of ALL steps of the product-batched induction (mcx_lsm_run_batch), host only.  Step order as the
+    reference walks it (one date further back per step, the products of one exercise-state count per launch): step (r, S) holds,
+    class by class, the members of every class with S states whose schedule is longer than r.  Destination rows by cumulative sums
+    over a [class][r] matrix, fields by broadcast assignment per class — no Python iteration per (product, date) or per step.
+    Job j owns the [S_j][n_local] cache block behind those of the jobs before it.
+    -> (jt LSM_JOB_DTYPE, sj LSM_SOLVE_JOB_DTYPE, step_begin int32 [n_steps + 1], step_states int32 [n_steps], S_of, w_len)"""
+    S_of = [p.get_num_states() for _, p, _, _ in jobs]
+    S_arr = np.asarray(S_of, dtype=np.int64)
+    w_off = np.concatenate([[0], np.cumsum(S_arr * n_local)])
+    cls = lsm_job_classes(jobs, S_of, w_off, x_range, reg_base, expo_base)
+    n_cls, max_len = len(cls), max(cl["L"] for cl in cls)
+    L_c = np.array([cl["L"] for cl in cls]); S_c = np.array([cl["S"] for cl in cls]); n_c = np.array([len(cl["members"]) for cl in cls])
+    S_vals = sorted(set(S_c.tolist()))
+    active = np.arange(max_len)[None, :] < L_c[:, None]
+    within = np.zeros((n_cls, max_len), dtype=np.int64)
+    size = np.zeros((max_len, len(S_vals)), dtype=np.int64)
+    for k_, S in enumerate(S_vals):
+        sz = n_c[:, None] * (active & (S_c == S)[:, None])
+        within += np.where((S_c == S)[:, None], np.cumsum(sz, axis=0) - sz, 0)
+        size[:, k_] = sz.sum(axis=0)
+    flat = size.reshape(-1)
+    start = np.concatenate([[0], np.cumsum(flat)])
+    keep = flat > 0
+    step_states = np.tile(np.array(S_vals, dtype=np.int32), max_len)[keep]
+    step_begin = np.concatenate([[0], np.cumsum(flat[keep])]).astype(np.int32)
+    n_jobs = int(start[-1])
+    jt = np.zeros(n_jobs, dtype=_abi.LSM_JOB_DTYPE)
+    sj = np.zeros(n_jobs, dtype=_abi.LSM_SOLVE_JOB_DTYPE)
+    for c_, cl in enumerate(cls):
+        S, L, n_m = cl["S"], cl["L"], int(n_c[c_])
+        d0 = start[np.arange(L) * len(S_vals) + S_vals.index(S)] + within[c_, :L]
+        dest = (d0[:, None] + np.arange(n_m)[None, :]).reshape(-1)                 # [step][member]
+        col = lambda v, dt=None: np.repeat(np.asarray(v, dtype=dt), n_m)            # one value per step -> every member
+        row = lambda v: np.tile(v, L)                                              # one value per member -> every step
+        lsm_fill_class(jt, sj, cl, dest, col, row, K)
+    return jt, sj, step_begin, step_states, S_of, int(w_off[-1])
+
+
+def lsm_date_chains(jobs, x_range, reg_base, expo_base, n_local: int, K: int):
+    """The date-batched route's tables (mcx_lsm_dates_moments / mcx_lsm_dates_run), host only.  The regression jobs (p_i, product,
+    schedule, atoms) are split into the stateless ones (get_num_states() == 1: their roll reads no regression output) and the rest.
+    Every stateless product is one CHAIN: its systems in schedule order, consecutive in the table (none for an empty schedule), on
+    a private [n_local] cache row (chain c owns W[c * n_local : (c + 1) * n_local]).  Same per-class arrays, same fields and the same
+    coefficient targets per (product, date) as the step-major table of the product-batched route.
+    -> (stateless jobs, remaining jobs, jt LSM_JOB_DTYPE, sj LSM_SOLVE_JOB_DTYPE, chain_begin int32 [n_chains + 1], w_len)"""
+    stateless = [job for job in jobs if job[1].get_num_states() == 1]
+    rest = [job for job in jobs if job[1].get_num_states() != 1]
+    L_of = np.array([len(job[2]) for job in stateless], dtype=np.int64)
+    chain_begin = np.concatenate([[0], np.cumsum(L_of)]).astype(np.int32)
+    n_jobs = int(chain_begin[-1])
+    jt = np.zeros(n_jobs, dtype=_abi.LSM_JOB_DTYPE)
+    sj = np.zeros(n_jobs, dtype=_abi.LSM_SOLVE_JOB_DTYPE)
+    w_off = np.arange(len(stateless), dtype=np.int64) * n_local
+    for cl in lsm_job_classes(stateless, [1] * len(stateless), w_off, x_range, reg_base, expo_base):
+        L, n_m = cl["L"], len(cl["members"])
+        dest = (chain_begin[cl["members"]].astype(np.int64)[:, None] + np.arange(L)[None, :]).reshape(-1)      # [member][step]
+        col = lambda v, dt=None: np.tile(np.asarray(v, dtype=dt), n_m)
+        row = lambda v: np.repeat(v, L)
+        lsm_fill_class(jt, sj, cl, dest, col, row, K)
+    return stateless, rest, jt, sj, chain_begin, len(stateless) * n_local
+
+
 class SimulationController:
     @single_threaded_host()
     def __init__(self, netting_sets: Sequence[NettingSet], model: Model, risk_metrics: RiskMetrics,
@@ -158,6 +267,13 @@ class SimulationController:
         self.materialize = False     # also write paths / cashflows / exposures in the fused pass (inspection, tests)
         self.batch_lsm = True        # product-batched LSM pre-simulation (one launch per backward step of the whole book)
         self.batch_storage_lsm = True        # the same for gas storages: two or more of them share the launches of a step
+        # True: the products without exercise rights (one exercise state) regress all their dates in ONE launch and ONE collective
+        # (mcx_lsm_dates_run / mcx_lsm_dates_moments), at any product count; the others keep their route.  Bit-equal to the
+        # product-batched route; against the per-product route the moments are reordered sums of the same terms
+        self.date_batched_lsm = False
+        # what the last regression ran: systems through the date-batched route, steps of the product-batched route, products of
+        # the per-product route
+        self.lsm_routes = {"dates": 0, "batched_steps": 0, "per_product": 0}
         # differentiate=True, regression of the products without exercise states in forward mode: None = one mcx_tangent_lsm_batch
         # call per parameter chunk for a book of more than 64 products, one mcx_tangent_lsm call per (product, date) below;
         # True / False = the batched / the per-job route at any size (mcx/aad.py run_with_tangent_book)
@@ -611,6 +727,7 @@ class SimulationController:
 
     def _perform_regression(self, shard: Shard, sim_plan: SimPlan, sim):
         be = self.backend
+        self.lsm_routes = {"dates": 0, "batched_steps": 0, "per_product": 0}
         off, n_local = shard.split(self.num_paths_presim)
         eng = MonteCarloEngine(self.simulation_timeline, self.simulation_scheme, self.model, n_local, self.num_steps,
                                is_pre_simulation=True, path_offset=off, backend=be, plan=sim_plan, sim=sim,
@@ -639,12 +756,76 @@ class SimulationController:
                     self._storage_regression(shard, p_i, p, sched, atoms, x_range, paths, n_local, K, lsm_flags)
         if not jobs:
             return
+        args = (x_range, paths, n_local, K, lsm_flags)
+        if not (self.date_batched_lsm and not self.use_mfma and hasattr(be, "lsm_dates_run")):
+            return self._perform_regression_routes(shard, jobs, *args)
+        # date-batched route: the products without exercise rights in one launch and one collective (any count of them), the others
+        # on the route the remaining list takes today.  The two groups share no coefficient slot and no cache block, so their
+        # order is free: the others go first because their batched route resets the book's coefficients when it has to repeat
+        # itself with host solves
+        stateless, rest, jt, sj, chain_begin, w_len = lsm_date_chains(jobs, x_range, self._reg_coeff_base, self._expo_coeff_base, n_local, K)
+        if rest:
+            self._perform_regression_routes(shard, rest, *args)
+        if stateless and not self._perform_regression_dates(shard, stateless, jt, sj, chain_begin, w_len, *args):
+            # a numerically singular system: the whole regression again through the routes above with host solves
+            self.lsm_singular_retries = getattr(self, "lsm_singular_retries", 0) + 1
+            self.lsm_routes.update(dates=0, batched_steps=0, per_product=0)
+            self._lsm_host_solves = True
+            try:
+                be.book_reset_coeffs(self.book, self._coeffs_at_upload)
+                self._perform_regression_routes(shard, jobs, *args)
+            finally:
+                self._lsm_host_solves = False
+
+    def _perform_regression_dates(self, shard: Shard, stateless, jt, sj, chain_begin, w_len: int, x_range, paths, n_local: int, K: int,
+                                  lsm_flags: int) -> bool:
+        """The regression of the products without exercise rights through the date-batched entry points (lsm_date_chains): one moment
+        launch over every (product, date) system and ONE collective.  False: a system came out numerically singular (no host mirror
+        is touched; the caller repeats the regression with host solves)."""
+        be = self.backend
+        W = be.zeros(max(w_len, 1))
+        mirror = None
+        if len(jt) == 0:
+            pass
+        elif shard.world == 1:
+            if be.lsm_dates_run(self.book, jt, sj, chain_begin, paths, W, n_local, flags=lsm_flags) != 0:
+                return False
+        else:
+            mom = be.lsm_dates_moments(self.book, jt, chain_begin, paths, W, n_local, flags=lsm_flags)
+            if shard.device_collectives:
+                flag = be.zeros(1, dtype=torch.int32)
+                shard.all_reduce_(mom)
+                be.lsm_solve_batch(self.book, sj, 1, mom, flag)
+                if int(flag.cpu()[0]) != 0:
+                    return False
+            else:
+                # host collectives: the reduce and the solves on the host (the solver falls back to lstsq on a singular system)
+                mom = shard.all_reduce_np(mom.cpu().numpy())
+                coeffs = solve_normal_equations_batch(mom, K, 1, jt["shift"], jt["scale"], sj["degenerate"].astype(bool), sj["x0"]).reshape(len(jt), K)
+                tgt = sj["coeff_off"]
+                rows = np.concatenate([np.nonzero(tgt[:, w] >= 0)[0] for w in (0, 1)])
+                mirror = np.zeros(len(self.book_plan.coeffs))
+                if len(rows):
+                    offs = np.concatenate([tgt[tgt[:, w] >= 0, w] for w in (0, 1)]).astype(np.int64)
+                    be.book_set_coeffs_batch(self.book, offs, coeffs[rows])
+                    mirror[offs[:, None] + np.arange(K)[None, :]] = coeffs[rows]
+        if mirror is None:
+            mirror = be.book_get_coeffs(self.book)
+            self.book.plan.coeffs[:] = mirror                                 # (the host image of the uploaded book follows)
+        self.lsm_routes["dates"] = len(jt)
+        self._adopt_coefficient_image(stateless, [1] * len(stateless), mirror, K)
+        return True
+
+    def _perform_regression_routes(self, shard: Shard, jobs, x_range, paths, n_local: int, K: int, lsm_flags: int):
+        """the product-batched route for four jobs or more, the per-product route below"""
+        be = self.backend
         if self.batch_lsm and not self.use_mfma and len(jobs) >= 4:       # (one or two products: the per-product loop has less fixed cost per step)
             return self._perform_regression_batched(shard, jobs, x_range, paths, n_local, K, lsm_flags)
+        self.lsm_routes["per_product"] = len(jobs)
         for p_i, p, sched, atoms in jobs:
             S = p.get_num_states()
-            W = be.zeros(S, n_local)
-            if hasattr(be, "lsm_run") and (shard.world == 1 or shard.device_collectives) \
+            W = be.zeros(S, max(n_local, 1))                               # (a rank without paths: an empty tensor has no data pointer)
+            if hasattr(be, "lsm_run") and (shard.world == 1 or shard.device_collectives) and not getattr(self, "_lsm_host_solves", False) \
                     and self._lsm_on_device(be, p_i, p, sched, atoms, x_range, paths, W, S, K, lsm_flags, shard):
                 continue
             W.zero_()
@@ -839,75 +1020,10 @@ class SimulationController:
         coefficients go back in one scatter.  Same arithmetic per (product, date) as the per-product loop above
         (reference: controller.py:289-383, one Python iteration per product and date)."""
         be = self.backend
-        S_of = [p.get_num_states() for _, p, _, _ in jobs]
-        S_arr = np.asarray(S_of, dtype=np.int64)
-        w_off = np.concatenate([[0], np.cumsum(S_arr * n_local)])
-        tot = int(w_off[-1])
+        jt, sj, step_begin, step_states, S_of, tot = lsm_step_tables(jobs, x_range, self._reg_coeff_base, self._expo_coeff_base, n_local, K)
         W = be.zeros(max(tot, 1))
         mirror = np.zeros(len(self.book_plan.coeffs))                 # host image of the coefficients this pass produces
-        # products sharing (schedule, explanatory asset, state count) differ only in their ids and offsets: one vectorised
-        # block of the job table per class and step instead of a Python iteration per (product, date)
-        pi_all = np.fromiter((job[0] for job in jobs), dtype=np.int64, count=len(jobs))
-        reg_all = np.asarray(self._reg_coeff_base, dtype=np.int64)[pi_all]
-        expo_all = np.asarray(self._expo_coeff_base, dtype=np.int64)[pi_all]
-        classes: dict = {}
-        for j, (p_i, p, sched, atoms) in enumerate(jobs):
-            classes.setdefault((id(sched), id(atoms), S_of[j]), []).append(j)
-        cls = []
-        for (_, _, S), members in classes.items():
-            _, _, sched, atoms = jobs[members[0]]
-            L = len(sched)
-            lo = np.array([x_range[x][0] for _, x in atoms]); hi = np.array([x_range[x][1] for _, x in atoms])
-            deg = ~(hi > lo)
-            m_ = np.asarray(members)
-            cls.append(dict(S=S, L=L, members=m_, p_i=pi_all[m_].astype(np.int32), w_off=w_off[m_],
-                            reg_base=reg_all[m_], expo_base=expo_all[m_],
-                            r0=[s[1] for s in sched], r1=[s[2] for s in sched],
-                            prod_idx=[-1 if s[3] is None else s[3] for s in sched],
-                            expo_idx=[-1 if s[4] is None else s[4] for s in sched],
-                            num=[a_[0] for a_ in atoms], x=[a_[1] for a_ in atoms], xmin=lo, deg=deg,
-                            shift=np.where(deg, lo, 0.5 * (lo + hi)), scale=np.where(deg, 1.0, 2.0 / np.where(deg, 1.0, hi - lo))))
-        # the job / solve tables of ALL steps at once.  Step order as the reference walks it (one date further back per step, the
-        # products of one exercise-state count per launch): step (r, S) holds, class by class, the members of every class with S
-        # states whose schedule is longer than r.  Destination rows by cumulative sums over a [class][r] matrix, fields by
-        # broadcast assignment per class — no Python iteration per (product, date) or per step.
-        n_cls, max_len = len(cls), max(cl["L"] for cl in cls)
-        L_c = np.array([cl["L"] for cl in cls]); S_c = np.array([cl["S"] for cl in cls]); n_c = np.array([len(cl["members"]) for cl in cls])
-        S_vals = sorted(set(S_c.tolist()))
-        active = np.arange(max_len)[None, :] < L_c[:, None]
-        within = np.zeros((n_cls, max_len), dtype=np.int64)
-        size = np.zeros((max_len, len(S_vals)), dtype=np.int64)
-        for k_, S in enumerate(S_vals):
-            sz = n_c[:, None] * (active & (S_c == S)[:, None])
-            within += np.where((S_c == S)[:, None], np.cumsum(sz, axis=0) - sz, 0)
-            size[:, k_] = sz.sum(axis=0)
-        flat = size.reshape(-1)
-        start = np.concatenate([[0], np.cumsum(flat)])
-        keep = flat > 0
-        step_states = np.tile(np.array(S_vals, dtype=np.int32), max_len)[keep]
-        step_begin = np.concatenate([[0], np.cumsum(flat[keep])]).astype(np.int32)
-        n_jobs = int(start[-1])
-        jt = np.zeros(n_jobs, dtype=_abi.LSM_JOB_DTYPE)
-        sj = np.zeros(n_jobs, dtype=_abi.LSM_SOLVE_JOB_DTYPE)
-        sj_off = sj["coeff_off"]
-        for c_, cl in enumerate(cls):
-            S, L, n_m = cl["S"], cl["L"], int(n_c[c_])
-            d0 = start[np.arange(L) * len(S_vals) + S_vals.index(S)] + within[c_, :L]
-            dest = (d0[:, None] + np.arange(n_m)[None, :]).reshape(-1)
-            col = lambda v, dt=None: np.repeat(np.asarray(v, dtype=dt), n_m)            # one value per step -> every member
-            row = lambda v: np.tile(v, L)                                              # one value per member -> every step
-            jt["product"][dest], jt["w_offset"][dest] = row(cl["p_i"]), row(cl["w_off"])
-            jt["roll_begin"][dest], jt["roll_end"][dest] = col(cl["r0"]), col(cl["r1"])
-            jt["num_atom"][dest], jt["x_atom"][dest] = col(cl["num"]), col(cl["x"])
-            jt["shift"][dest] = sj["shift"][dest] = col(cl["shift"])
-            jt["scale"][dest] = sj["scale"][dest] = col(cl["scale"])
-            sj["x0"][dest], sj["degenerate"][dest] = col(cl["xmin"]), col(cl["deg"], np.int32)
-            pr, ex = np.asarray(cl["prod_idx"], dtype=np.int64), np.asarray(cl["expo_idx"], dtype=np.int64)
-            t_prod = np.where(pr[:, None] >= 0, cl["reg_base"][None, :] + pr[:, None] * (S * K), -1)
-            t_expo = np.where(ex[:, None] >= 0, cl["expo_base"][None, :] + ex[:, None] * (S * K), -1)
-            has_p = np.broadcast_to(pr[:, None] >= 0, t_prod.shape)                   # at most two targets per system, the product block first
-            sj_off[dest, 0] = np.where(has_p, t_prod, t_expo).reshape(-1)
-            sj_off[dest, 1] = np.where(has_p, t_expo, -1).reshape(-1)
+        self.lsm_routes["batched_steps"] = len(step_states)
         # solves on the device when the backend has them; a singular system anywhere repeats the induction with the host solver
         # (which falls back to lstsq)
         on_device = hasattr(be, "lsm_solve_batch") and not getattr(self, "_lsm_host_solves", False)
@@ -950,6 +1066,10 @@ class SimulationController:
                     self._lsm_host_solves = False
             mirror = be.book_get_coeffs(self.book)
             self.book.plan.coeffs[:] = mirror                                 # (the host image of the uploaded book follows)
+        self._adopt_coefficient_image(jobs, S_of, mirror, K)
+
+    def _adopt_coefficient_image(self, jobs, S_of, mirror: np.ndarray, K: int):
+        """the host mirrors of the regression coefficients of `jobs` as views of one image of the book's coefficient array"""
         E = len(self.exposure_timeline)
         mt = torch.from_numpy(mirror)                                 # the products' coefficient tensors are views of this one image
         for j, (p_i, p, _, _) in enumerate(jobs):

@@ -131,6 +131,8 @@ def main():
     ap.add_argument("--book", choices=("cva", "ee", "pv"), default="cva")
     ap.add_argument("--storages", type=int, default=0, help="gas storages added to the book (the reference scripts: 10 per 4,990 products)")
     ap.add_argument("--profile", action="store_true", help="cProfile the last repetition's run_simulation (top functions to stderr)")
+    ap.add_argument("--date-batched-lsm", action="store_true", help="SimulationController.date_batched_lsm: the products without exercise rights "
+                    "regress all their dates in one launch")
     args = ap.parse_args()
     from mcx import _native
     be = _native.HipBackend(0)
@@ -155,6 +157,7 @@ def main():
             rm_kw, scheme = (dict(exposure_timeline=tl) if args.book == "ee" else {}), SimulationScheme.ANALYTICAL
         t0 = time.perf_counter()
         sc = SimulationController([ns], model, RiskMetrics(mets, **rm_kw), args.paths, args.paths, 1, scheme, backend=be)
+        sc.date_batched_lsm = args.date_batched_lsm
         t1 = time.perf_counter()
         if args.profile and rep == args.repeat - 1:
             import cProfile, pstats
@@ -168,7 +171,7 @@ def main():
         out = dict(book=args.book, products=len(products), counts=counts, storages=args.storages, paths=args.paths, exposure_points=args.exposure_points,
                    timeline_size=int(sc.simulation_timeline.numel()), construct_s=t1 - t0, run_s=t2 - t1,
                    products_per_second=len(products) / (t2 - t1), timings=sc.timings, prepare=getattr(sc, 'prepare_timings', None),
-                   lsm_singular_retries=getattr(sc, 'lsm_singular_retries', 0), storage_lsm_route=getattr(sc, 'storage_lsm_route', None),
+                   lsm_singular_retries=getattr(sc, 'lsm_singular_retries', 0), lsm_routes=sc.lsm_routes, storage_lsm_route=getattr(sc, 'storage_lsm_route', None),
                    storage_lsm_singular_retries=getattr(sc, 'storage_lsm_singular_retries', 0))
         name = ns.get_name()
         if args.book == "ee":
