@@ -43,6 +43,8 @@ extern "C" {
 #define MCX_MAX_SLOTS   8    /* sub-models in one ModelConfig                                  */
 #define MCX_MAX_Z       8    /* total simulation dimension (correlated normals per sub-step)    */
 #define MCX_MAX_STATE   16   /* total state dimension D                                         */
+#define MCX_WIDE_MAX_SLOTS 32 /* one-factor sub-models of a wide model (mcx_sim_create_wide)       */
+#define MCX_WIDE_MAX_STATE 64 /* total state dimension D of a wide model                           */
 #define MCX_SLOT_NPARAM 8
 #define MCX_AUX         8    /* host-precomputed per-(sub-step, slot) constants                 */
 #define MCX_MAX_BASIS   6    /* regression basis functions (polynomial degree + 1)              */
@@ -110,6 +112,38 @@ typedef struct {
     const double*   aux;      /* [n_steps][n_slots][MCX_AUX]                                          */
     const double*   init_state; /* [n_state]                                                          */
 } mcx_sim_desc;
+
+/* ---- wide models: 1 .. MCX_WIDE_MAX_SLOTS correlated ONE-FACTOR sub-models -------------------------------------------
+ * mcx_sim_desc with the slot records behind a pointer.  Every slot has simulation dimension 1 and one of the kinds MCX_MODEL_BS,
+ * VASICEK, HW, CIRPP, CIRPP_DET, under EULER or ANALYTICAL as mcx_sim_create allows per kind; hence n_z == n_slots,
+ * n_state <= MCX_WIDE_MAX_STATE and n_uniform == 0.  The contract of the paths is the narrow kernel's, extended:
+ *   - normal f of sub-step k of global path p is component f & 1 of the Box-Muller pair of Philox block (p, k, draw = f >> 1)
+ *     under the seed (RNG contract below); an odd n_z discards the last second component;
+ *   - correlated normal r is L[r][0] z[0], then fma over ascending c <= r (under EULER row 0 is z[0] itself: the factor of a
+ *     correlation matrix starts with 1); under ANALYTICAL one factor per distinct dt, selected by mcx_step::chol_idx;
+ *   - the step maps, aux semantics and derived Euler constants are those of mcx_sim_create, slot by slot;
+ *   - stores, n_initial_store, path_offset, a padded ld, injected draws d_inject_z [n_steps][n_z][ld] and a per-path start state
+ *     behave as for a narrow sim.
+ * The result is the same opaque mcx_sim, marked wide: mcx_generate_paths, mcx_generate_paths_from_state, mcx_sim_describe and
+ * mcx_sim_destroy take it; mcx_fused_create, mcx_tangent_european, mcx_tangent_paths, mcx_tangent_paths_chol,
+ * mcx_tangent_paths_s2f and mcx_tangent_paths_heston return MCX_E_NOT_FUSABLE (reason in mcx_last_error) and write nothing. */
+typedef struct {
+    int32_t scheme;
+    int32_t n_slots;          /* 1 .. MCX_WIDE_MAX_SLOTS                                              */
+    int32_t n_state;
+    int32_t n_z;              /* == n_slots                                                           */
+    int32_t n_uniform;        /* 0                                                                    */
+    int32_t n_steps;
+    int32_t n_dates;
+    int32_t n_chol;
+    int32_t n_initial_store;
+    int32_t flags;
+    const mcx_slot* slots;    /* [n_slots]                                                            */
+    const mcx_step* steps;    /* [n_steps]                                                            */
+    const double*   chol;     /* [n_chol][n_z][n_z] row-major, lower triangular                       */
+    const double*   aux;      /* [n_steps][n_slots][MCX_AUX]                                          */
+    const double*   init_state; /* [n_state]                                                          */
+} mcx_wide_sim_desc;
 
 /* ---- RNG contract (bit-exact between oracle and HIP) ----------------------------------------------------------------
  * Philox4x32-10 (Salmon et al. 2011, Random123 constants M0=0xD2511F53 M1=0xCD9E8D57 W0=0x9E3779B9 W1=0xBB67AE85).
@@ -265,6 +299,10 @@ int         mcx_device_info(mcx_handle* h, int32_t* n_cu, int64_t* hbm_bytes, ch
 
 /* K1 — replaces MonteCarloEngine(...).generate_paths() (engine/engine.py:10-33). */
 int  mcx_sim_create(mcx_handle* h, const mcx_sim_desc* desc, mcx_sim** out);
+/* A wide model (mcx_wide_sim_desc above).  The checks and codes of mcx_sim_create; -2 outside 1 .. MCX_WIDE_MAX_SLOTS slots, when
+ * n_z != n_slots, or for a slot kind a wide model cannot hold.  Models of 1 .. 8 slots are accepted too (they produce the paths of
+ * the generic narrow kernel bit for bit). */
+int  mcx_sim_create_wide(mcx_handle* h, const mcx_wide_sim_desc* desc, mcx_sim** out);
 void mcx_sim_destroy(mcx_sim* sim);
 int  mcx_generate_paths(mcx_handle* h, const mcx_sim* sim, uint64_t seed, uint64_t path_offset, int64_t n_paths,
                         int64_t ld, double* d_paths /* [n_dates][n_state][ld] */,
@@ -283,7 +321,8 @@ int  mcx_generate_paths_from_state(mcx_handle* h, const mcx_sim* sim, uint64_t s
  * MCX_SIG_GENERIC: run-time dispatch per slot), out[1] = slots, out[2] = normals per sub-step of the instantiation.  Returns 0,
  * -1 on an invalid argument, -4 when no instantiation exists (the launch would fail with the same code).  Reads host memory only. */
 enum { MCX_SIG_GENERIC = 0, MCX_SIG_VAS_CIR_E = 1, MCX_SIG_BS_A = 2, MCX_SIG_BS_E = 3, MCX_SIG_HESTON_QE = 4, MCX_SIG_HESTON_E = 5,
-       MCX_SIG_VAS_E = 6, MCX_SIG_VAS_A = 7, MCX_SIG_BS_VAS_CIRDET_E = 8 };
+       MCX_SIG_VAS_E = 6, MCX_SIG_VAS_A = 7, MCX_SIG_BS_VAS_CIRDET_E = 8,
+       MCX_SIG_WIDE = 9 /* a wide sim: out[1] = out[2] = its slot count (the kernel's capacity is 16 or 32) */ };
 int  mcx_sim_describe(const mcx_sim* sim, int32_t* out);
 
 /* Probe of the RNG contract above (what the path kernels consume): for i < n the draw (path = path0 + i, step, draw) as

@@ -245,6 +245,7 @@ extern "C" void mcx_sim_destroy(mcx_sim* sim)
 {
     if (!sim) return;
     hipFree(sim->d_steps); hipFree(sim->d_chol); hipFree(sim->d_aux);
+    hipFree(sim->d_slots); hipFree(sim->d_init);
     delete[] sim->desc.init_state;
     delete sim;
 }
@@ -259,6 +260,7 @@ static_assert(SIG_GENERIC == MCX_SIG_GENERIC && SIG_VAS_CIR_E == MCX_SIG_VAS_CIR
 extern "C" int mcx_sim_describe(const mcx_sim* sim, int32_t* out)
 {
     if (!sim || !out) return -1;
+    if (sim->wide) { out[0] = MCX_SIG_WIDE; out[1] = sim->desc.n_slots; out[2] = sim->desc.n_z; return 0; }
     const bool found = mcx_dispatch_signature<8>(sim->desc, [&](auto nslot, auto nz, auto sig) {
         out[0] = decltype(sig)::value; out[1] = decltype(nslot)::value; out[2] = decltype(nz)::value;
     });
@@ -285,6 +287,7 @@ static int generate_paths_impl(mcx_handle* h, const mcx_sim* sim, uint64_t seed,
     if (!h || !sim || !d_paths) return -1;
     if (n_paths <= 0) return 0;
     if (ld < n_paths) MCX_FAIL(h, -2, "mcx_generate_paths: ld < n_paths");
+    if (sim->wide) return mcx_wide_generate(h, sim, seed, path_offset, n_paths, ld, d_init_state, d_paths, d_inject_z, stream);
     const mcx_sim_desc& d = sim->desc;
     if (d.n_uniform && d_inject_z && !d_inject_u) MCX_FAIL(h, -3, "mcx_generate_paths: inject_u required with inject_z under QE");
     K1Args a;

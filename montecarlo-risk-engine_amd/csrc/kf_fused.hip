@@ -865,6 +865,7 @@ int upload(mcx_handle* h, const mcx_sim* sim, const mcx_book* book, const mcx_fu
 extern "C" int mcx_fused_create(mcx_handle* h, const mcx_sim* sim, const mcx_book* book, const mcx_fused_desc* d, mcx_fused** out)
 {
     if (!h || !sim || !book || !d || !out) return -1;
+    MCX_REFUSE_WIDE(h, sim, "mcx_fused_create");
     const mcx_sim_desc& sd = sim->desc;
     if (const int rc = check_arguments(h, sd, book, d)) return rc;
     const int T = sd.n_dates;

@@ -1087,6 +1087,7 @@ int ktp_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const do
               void* stream, const char* who, bool chol_entry)
 {
     if (!h || !sim || !h_dslot || !h_dinit || !h_daux || !d_paths || !d_dpaths) return -1;
+    MCX_REFUSE_WIDE(h, sim, "mcx_tangent_paths / mcx_tangent_paths_chol");
     const mcx_sim_desc& sd = sim->desc;
     const bool analytic = chol_entry && sd.scheme == MCX_SCHEME_ANALYTICAL;
     if (analytic && !h_dchol) return -1;
@@ -1161,6 +1162,7 @@ extern "C" int mcx_tangent_paths_heston(mcx_handle* h, const mcx_sim* sim, const
 {
     const char* who = "mcx_tangent_paths_heston";
     if (!h || !sim || !h_dslot || !h_dinit || !h_daux || !d_paths || !d_dpaths) return -1;
+    MCX_REFUSE_WIDE(h, sim, "mcx_tangent_paths_heston");
     const mcx_sim_desc& sd = sim->desc;
     const bool euler = sd.scheme == MCX_SCHEME_EULER, qe = sd.scheme == MCX_SCHEME_QE;
     if (euler && !h_dchol) return -1;

@@ -494,6 +494,7 @@ extern "C" int mcx_tangent_paths_s2f(mcx_handle* h, const mcx_sim* sim, const do
 {
     const char* who = "mcx_tangent_paths_s2f";
     if (!h || !sim || !h_dslot || !h_dinit || !h_daux || !h_dchol || !d_paths || !d_dpaths) return -1;
+    MCX_REFUSE_WIDE(h, sim, "mcx_tangent_paths_s2f");
     if (n_paths <= 0) return 0;
     if (ld < n_paths) MCX_FAIL(h, -2, "%s: ld < n_paths", who);
     const mcx_sim_desc& sd = sim->desc;

@@ -295,6 +295,7 @@ extern "C" int mcx_tangent_european(mcx_handle* h, const mcx_sim* sim, const mcx
                                     const double* d_inject_u, void* stream)
 {
     if (!h || !sim || !h_opts || !d_cfs || !d_dcfs) return -1;
+    MCX_REFUSE_WIDE(h, sim, "mcx_tangent_european");
     const mcx_sim_desc& d = sim->desc;
     if (d.n_slots != 1 || (d.slots[0].kind != MCX_MODEL_BS && d.slots[0].kind != MCX_MODEL_HESTON))
         MCX_FAIL(h, -2, "mcx_tangent_european: single Black-Scholes or Heston model required");

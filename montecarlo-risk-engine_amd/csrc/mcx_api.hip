@@ -64,7 +64,7 @@ extern "C" int mcx_book_create(mcx_handle* h, const mcx_book_desc* d, mcx_book**
 {
     if (!h || !d || !out) return -1;
     if (d->n_basis < 1 || d->n_basis > MCX_MAX_BASIS) MCX_FAIL(h, -2, "mcx_book_create: n_basis %d out of range", d->n_basis);
-    if (d->n_state < 1 || d->n_state > MCX_MAX_STATE) MCX_FAIL(h, -2, "mcx_book_create: n_state %d out of range", d->n_state);
+    if (d->n_state < 1 || d->n_state > MCX_WIDE_MAX_STATE) MCX_FAIL(h, -2, "mcx_book_create: n_state %d out of range", d->n_state);
     // validate every index the kernels will dereference (a wild index on the GPU can take the whole node down)
     if (d->n_dates < 1) MCX_FAIL(h, -2, "mcx_book_create: n_dates %d out of range", d->n_dates);
     for (int i = 0; i < d->n_atoms; ++i)

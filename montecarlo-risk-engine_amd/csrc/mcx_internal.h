@@ -183,7 +183,22 @@ struct mcx_sim {
     std::vector<mcx_step> h_steps; // host copy of the sub-step table (per-step records derived from it: kt_tangent.hip)
     int n_state_total;
     int state_dim[MCX_MAX_SLOTS];
+    // a wide sim (mcx_sim_create_wide, k1_wide.hip): up to MCX_WIDE_MAX_SLOTS one-factor slots whose records and initial state live
+    // in device tables; desc.slots / desc.init_state are EMPTY, so every entry point that takes an mcx_sim checks `wide` first
+    bool wide = false;
+    mcx_slot* d_slots = nullptr;   // [desc.n_slots]
+    double* d_init = nullptr;      // [desc.n_state]
 };
+// the refusal of the entry points that have no wide form (fused kernels, forward-mode tangents)
+#define MCX_REFUSE_WIDE(h, sim, who)                                                                                          \
+    do {                                                                                                                      \
+        if ((sim)->wide)                                                                                                      \
+            MCX_FAIL(h, MCX_E_NOT_FUSABLE, who ": a wide model (%d slots; this entry point takes at most MCX_MAX_SLOTS = %d) runs "  \
+                     "through mcx_generate_paths and the unfused passes only", (sim)->desc.n_slots, MCX_MAX_SLOTS);            \
+    } while (0)
+// k1_wide.hip: the launch behind mcx_generate_paths / mcx_generate_paths_from_state for a wide sim
+int mcx_wide_generate(mcx_handle* h, const mcx_sim* sim, uint64_t seed, uint64_t path_offset, int64_t n_paths, int64_t ld,
+                      const double* d_init_state, double* d_paths, const double* d_inject_z, void* stream);
 
 // ---- device helpers -------------------------------------------------------------------------------------------------
 // Read-only, wave-uniform table loads.  Kernel tables (sub-step table, Cholesky factors, event program, coefficients) are

@@ -10,6 +10,9 @@ SELECT_LOST = 1 << 44        # MCX_SELECT_LOST (mcx_select_bracket)
 MAX_SLOTS = 8
 MAX_Z = 8
 MAX_STATE = 16
+WIDE_MAX_SLOTS = 32         # MCX_WIDE_MAX_SLOTS: one-factor sub-models of a wide model (mcx_sim_create_wide)
+WIDE_MAX_STATE = 64
+WIDE_KINDS = (1, 3, 4, 5, 6)  # MCX_MODEL_BS, VASICEK, CIRPP, CIRPP_DET, HW: the kinds a wide model may hold
 SLOT_NPARAM = 8
 AUX = 8
 MAX_BASIS = 6
@@ -21,7 +24,7 @@ SCHEME_EULER, SCHEME_MILSTEIN, SCHEME_ANALYTICAL, SCHEME_QE = 0, 1, 2, 3
 MODEL_BS, MODEL_HESTON, MODEL_VASICEK, MODEL_CIRPP, MODEL_CIRPP_DET, MODEL_HW, MODEL_S2F = 1, 2, 3, 4, 5, 6, 7
 FLAG_SMOOTHING = 1
 # MCX_SIG_*: the model signatures of the path kernels, as mcx_sim_describe reports them
-SIG_NAMES = ("GENERIC", "VAS_CIR_E", "BS_A", "BS_E", "HESTON_QE", "HESTON_E", "VAS_E", "VAS_A", "BS_VAS_CIRDET_E")
+SIG_NAMES = ("GENERIC", "VAS_CIR_E", "BS_A", "BS_E", "HESTON_QE", "HESTON_E", "VAS_E", "VAS_A", "BS_VAS_CIRDET_E", "WIDE")
 LSM_MFMA, LSM_F32_CACHE = 1, 2
 EV_CASHFLOW, EV_OPTION, EV_EXERCISE, EV_EXPO_POLY, EV_EXPO_BS = 1, 2, 3, 4, 5
 
@@ -50,6 +53,15 @@ class SimDesc(C.Structure):
                 ("n_uniform", C.c_int32), ("n_steps", C.c_int32), ("n_dates", C.c_int32), ("n_chol", C.c_int32),
                 ("n_initial_store", C.c_int32), ("flags", C.c_int32),
                 ("slots", Slot * MAX_SLOTS),
+                ("steps", C.c_void_p), ("chol", C.c_void_p), ("aux", C.c_void_p), ("init_state", C.c_void_p)]
+
+
+class WideSimDesc(C.Structure):
+    """mcx_wide_sim_desc: SimDesc with the slot records behind a pointer ([n_slots] Slot)"""
+    _fields_ = [("scheme", C.c_int32), ("n_slots", C.c_int32), ("n_state", C.c_int32), ("n_z", C.c_int32),
+                ("n_uniform", C.c_int32), ("n_steps", C.c_int32), ("n_dates", C.c_int32), ("n_chol", C.c_int32),
+                ("n_initial_store", C.c_int32), ("flags", C.c_int32),
+                ("slots", C.c_void_p),
                 ("steps", C.c_void_p), ("chol", C.c_void_p), ("aux", C.c_void_p), ("init_state", C.c_void_p)]
 
 

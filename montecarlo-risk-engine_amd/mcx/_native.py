@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("MCX_LIB_PATH") or os.path.join(os.path.dirname(_HERE)
 
 _EXPORTS = [
     "mcx_abi_version", "mcx_create", "mcx_destroy", "mcx_last_error", "mcx_device_info",
-    "mcx_sim_create", "mcx_sim_destroy", "mcx_generate_paths", "mcx_generate_paths_from_state", "mcx_sim_describe", "mcx_rng_draws",
+    "mcx_sim_create", "mcx_sim_create_wide", "mcx_sim_destroy", "mcx_generate_paths", "mcx_generate_paths_from_state", "mcx_sim_describe", "mcx_rng_draws",
     "mcx_comm_unique_id", "mcx_comm_init", "mcx_comm_destroy", "mcx_allreduce_f64", "mcx_allgather_f64",
     "mcx_book_create", "mcx_book_destroy", "mcx_book_set_coeffs", "mcx_eval_book", "mcx_eval_book_describe", "mcx_resolve_atoms",
     "mcx_lsm_stats", "mcx_lsm_step", "mcx_lsm_run", "mcx_lsm_solve", "mcx_lsm_step_batch", "mcx_lsm_step_batch_dev", "mcx_lsm_solve_batch", "mcx_lsm_run_batch", "mcx_lsm_dates_moments", "mcx_lsm_dates_run", "mcx_book_get_coeffs", "mcx_book_set_coeffs_batch", "mcx_book_set_bridge_rng", "mcx_book_set_exercise_replay", "mcx_book_set_payoff_tangents",
@@ -75,6 +75,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_tangent_paths_chol.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_tangent_paths_heston.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp, vp]
     lib.mcx_sim_describe.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mcx_sim_create_wide.argtypes = [vp, vp, vp]
     lib.mcx_fused_num_records.argtypes = [C.c_void_p]
     lib.mcx_fused_is_straight_line.argtypes = [C.c_void_p]
     lib.mcx_fused_describe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
@@ -137,6 +138,7 @@ class HipBackend:
     """One per process / GPU. Methods mirror the C ABI one-to-one; tensors are torch CUDA tensors (float64)."""
 
     name = "hip"
+    supports_wide = True        # mcx_sim_create_wide: SimPlan.wide plans (more than MCX_MAX_SLOTS one-factor sub-models)
 
     def __init__(self, device_index: int | None = None):
         self.lib = load_library()
@@ -190,8 +192,12 @@ class HipBackend:
 
     # ---- K1 ------------------------------------------------------------------------------------------------------
     def sim_create(self, plan):
+        """a wide plan (SimPlan.wide: more than MCX_MAX_SLOTS one-factor sub-models, or force_wide) goes to mcx_sim_create_wide"""
         out = C.c_void_p()
-        self._check(self.lib.mcx_sim_create(self.h, C.byref(plan.desc), C.byref(out)), "mcx_sim_create")
+        if getattr(plan, "wide", False):
+            self._check(self.lib.mcx_sim_create_wide(self.h, C.byref(plan.desc), C.byref(out)), "mcx_sim_create_wide")
+        else:
+            self._check(self.lib.mcx_sim_create(self.h, C.byref(plan.desc), C.byref(out)), "mcx_sim_create")
         return _Owned(out, self.lib.mcx_sim_destroy, plan)
 
     def sim_describe(self, sim) -> dict:

@@ -55,9 +55,16 @@ class TangentOption(C.Structure):
                 ("numeraire", C.c_double), ("dnum_drate", C.c_double)]
 
 
+def _wide_model(model) -> bool:
+    """more than MCX_MAX_SLOTS sub-models: the wide path kernel serves it, no fused or forward-mode kernel does"""
+    return len(model._slots()) > _abi.MAX_SLOTS
+
+
 def _check_supported(sc):
     from .products.equity import Equity
     from .products.european_option import EuropeanOption
+    if _wide_model(sc.model):
+        raise NotImplementedError("differentiate=True: a wide model (more than MCX_MAX_SLOTS sub-models) has no tangent kernels")
     if not isinstance(sc.model, (BlackScholesModel, HestonModel)):
         raise NotImplementedError("differentiate=True: tangent kernels exist for a single BlackScholesModel or HestonModel")
     if any(m.metric_type != MetricType.PV or not m._native for m in sc.risk_metrics.metrics):
@@ -82,7 +89,7 @@ def run_with_tangents(sc):
     shard = sc.shard_factory()
     model = sc.model
     plan = SimPlan(model, sc.simulation_timeline.numpy(), sc.simulation_scheme, sc.num_steps)
-    sim = be.sim_create(plan)
+    sim = plan.create_sim(be)
     sc.sim_plan = plan
     tl = {float(t): i for i, t in enumerate(sc.simulation_timeline)}
     rate, t_cal = model._pf(2), model.t0()
@@ -379,6 +386,8 @@ def _tangent_book_routes(sc):
     heston_route: it only widens the scheme gate here.)"""
     if sc.requires_higher_order_derivatives:
         raise _NoTangentForm("second order")
+    if _wide_model(sc.model):
+        raise _NoTangentForm("wide model")          # bump-and-revalue; the library would refuse after a wasted base run
     # Schwartz two-factor dual paths serve books that hold a storage; every other book keeps the route it had (no tangent form)
     s2f = hasattr(sc.model, "_cholesky_entries") and hasattr(sc.backend, "tangent_paths_s2f") \
         and all(sp.kind == _abi.MODEL_S2F for sp in sc.model._slots()) \

@@ -1337,7 +1337,7 @@ class SimulationController:
         self._compile_all()
         t1 = time.perf_counter()
         self.sim_plan = SimPlan(self.model, self.simulation_timeline.numpy(), self.simulation_scheme, self.num_steps)
-        self._sim = be.sim_create(self.sim_plan)
+        self._sim = self.sim_plan.create_sim(be)
         if self.requires_regression:
             self._perform_regression(self._shard, self.sim_plan, self._sim)
         self._book_ready()

@@ -33,7 +33,7 @@ class MonteCarloEngine:
         tl = simulation_timeline.detach().cpu().numpy() if isinstance(simulation_timeline, torch.Tensor) \
             else np.asarray(simulation_timeline, dtype=np.float64)
         self.plan = plan if plan is not None else SimPlan(model, tl, simulation_type, num_steps)
-        self.sim = sim if sim is not None else self.backend.sim_create(self.plan)
+        self.sim = sim if sim is not None else self.plan.create_sim(self.backend)
         self.inject_z = None     # tests: replay recorded reference draws, [n_steps][n_z][N]
         self.inject_u = None
 

@@ -167,7 +167,7 @@ class Model:
             if uniforms is None:
                 uniforms = torch.rand(n, 1, dtype=FLOAT)
             u = be.from_numpy(np.ascontiguousarray(uniforms.detach().cpu().numpy().reshape(1, n), dtype=np.float64))
-        sim = be.sim_create(plan)
+        sim = plan.create_sim(be)
         out = be.generate_paths(sim, 0, 0, n, inject_z=z, inject_u=u, init_state=st)                         # [1][D][N]
         return out[0].T.to(state.device).contiguous()
 

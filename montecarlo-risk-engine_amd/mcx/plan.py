@@ -24,18 +24,27 @@ class SimPlan:
     `+ dt` (never snapped to the timeline date); a timeline date with dt <= 0 (the calibration date itself) is stored
     without stepping; models see delta_t = (t_prev + dt) - t_prev while the ANALYTICAL Cholesky factor is keyed on dt."""
 
-    def __init__(self, model, timeline, scheme: SimulationScheme, num_steps: int):
+    def __init__(self, model, timeline, scheme: SimulationScheme, num_steps: int, force_wide: bool = False):
+        """force_wide: send a model of 1 .. 8 one-factor slots down the wide route (mcx_sim_create_wide) — for tests; a model of more
+        than MCX_MAX_SLOTS slots always takes it (`plan.wide`)"""
         if not model._supports_scheme(scheme):
             raise NotImplementedError(f"{type(model).__name__} does not implement the {scheme.name} scheme")
         self.model, self.scheme, self.num_steps = model, scheme, int(num_steps)
         self.timeline = np.asarray(timeline, dtype=np.float64).reshape(-1)
         slots = model._slots()
-        if len(slots) > _abi.MAX_SLOTS:
-            raise ValueError(f"at most {_abi.MAX_SLOTS} sub-models are supported")
+        self.wide = bool(force_wide) or len(slots) > _abi.MAX_SLOTS
+        if self.wide:
+            # the wide path kernel: one lane keeps z[32] and up to 64 state doubles in registers, every slot is a one-factor model
+            if len(slots) > _abi.WIDE_MAX_SLOTS:
+                raise ValueError(f"at most MCX_WIDE_MAX_SLOTS = {_abi.WIDE_MAX_SLOTS} sub-models are supported ({len(slots)} given)")
+            bad = [s for s in slots if s.sim_dim != 1 or s.kind not in _abi.WIDE_KINDS]
+            if bad:
+                raise ValueError(f"a model of more than {_abi.MAX_SLOTS} sub-models (up to MCX_WIDE_MAX_SLOTS = {_abi.WIDE_MAX_SLOTS}) holds "
+                                 f"one-factor sub-models only (model kind {bad[0].kind}, simulation dimension {bad[0].sim_dim})")
         self.n_slots = len(slots)
         self.n_state = sum(s.state_dim for s in slots)
         self.n_z = sum(s.sim_dim for s in slots)
-        if self.n_z > _abi.MAX_Z or self.n_state > _abi.MAX_STATE:
+        if not self.wide and (self.n_z > _abi.MAX_Z or self.n_state > _abi.MAX_STATE):
             raise ValueError("simulation / state dimension exceeds MCX_MAX_Z / MCX_MAX_STATE")
         self.n_uniform = int(getattr(model, "_n_uniform", lambda s: 0)(scheme))
         self.n_dates = len(self.timeline)
@@ -73,30 +82,42 @@ class SimPlan:
         self.init_state = np.array(model._initial_state(), dtype=np.float64)
         self.flags = _abi.FLAG_SMOOTHING if model.perform_smoothing else 0
 
-        d = _abi.SimDesc()
+        d = _abi.WideSimDesc() if self.wide else _abi.SimDesc()
+        if self.wide:
+            self.slot_records = (_abi.Slot * self.n_slots)()
+            d.slots = C.cast(self.slot_records, C.c_void_p)
+        recs = self.slot_records if self.wide else d.slots
         d.scheme, d.n_slots, d.n_state, d.n_z = scheme.value, self.n_slots, self.n_state, self.n_z
         d.n_uniform, d.n_steps, d.n_dates, d.n_chol = self.n_uniform, self.n_steps, self.n_dates, len(chols)
         d.n_initial_store, d.flags = self.n_initial_store, self.flags
         so = zo = 0
         for i, s in enumerate(slots):
-            d.slots[i].kind, d.slots[i].state_off, d.slots[i].z_off, d.slots[i].flags = s.kind, so, zo, s.flags
+            recs[i].kind, recs[i].state_off, recs[i].z_off, recs[i].flags = s.kind, so, zo, s.flags
             for j, v in enumerate(s.params):
-                d.slots[i].p[j] = v
+                recs[i].p[j] = v
             so += s.state_dim
             zo += s.sim_dim
         d.steps, d.chol, d.aux, d.init_state = (_abi.ptr(self.steps), _abi.ptr(self.chol), _abi.ptr(self.aux),
                                                 _abi.ptr(self.init_state))
         self.desc = d                      # keeps pointers into the numpy arrays above (kept alive by self)
 
+    def create_sim(self, backend):
+        """backend.sim_create(self); a wide plan needs a backend whose library has mcx_sim_create_wide (`backend.supports_wide`)"""
+        if self.wide and not getattr(backend, "supports_wide", False):
+            raise ValueError(f"the {getattr(backend, 'name', type(backend).__name__)} backend has no wide path kernel (mcx_sim_create_wide): "
+                             f"a model of {self.n_slots} sub-models" + (" with force_wide" if self.n_slots <= _abi.MAX_SLOTS else "") +
+                             " cannot run on it")
+        return backend.sim_create(self)
+
     @property
     def path_steps_per_path(self) -> int:
         return self.n_steps
 
     @classmethod
-    def single_step(cls, model, scheme: SimulationScheme, t1: float, t2: float) -> "SimPlan":
+    def single_step(cls, model, scheme: SimulationScheme, t1: float, t2: float, force_wide: bool = False) -> "SimPlan":
         """the one sub-step [t1, t2] with an identity Cholesky factor: Model.simulate_time_step_*(time1, time2, state, corr_randn)
         receives normals that are already correlated (model.py:38-48 applies the factor before the step)"""
-        plan = cls(model, np.array([t2]), scheme, 1)
+        plan = cls(model, np.array([t2]), scheme, 1, force_wide=force_wide)
         if plan.n_steps != 1:
             raise ValueError("time2 must lie after the calibration date")
         dt = float(t2) - float(t1)
