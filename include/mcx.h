@@ -126,7 +126,8 @@ typedef struct {
  *     behave as for a narrow sim.
  * The result is the same opaque mcx_sim, marked wide: mcx_generate_paths, mcx_generate_paths_from_state, mcx_sim_describe and
  * mcx_sim_destroy take it; mcx_fused_create, mcx_tangent_european, mcx_tangent_paths, mcx_tangent_paths_chol,
- * mcx_tangent_paths_s2f and mcx_tangent_paths_heston return MCX_E_NOT_FUSABLE (reason in mcx_last_error) and write nothing. */
+ * mcx_tangent_paths_s2f and mcx_tangent_paths_heston return MCX_E_NOT_FUSABLE (reason in mcx_last_error) and write nothing.
+ * Its dual paths come from mcx_tangent_paths_wide, which takes a wide sim ONLY. */
 typedef struct {
     int32_t scheme;
     int32_t n_slots;          /* 1 .. MCX_WIDE_MAX_SLOTS                                              */
@@ -505,6 +506,24 @@ int  mcx_tangent_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot,
 int  mcx_tangent_paths_chol(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
                             const double* h_dchol, uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths,
                             double* d_dpaths, int64_t ld, const double* d_inject_z, void* stream);
+/* The dual paths of a WIDE sim (mcx_sim_create_wide, forced wide included; csrc/kt_wide.hip).  Tables as above with n_slots up to
+ * MCX_WIDE_MAX_SLOTS; h_dchol [n_chol][n_z][n_z][NP] is read under ANALYTICAL only (NULL under EULER).  The sub-models of a wide
+ * model are one-factor and independent given their correlated normal, so the tangent of slot r's state columns is non-zero only
+ * where the tables reach the slot's own numbers: slot r is ACTIVE iff any entry of its h_dslot row, its h_dinit rows, its h_daux rows
+ * over all sub-steps or (ANALYTICAL) row r of h_dchol over all factors is non-zero.  Enqueued on `stream`, in this order: the tables
+ * (staged before anything is written: a call that fails there leaves the outputs untouched as well); the value
+ * image d_paths [T][D][ld] by the primal kernel (the bytes of mcx_generate_paths on the same draws); d_dpaths [NP][T][D][ld] zeroed
+ * (columns 0 .. n_paths-1 of every row: padding stays); ONE launch of kt_paths_wide over (path blocks, active slots) that writes the
+ * tangent images of the active slots' state columns — none when no slot is active; the stream is synchronised.  A block row of slot
+ * r redraws the (r >> 1) + 1 Philox pairs its correlated normal needs: a call costs sum over the active r of that, per path-step.
+ * *n_active_out (nullable): the number of active slots.  -1: a NULL argument (h_dchol under ANALYTICAL included); -2: ld < n_paths;
+ * MCX_E_NOT_FUSABLE with the reason in mcx_last_error: a narrow sim, a scheme other than EULER / ANALYTICAL (QE), a Hull-White slot
+ * (no tangent step exists), ANALYTICAL with a slot other than MCX_MODEL_BS / MCX_MODEL_VASICEK.  Every check comes first: a refused
+ * call enqueues nothing and writes nothing. */
+int  mcx_tangent_paths_wide(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                            const double* h_dchol /* NULL under EULER */, uint64_t seed, uint64_t path_offset, int64_t n_paths,
+                            double* d_paths, double* d_dpaths, int64_t ld, const double* d_inject_z, int32_t* n_active_out /* nullable */,
+                            void* stream);
 /* dual normal equations of (product, regression date): Y = numeraire * sum of the product's cash events with index >=
  * first_event; h_moments [1+NP][(2K-1)+K]: sums of z^k (k < 2K-1) then of z^k Y (k < K), z = (x - shift) * scale */
 int  mcx_tangent_lsm(mcx_handle* h, const mcx_book* book, int32_t product, int32_t first_event, int32_t num_atom, int32_t x_atom,

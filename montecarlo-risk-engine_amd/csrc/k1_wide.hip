@@ -205,6 +205,7 @@ extern "C" int mcx_sim_create_wide(mcx_handle* h, const mcx_wide_sim_desc* d, mc
     sim->d_steps = nullptr; sim->d_chol = nullptr; sim->d_aux = nullptr; sim->d_slots = nullptr; sim->d_init = nullptr;
     sim->n_state_total = d->n_state;
     sim->h_steps.assign(d->steps, d->steps + (d->n_steps > 0 ? d->n_steps : 0));
+    sim->h_slots.assign(d->slots, d->slots + d->n_slots);
     const int ns = d->n_slots;
     const size_t n_steps = (size_t)(d->n_steps > 0 ? d->n_steps : 0);
     hipError_t e = hipMalloc(&sim->d_steps, sizeof(mcx_step) * (n_steps ? n_steps : 1));

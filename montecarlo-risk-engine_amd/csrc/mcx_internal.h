@@ -188,6 +188,7 @@ struct mcx_sim {
     bool wide = false;
     mcx_slot* d_slots = nullptr;   // [desc.n_slots]
     double* d_init = nullptr;      // [desc.n_state]
+    std::vector<mcx_slot> h_slots; // host copy of d_slots (kt_wide.hip checks the kinds and derives the active slots from it)
 };
 // the refusal of the entry points that have no wide form (fused kernels, forward-mode tangents)
 #define MCX_REFUSE_WIDE(h, sim, who)                                                                                          \

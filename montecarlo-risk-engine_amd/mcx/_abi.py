@@ -130,6 +130,10 @@ TANGENT_NP = 4          # MCX_TANGENT_NP: model parameters per forward-mode pass
 TANGENT_LSM_JOB_DTYPE = np.dtype([("product", "<i4"), ("first_event", "<i4"), ("num_atom", "<i4"), ("x_atom", "<i4"),
                                   ("shift", "<f8"), ("scale", "<f8")])
 assert TANGENT_LSM_JOB_DTYPE.itemsize == 32
+# mcx_tangent_paths_wide(h, sim, h_dslot, h_dinit, h_daux, h_dchol, seed, path_offset, n_paths, d_paths, d_dpaths, ld, d_inject_z,
+# n_active_out, stream)
+TANGENT_PATHS_WIDE_ARGTYPES = [C.c_void_p] * 6 + [C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                  C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
 
 # gas storage (include/mcx.h "K6"): mcx_storage_date, mcx_storage_desc, mcx_storage_lsm_date, mcx_storage_op
 STORAGE_DATE_DTYPE = np.dtype([("vmin", "<f8"), ("step", "<f8"), ("next_vmin", "<f8"), ("next_vmax", "<f8"), ("next_scale", "<f8"),

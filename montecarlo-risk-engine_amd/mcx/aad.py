@@ -15,6 +15,8 @@ the ANALYTICAL scheme whose slots are Black-Scholes or Vasicek: there the Choles
 parameters, the models give it in closed form (`Model._analytic_factor_entries`) and mcx_tangent_paths_chol carries its tangent.
 With `SimulationController.tangent_heston` a book under a single HestonModel (EULER or QE, no storage) whose metrics go through
 exposures or exercise takes the same pass on the dual paths of mcx_tangent_paths_heston (`heston_route`).
+With `SimulationController.tangent_wide` a book under 5 to 32 correlated one-factor sub-models takes it on the dual paths of
+mcx_tangent_paths_wide (csrc/kt_wide.hip: one block row per slot the chunk's parameters reach; `wide_route`).
 
 Every other configuration (`run_with_bumps`): sensitivities through the LSM regression — CVA / EPE / PFE greeks, SURVEY §8f
 rank 1, reference test `tests/pytests/test_cva_large_netting_set_aad_vs_fd.py` — are computed by CENTRAL DIFFERENCES WITH
@@ -56,7 +58,8 @@ class TangentOption(C.Structure):
 
 
 def _wide_model(model) -> bool:
-    """more than MCX_MAX_SLOTS sub-models: the wide path kernel serves it, no fused or forward-mode kernel does"""
+    """more than MCX_MAX_SLOTS sub-models: the wide path kernel serves it, no fused kernel does, and in forward mode only
+    mcx_tangent_paths_wide (wide_route)"""
     return len(model._slots()) > _abi.MAX_SLOTS
 
 
@@ -140,10 +143,11 @@ def bump_size(theta: float) -> float:
     return 1e-5 * max(abs(theta), 1e-2)
 
 
-def _clone_controller(sc, model, float32_cache, objects=None):
+def _clone_controller(sc, model, float32_cache, objects=None, force_wide=False):
     """a controller on the same book under `model`.  objects: (netting_sets, risk_metrics) to build it on — a private deep copy by
     default; the bumped controllers of one differentiation run one after the other and share ONE copy (a run only reassigns the
-    regression coefficients it produces; copying the product graph was 12 ms per controller)"""
+    regression coefficients it produces; copying the product graph was 12 ms per controller).  force_wide: the clone builds its
+    SimPlan with force_wide=True (the base controller of a forward-mode pass on the wide route, for a model of 5 to 8 slots)"""
     import copy
     from .controller.controller import SimulationController
     ns, rm = objects if objects is not None else (copy.deepcopy(sc.netting_sets), copy.deepcopy(sc.risk_metrics))
@@ -153,6 +157,7 @@ def _clone_controller(sc, model, float32_cache, objects=None):
     for attr in ("seed_offset", "allow_fused", "main_plan", "materialize", "_inject", "date_batched_lsm"):
         setattr(clone, attr, getattr(sc, attr))
     clone.reference_float32_cf_cache = float32_cache
+    clone._force_wide_plan = bool(force_wide)
     return clone
 
 
@@ -365,7 +370,9 @@ def no_tangent_form(e) -> bool:
 # of one differentiation reads; _Chunk: one group of <= TANGENT_NP parameters, their indices `sel` and their zero-padded descriptor
 # tangents; _Presim: the dual pre-simulation of a chunk and the coefficient images its regression fills; _Images: the main pass.
 # dpayoff: tangent_payoffs only; heston: the book's dual paths come from mcx_tangent_paths_heston (heston_route)
-_BookPass = namedtuple("_BookPass", "sc base be shard s2f chol batched rows base_coeffs dpayoff heston", defaults=(None, False))
+# wide: the book's dual paths come from mcx_tangent_paths_wide (wide_route); active: {first parameter of a chunk: its active slots}
+_BookPass = namedtuple("_BookPass", "sc base be shard s2f chol batched rows base_coeffs dpayoff heston wide active",
+                       defaults=(None, False, False, None))
 _Chunk = namedtuple("_Chunk", "sel dslot dinit daux dchol datoms")
 _Presim = namedtuple("_Presim", "x_range paths dpaths n coeffs dcoeffs")
 _Images = namedtuple("_Images", "paths dpaths cfs expo")
@@ -380,13 +387,57 @@ def heston_route(sc) -> bool:
         and not any(getattr(p, "is_storage", False) for p in sc.products)
 
 
+TANGENT_MAX_SLOTS = 4          # slots the narrow dual path kernels are instantiated for (csrc/kt_book.hip ktp_paths)
+
+
+def wide_route(sc) -> bool:
+    """Host only: do the book's dual paths come from mcx_tangent_paths_wide (csrc/kt_wide.hip kt_paths_wide: one block row per
+    ACTIVE slot)?  Only with SimulationController.tangent_wide on a backend with the binding, for a model of more than
+    TANGENT_MAX_SLOTS slots (5 to 8 slots: the pass forces the base controller's plan wide; 9 to 32: it is wide already) whose
+    every slot is one-factor with a kind the kernel serves under the scheme — EULER: Black-Scholes, Vasicek, CIR++ (stochastic and
+    deterministic); ANALYTICAL: Black-Scholes and Vasicek with the factor in closed form — and a book without a storage.  A
+    Hull-White slot makes it False: that book is bumped (a wide one without a wasted base run)."""
+    if not getattr(sc, "tangent_wide", False) or not hasattr(sc.backend, "tangent_paths_wide"):
+        return False
+    slots = sc.model._slots()
+    if not TANGENT_MAX_SLOTS < len(slots) <= _abi.WIDE_MAX_SLOTS:
+        return False
+    scheme = sc.simulation_scheme.name
+    if scheme == "EULER":
+        kinds = (_abi.MODEL_BS, _abi.MODEL_VASICEK, _abi.MODEL_CIRPP, _abi.MODEL_CIRPP_DET)
+    elif scheme == "ANALYTICAL" and _analytic_factor_form(sc.model, sc.simulation_scheme):
+        kinds = (_abi.MODEL_BS, _abi.MODEL_VASICEK)
+    else:
+        return False
+    return all(sp.sim_dim == 1 and sp.kind in kinds for sp in slots) \
+        and not any(getattr(p, "is_storage", False) for p in sc.products)
+
+
+def active_slots(plan, dslot, dinit, daux, dchol=None) -> list:
+    """Host only: the slots mcx_tangent_paths_wide launches a block row for, ascending — slot r is active iff any entry of its dslot
+    row, its dinit rows, its daux rows over all sub-steps or (dchol given: ANALYTICAL) row r of dchol over all factors is non-zero.
+    plan: anything with the slots' state offsets and dimensions (`slot_states`: [(state_off, state_dim)]), or a SimPlan"""
+    states = getattr(plan, "slot_states", None)
+    if states is None:
+        offs = np.cumsum([0] + [sp.state_dim for sp in plan.model._slots()])
+        states = [(int(offs[s]), int(sp.state_dim)) for s, sp in enumerate(plan.model._slots())]
+    out = []
+    for r, (c, dim) in enumerate(states):
+        on = np.any(dslot[r] != 0) or np.any(dinit[c:c + dim] != 0) or np.any(daux[:, r] != 0)
+        if not on and dchol is not None:
+            on = np.any(dchol[:, r] != 0)
+        if on:
+            out.append(r)
+    return out
+
+
 def _tangent_book_routes(sc):
     """Host only: every gate that holds before any GPU work, in the order their reasons are reported.  -> (s2f, chol, batched):
     which dual path kernel serves the book, and whether the stateless products' regression is batched.  (The Heston route is
     heston_route: it only widens the scheme gate here.)"""
     if sc.requires_higher_order_derivatives:
         raise _NoTangentForm("second order")
-    if _wide_model(sc.model):
+    if _wide_model(sc.model) and not wide_route(sc):
         raise _NoTangentForm("wide model")          # bump-and-revalue; the library would refuse after a wasted base run
     # Schwartz two-factor dual paths serve books that hold a storage; every other book keeps the route it had (no tangent form)
     s2f = hasattr(sc.model, "_cholesky_entries") and hasattr(sc.backend, "tangent_paths_s2f") \
@@ -510,7 +561,7 @@ def payoff_forms_armed(sc, be) -> bool:
     so such a book keeps the library's refusal, and with it the NotImplementedError of storage books"""
     return bool(getattr(sc, "tangent_payoffs", False)) and hasattr(be, "book_set_payoff_tangents") \
         and not any(getattr(p, "is_storage", False) for p in sc.products) \
-        and not heston_route(sc)             # the payoff forms on Heston dual paths: not compared either
+        and not heston_route(sc) and not wide_route(sc)      # the payoff forms on Heston / wide dual paths: not compared either
 
 
 def pad_chunk(a, sel):
@@ -520,7 +571,7 @@ def pad_chunk(a, sel):
 
 def _parameter_chunk(ctx, dd, sel):
     """the padded descriptor tangents of the parameters `sel`; the atoms' go to the device, the factors' only where a route reads them"""
-    dchol = pad_chunk(dd["chol"], sel) if ctx.s2f or ctx.chol or ctx.heston else None
+    dchol = pad_chunk(dd["chol"], sel) if ctx.s2f or ctx.chol or ctx.heston or (ctx.wide and "chol" in dd) else None
     return _Chunk(sel, pad_chunk(dd["slots"], sel), pad_chunk(dd["init"], sel), pad_chunk(dd["aux"], sel), dchol,
                   ctx.be.from_numpy(pad_chunk(dd["atoms"], sel)))
 
@@ -529,6 +580,9 @@ def _dual_paths(ctx, chunk, seed, off, n, inject_z, inject_u=None):
     """GPU: (paths, dpaths) of n paths from path `off` on, through the dual path kernel of the book's route.  inject_u: the injected
     uniforms of the same simulation (pre-simulation or main), which only the Heston QE step consumes"""
     be, sim, c = ctx.be, ctx.base._sim, chunk
+    if ctx.wide:                              # (pre-simulation and main pass of a chunk have the same active slots)
+        paths, dpaths, ctx.active[c.sel[0]] = be.tangent_paths_wide(sim, c.dslot, c.dinit, c.daux, c.dchol, seed, off, n, inject_z)
+        return paths, dpaths
     if ctx.heston:
         return be.tangent_paths_heston(sim, c.dslot, c.dinit, c.daux, c.dchol, seed, off, n, inject_z, inject_u)
     if ctx.s2f:
@@ -757,7 +811,10 @@ def run_with_tangent_book(sc):
     t0 = time.perf_counter()
     be, shard = sc.backend, sc.shard_factory()
     NP = _abi.TANGENT_NP
-    base = _clone_controller(sc, sc.model, sc.reference_float32_cf_cache)
+    # the wide route: a model of 5 to 8 slots has no narrow dual path kernel, so the base controller's plan is forced wide (the
+    # paths are the narrow kernel's bit for bit, but the book then runs unfused); a model of more than 8 slots is wide already
+    wide = wide_route(sc)
+    base = _clone_controller(sc, sc.model, sc.reference_float32_cf_cache, force_wide=wide and not _wide_model(sc.model))
     res0 = base.run_simulation()
     if base.book_plan.n_basis > 4:
         raise _NoTangentForm("basis")
@@ -778,7 +835,7 @@ def run_with_tangent_book(sc):
     dpayoff = None
     if payoff_forms_armed(sc, be):
         dpayoff = payoff_tangents(base, sc.model, getattr(sc.model, "perform_smoothing", False))
-    ctx = _BookPass(sc, base, be, shard, s2f, chol, batched, rows, base_coeffs, dpayoff, heston_route(sc))
+    ctx = _BookPass(sc, base, be, shard, s2f, chol, batched, rows, base_coeffs, dpayoff, heston_route(sc), wide, {})
     n_batched = 0
     try:
         for c0 in range(0, P, NP):
@@ -803,6 +860,8 @@ def run_with_tangent_book(sc):
     sc.timings = dict(total=time.perf_counter() - t0, tangent=True, forward_mode_passes=(P + NP - 1) // NP,
                       base_run_and_descriptor_derivatives=t_desc, presim_and_regression=t_pre, main=t_main,
                       batched_lsm_jobs=n_batched)
+    if wide:
+        sc.timings["wide_active_slots"] = [ctx.active[c0] for c0 in range(0, P, NP)]
     g = [[[tuple(ev) for ev in per_metric] for per_metric in per_ns] for per_ns in grads]
     return sc._package([[[tuple(v) for v in evals] for evals in per_metric] for per_metric in res0.results], g, [])
 

@@ -288,6 +288,13 @@ class SimulationController:
         # exposures or exercise through the forward-mode book pass on mcx_tangent_paths_heston (mcx/aad.py heston_route); False: such
         # a book keeps bump-and-revalue.  European PV books go to the fused tangent kernel either way
         self.tangent_heston = False
+        # differentiate=True: True sends a book under a model of 5 to 32 one-factor sub-models (Black-Scholes, Vasicek, CIR++ under
+        # EULER; Black-Scholes, Vasicek under ANALYTICAL; no Hull-White slot, no storage) through the forward-mode book pass on
+        # mcx_tangent_paths_wide (mcx/aad.py wide_route); False: such a book keeps bump-and-revalue.  Turning it on is this one line;
+        # a model of 5 to 8 slots then runs its base pass on a forced-wide plan, i.e. unfused.  Never armed together with
+        # tangent_payoffs (aad.payoff_forms_armed)
+        self.tangent_wide = False
+        self._force_wide_plan = False    # set by aad._clone_controller only: build the SimPlan with force_wide=True
         # The reference compiles nothing: every run_simulation() sees the current state of its products / metrics.  Re-using the
         # compiled descriptors and the uploaded book of the previous run is an opt-in for callers that re-run an UNCHANGED
         # controller (bench.py, tools/run_configs.py); invalidate() drops the cache after a mutation.
@@ -1336,7 +1343,8 @@ class SimulationController:
         t0 = time.perf_counter()
         self._compile_all()
         t1 = time.perf_counter()
-        self.sim_plan = SimPlan(self.model, self.simulation_timeline.numpy(), self.simulation_scheme, self.num_steps)
+        self.sim_plan = SimPlan(self.model, self.simulation_timeline.numpy(), self.simulation_scheme, self.num_steps,
+                                force_wide=self._force_wide_plan)
         self._sim = self.sim_plan.create_sim(be)
         if self.requires_regression:
             self._perform_regression(self._shard, self.sim_plan, self._sim)
