@@ -524,6 +524,18 @@ int  mcx_tangent_paths_wide(mcx_handle* h, const mcx_sim* sim, const double* h_d
                             const double* h_dchol /* NULL under EULER */, uint64_t seed, uint64_t path_offset, int64_t n_paths,
                             double* d_paths, double* d_dpaths, int64_t ld, const double* d_inject_z, int32_t* n_active_out /* nullable */,
                             void* stream);
+/* mcx_tangent_paths_wide that also takes MCX_MODEL_HW slots: under EULER next to Black-Scholes, Vasicek and the two CIR++ kinds,
+ * under ANALYTICAL next to Black-Scholes and Vasicek.  The Hull-White dual steps are the primal's (state [r, log B]):
+ *   EULER       log B += r dt;  r' = r + (theta_k - a r) dt + sigma (sqrt(dt) zc),  theta_k = aux[0] with tangent h_daux, a = p[3],
+ *               sigma = p[1] with tangents h_dslot;
+ *   ANALYTICAL  log B += r dt;  r' = r E + shift + zc,  E = aux[0], shift = aux[1] with tangents h_daux, zc with row r of h_dchol.
+ * A sim that holds a Hull-White slot runs a second instantiation of kt_paths_wide that has these steps; a sim without one runs the
+ * kernel of mcx_tangent_paths_wide and gets its bytes.  Arguments, order of work, active slots and every other refusal (a narrow
+ * sim, QE, NULL h_dchol under ANALYTICAL, ld < n_paths, a kind without a step) are mcx_tangent_paths_wide's, checked by the same code. */
+int  mcx_tangent_paths_wide_hw(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                               const double* h_dchol /* NULL under EULER */, uint64_t seed, uint64_t path_offset, int64_t n_paths,
+                               double* d_paths, double* d_dpaths, int64_t ld, const double* d_inject_z, int32_t* n_active_out /* nullable */,
+                               void* stream);
 /* dual normal equations of (product, regression date): Y = numeraire * sum of the product's cash events with index >=
  * first_event; h_moments [1+NP][(2K-1)+K]: sums of z^k (k < 2K-1) then of z^k Y (k < K), z = (x - shift) * scale */
 int  mcx_tangent_lsm(mcx_handle* h, const mcx_book* book, int32_t product, int32_t first_event, int32_t num_atom, int32_t x_atom,

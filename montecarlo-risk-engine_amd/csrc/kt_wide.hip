@@ -18,7 +18,9 @@
 //   * ANALYTICAL: zc is a dual number, the factor's row r carries its tangent (ktp_fma of kt_book.hip); EULER: a plain double (the
 //     correlations are not model parameters);
 //   * the dual step of the slot's kind — the four EULER cases of kt_paths, the two ANALYTICAL cases of kt_paths_chol, RESTATED (sharing
-//     them through a header would have to leave every kernel of kt_book.hip with its register allocation);
+//     them through a header would have to leave every kernel of kt_book.hip with its register allocation); the two Hull-White steps
+//     (no narrow kernel has them) only in the instantiations with HW = true, which mcx_tangent_paths_wide_hw launches for a sim
+//     that holds a Hull-White slot: the plain instantiations keep the instruction stream they had without them;
 //   * only the TANGENT images of the slot's state columns are written (c, and c + 1 unless Black-Scholes: wide_store's placement).  The
 //     value image is the primal kernel's (mcx_wide_generate), so image 0 is K1's bytes; the columns of inactive slots stay at the
 //     zero the entry point's memset wrote.
@@ -78,7 +80,9 @@ __device__ __forceinline__ void ktw_store(const KTWArgs& a, int t, int col, int6
     for (int q = 0; q < NP; ++q) a.dpaths[q * a.pstride + off] = x.d[q];
 }
 
-template <bool INJECT>
+// HW: the instantiation that also holds the two Hull-White dual steps (mcx_tangent_paths_wide_hw launches it for a sim with a
+// Hull-White slot, and only for such a sim); without it the kernel is the one it was before those steps existed
+template <bool INJECT, bool HW>
 __global__ __launch_bounds__(MCX_BLOCK) void kt_paths_wide(const KTWArgs a)
 {
     __shared__ double bm_lds[INJECT ? 2 : MCX_BM_LDS_DOUBLES];
@@ -168,11 +172,24 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_paths_wide(const KTWArgs a)
                 s0 = ld_dual(ldk(ax + 1), dax + 1 * NP);
                 break;
             }
-            default: break;                                               // (the entry point refuses every other kind)
+            default:
+                if (HW && kind == MCX_MODEL_HW) {                         // mcx_device.h case MCX_MODEL_HW in dual numbers; theta_k = aux[0]
+                    const DN sigma = ld_dual(ldk(p + 1), dp + 1 * NP), speed = ld_dual(ldk(p + 3), dp + 3 * NP);
+                    const DN theta = ld_dual(ldk(ax + 0), dax + 0 * NP);
+                    const DN x = s0;
+                    s1 = s1 + x * dt;
+                    s0 = x + (theta - speed * x) * dt + sigma * (sq * zv);
+                }
+                break;                                                    // (the entry point refuses every other kind)
             }
         } else if (bs) {                                                  // black_scholes.py:61-67
             const DN drift = ld_dual(ldk(ax + 0), dax + 0 * NP), ito = ld_dual(ldk(ax + 1), dax + 1 * NP);
             s0 = s0 * dexp(drift + (zd - ito));
+        } else if (HW && kind == MCX_MODEL_HW) {                          // r' = r E + shift + w, hull_white.py _step_aux
+            const DN decay = ld_dual(ldk(ax + 0), dax + 0 * NP), shift = ld_dual(ldk(ax + 1), dax + 1 * NP);
+            const DN x = s0;
+            s1 = s1 + x * dt;
+            s0 = (x * decay + shift) + zd;
         } else {                                                          // MCX_MODEL_VASICEK, vasicek.py:76-86
             const DN mean = ld_dual(ldk(p + 2), dp + 2 * NP), decay = ld_dual(ldk(ax + 0), dax + 0 * NP);
             const DN x = s0;
@@ -195,14 +212,12 @@ bool ktw_any(const double* v, size_t n)
     return false;
 }
 
-}  // namespace
-
+// mcx_tangent_paths_wide and mcx_tangent_paths_wide_hw.  allow_hw: the latter, which also takes Hull-White slots under both schemes.
 // Every check comes before the first upload: a refused call enqueues nothing and writes nothing.
-extern "C" int mcx_tangent_paths_wide(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
-                                      const double* h_dchol, uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths,
-                                      double* d_dpaths, int64_t ld, const double* d_inject_z, int32_t* n_active_out, void* stream)
+int ktw_tangent_paths_wide(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                           const double* h_dchol, uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths, double* d_dpaths,
+                           int64_t ld, const double* d_inject_z, int32_t* n_active_out, void* stream, const char* who, bool allow_hw)
 {
-    const char* who = "mcx_tangent_paths_wide";
     if (!h || !sim || !h_dslot || !h_dinit || !h_daux || !d_paths || !d_dpaths) return -1;
     if (!sim->wide)
         MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: a narrow sim (mcx_sim_create) goes to mcx_tangent_paths / mcx_tangent_paths_chol; this entry "
@@ -219,8 +234,13 @@ extern "C" int mcx_tangent_paths_wide(mcx_handle* h, const mcx_sim* sim, const d
     const int ns = sd.n_slots;
     if (ns < 1 || ns > MCX_WIDE_MAX_SLOTS || sd.n_z != ns || (int)sim->h_slots.size() != ns)
         MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: one normal per slot and 1 .. %d slots expected", who, MCX_WIDE_MAX_SLOTS);
+    bool has_hw = false;
     for (int s = 0; s < ns; ++s) {
         const int kd = sim->h_slots[s].kind;
+        if (allow_hw && kd == MCX_MODEL_HW) {
+            has_hw = true;
+            continue;
+        }
         if (analytic) {
             if (kd != MCX_MODEL_BS && kd != MCX_MODEL_VASICEK)
                 MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: slot %d: model kind %d has no analytic tangent step", who, s, kd);
@@ -272,11 +292,33 @@ extern "C" int mcx_tangent_paths_wide(mcx_handle* h, const mcx_sim* sim, const d
         a.seed = seed; a.path_offset = path_offset;
         a.scheme = sd.scheme; a.n_steps = sd.n_steps; a.n_state = sd.n_state; a.n_slots = ns; a.n_initial_store = sd.n_initial_store;
         const dim3 grid((unsigned)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK), (unsigned)n_active);
-        if (d_inject_z) hipLaunchKernelGGL((kt_paths_wide<true>), grid, dim3(MCX_BLOCK), 0, s, a);
-        else hipLaunchKernelGGL((kt_paths_wide<false>), grid, dim3(MCX_BLOCK), 0, s, a);
+        if (has_hw) {
+            if (d_inject_z) hipLaunchKernelGGL((kt_paths_wide<true, true>), grid, dim3(MCX_BLOCK), 0, s, a);
+            else hipLaunchKernelGGL((kt_paths_wide<false, true>), grid, dim3(MCX_BLOCK), 0, s, a);
+        } else if (d_inject_z) hipLaunchKernelGGL((kt_paths_wide<true, false>), grid, dim3(MCX_BLOCK), 0, s, a);
+        else hipLaunchKernelGGL((kt_paths_wide<false, false>), grid, dim3(MCX_BLOCK), 0, s, a);
         MCX_HIP(h, hipGetLastError());
     }
     MCX_HIP(h, hipStreamSynchronize(s));
     if (n_active_out) *n_active_out = n_active;
     return 0;
+}
+
+}  // namespace
+
+extern "C" int mcx_tangent_paths_wide(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                                      const double* h_dchol, uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths,
+                                      double* d_dpaths, int64_t ld, const double* d_inject_z, int32_t* n_active_out, void* stream)
+{
+    return ktw_tangent_paths_wide(h, sim, h_dslot, h_dinit, h_daux, h_dchol, seed, path_offset, n_paths, d_paths, d_dpaths, ld, d_inject_z,
+                                  n_active_out, stream, "mcx_tangent_paths_wide", false);
+}
+
+// mcx_tangent_paths_wide that also takes Hull-White slots (EULER and ANALYTICAL); on a sim without one it is mcx_tangent_paths_wide
+extern "C" int mcx_tangent_paths_wide_hw(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                                         const double* h_dchol, uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths,
+                                         double* d_dpaths, int64_t ld, const double* d_inject_z, int32_t* n_active_out, void* stream)
+{
+    return ktw_tangent_paths_wide(h, sim, h_dslot, h_dinit, h_daux, h_dchol, seed, path_offset, n_paths, d_paths, d_dpaths, ld, d_inject_z,
+                                  n_active_out, stream, "mcx_tangent_paths_wide_hw", true);
 }

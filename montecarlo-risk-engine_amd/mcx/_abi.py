@@ -131,7 +131,7 @@ TANGENT_LSM_JOB_DTYPE = np.dtype([("product", "<i4"), ("first_event", "<i4"), ("
                                   ("shift", "<f8"), ("scale", "<f8")])
 assert TANGENT_LSM_JOB_DTYPE.itemsize == 32
 # mcx_tangent_paths_wide(h, sim, h_dslot, h_dinit, h_daux, h_dchol, seed, path_offset, n_paths, d_paths, d_dpaths, ld, d_inject_z,
-# n_active_out, stream)
+# n_active_out, stream); mcx_tangent_paths_wide_hw takes the same list
 TANGENT_PATHS_WIDE_ARGTYPES = [C.c_void_p] * 6 + [C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                                   C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
 

@@ -28,7 +28,7 @@ _EXPORTS = [
     "mcx_value_poly_fit", "mcx_book_collapse_values", "mcx_book_value_poly_info", "mcx_rows_minmax",
     "mcx_storage_create", "mcx_storage_destroy", "mcx_storage_lsm_step", "mcx_storage_lsm_run", "mcx_storage_eval",
     "mcx_storage_lsm_step_batch", "mcx_storage_lsm_solve_batch", "mcx_storage_lsm_run_batch",
-    "mcx_tangent_storage_lsm_step", "mcx_tangent_storage_eval", "mcx_tangent_paths_s2f", "mcx_tangent_paths_heston", "mcx_tangent_paths_wide",
+    "mcx_tangent_storage_lsm_step", "mcx_tangent_storage_eval", "mcx_tangent_paths_s2f", "mcx_tangent_paths_heston", "mcx_tangent_paths_wide", "mcx_tangent_paths_wide_hw",
     "mcx_reduce_vector", "mcx_reduce_profiles", "mcx_reduce_cva", "mcx_unsecured", "mcx_select_hist", "mcx_select_hist_dev", "mcx_select_narrow", "mcx_select_bracket", "mcx_select_hist_rows",
 ]
 
@@ -74,7 +74,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_tangent_paths_s2f.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_tangent_paths_chol.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_tangent_paths_heston.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp, vp]
-    lib.mcx_tangent_paths_wide.argtypes = _abi.TANGENT_PATHS_WIDE_ARGTYPES
+    lib.mcx_tangent_paths_wide.argtypes = lib.mcx_tangent_paths_wide_hw.argtypes = _abi.TANGENT_PATHS_WIDE_ARGTYPES
     lib.mcx_sim_describe.argtypes = [C.c_void_p, C.c_void_p]
     lib.mcx_sim_create_wide.argtypes = [vp, vp, vp]
     lib.mcx_fused_num_records.argtypes = [C.c_void_p]
@@ -499,7 +499,8 @@ class HipBackend:
         return paths, dpaths
 
     def tangent_paths_wide(self, sim, dslot: np.ndarray, dinit: np.ndarray, daux: np.ndarray, dchol: np.ndarray | None, seed: int,
-                           path_offset: int, n_paths: int, inject_z=None, out=None, ld: int | None = None):
+                           path_offset: int, n_paths: int, inject_z=None, out=None, ld: int | None = None,
+                           entry: str = "mcx_tangent_paths_wide"):
         """the dual paths of a WIDE sim (mcx_tangent_paths_wide, csrc/kt_wide.hip): the arguments of tangent_paths_chol with up to
         MCX_WIDE_MAX_SLOTS slots; dchol is read under ANALYTICAL only.  The value image is the primal path kernel's, the tangent images
         are zero except in the state columns of the ACTIVE slots (those a non-zero table entry reaches).
@@ -515,11 +516,18 @@ class HipBackend:
             dchol = np.ascontiguousarray(dchol, dtype=np.float64)
             assert dchol.shape == (len(plan.chol), plan.n_z, plan.n_z, NP)
         n_active = C.c_int32(-1)
-        self._check(self.lib.mcx_tangent_paths_wide(
+        self._check(getattr(self.lib, entry)(
             self.h, sim.ptr, _abi.ptr(a[0]), _abi.ptr(a[1]), _abi.ptr(a[2]), _abi.ptr(dchol) if dchol is not None else None, seed,
             path_offset, n_paths, paths.data_ptr(), dpaths.data_ptr(), n_paths if ld is None else ld,
-            inject_z.data_ptr() if inject_z is not None else None, C.byref(n_active), self._stream()), "mcx_tangent_paths_wide")
+            inject_z.data_ptr() if inject_z is not None else None, C.byref(n_active), self._stream()), entry)
         return paths, dpaths, int(n_active.value)
+
+    def tangent_paths_wide_hw(self, sim, dslot, dinit, daux, dchol, seed: int, path_offset: int, n_paths: int, inject_z=None, out=None,
+                              ld: int | None = None):
+        """tangent_paths_wide through mcx_tangent_paths_wide_hw: Hull-White slots are served too (EULER and ANALYTICAL); a sim
+        without one gets the bytes of tangent_paths_wide"""
+        return self.tangent_paths_wide(sim, dslot, dinit, daux, dchol, seed, path_offset, n_paths, inject_z, out, ld,
+                                       entry="mcx_tangent_paths_wide_hw")
 
     def tangent_paths_heston(self, sim, dslot: np.ndarray, dinit: np.ndarray, daux: np.ndarray, dchol: np.ndarray | None, seed: int,
                              path_offset: int, n_paths: int, inject_z=None, inject_u=None, out=None, ld: int | None = None):

@@ -17,6 +17,9 @@ With `SimulationController.tangent_heston` a book under a single HestonModel (EU
 exposures or exercise takes the same pass on the dual paths of mcx_tangent_paths_heston (`heston_route`).
 With `SimulationController.tangent_wide` a book under 5 to 32 correlated one-factor sub-models takes it on the dual paths of
 mcx_tangent_paths_wide (csrc/kt_wide.hip: one block row per slot the chunk's parameters reach; `wide_route`).
+With `SimulationController.tangent_hull_white` a book under 1 to 32 one-factor sub-models of which at least one is Hull-White takes it
+on the dual paths of mcx_tangent_paths_wide_hw (`hull_white_route`), in passes over the LIVE parameters only: a curve node beyond the
+book's horizon reaches no descriptor number, its rows are exact zeros without a pass.
 
 Every other configuration (`run_with_bumps`): sensitivities through the LSM regression — CVA / EPE / PFE greeks, SURVEY §8f
 rank 1, reference test `tests/pytests/test_cva_large_netting_set_aad_vs_fd.py` — are computed by CENTRAL DIFFERENCES WITH
@@ -229,11 +232,12 @@ class _NoTangentForm(Exception):
     pass
 
 
-def _host_descriptors(sc, model=None, dtype=np.float64):
+def _host_descriptors(sc, model=None, dtype=np.float64, factor=False):
     """every host-computed number the kernels consume (slot parameters, initial state, per-step tables, atom coefficients) of a
     COMPILED controller, re-evaluated under `model` (default: its own) WITHOUT touching the GPU.  Only the model-dependent
     numbers are recomputed: the per-step tables of the existing sub-step schedule and the closed-form coefficients of the
-    existing atoms (requests, events and terms do not depend on the model parameters)."""
+    existing atoms (requests, events and terms do not depend on the model parameters).  factor: under ANALYTICAL the closed-form factor
+    block also for a model whose slots the narrow dual path kernels do not all serve (hull_white_route: a Hull-White slot)."""
     model = sc.model if model is None else model
     sim, comp = sc.sim_plan, sc._comp
     specs = model._slots()
@@ -258,7 +262,7 @@ def _host_descriptors(sc, model=None, dtype=np.float64):
     out = dict(slots=slots, init=np.array(model._initial_state(), dtype=dtype), aux=aux, atoms=atoms)
     if hasattr(model, "_cholesky_entries"):          # factors that depend on the parameters (a correlation that is one of them)
         out["chol"] = np.array([model._cholesky_entries(sim.scheme, dt) for dt in sim.chol_dt], dtype=dtype).reshape(len(sim.chol_dt), sim.n_z, sim.n_z)
-    elif _analytic_factor_form(model, sim.scheme):   # ANALYTICAL: the factor of the per-dt covariance (volatilities, mean reversion)
+    elif _analytic_factor_form(model, sim.scheme) or (factor and sim.scheme.name == "ANALYTICAL"):   # ANALYTICAL: the factor of the per-dt covariance (volatilities, mean reversion)
         out["chol"] = np.array([model._analytic_factor_entries(dt) for dt in sim.chol_dt], dtype=dtype).reshape(len(sim.chol_dt), sim.n_z, sim.n_z)
     return out, shape
 
@@ -413,6 +417,41 @@ def wide_route(sc) -> bool:
         and not any(getattr(p, "is_storage", False) for p in sc.products)
 
 
+def hull_white_route(sc) -> bool:
+    """Host only: do the book's dual paths come from mcx_tangent_paths_wide_hw (csrc/kt_wide.hip kt_paths_wide<., true>: the per-slot
+    kernel with the two Hull-White dual steps)?  Only with SimulationController.tangent_hull_white on a backend with the binding, for
+    a model of 1 to WIDE_MAX_SLOTS slots of which at least one is Hull-White, whose every slot is one-factor with a kind the entry
+    serves under the scheme — EULER: Black-Scholes, Vasicek, Hull-White, CIR++ (stochastic and deterministic); ANALYTICAL:
+    Black-Scholes, Vasicek and Hull-White with the factor in closed form, in practice a single Hull-White model (ModelConfig
+    assembles mixed families for Black-Scholes pairs only) — and a book without a storage.  A model without a Hull-White slot is
+    never touched by the flag.  A model of 8 slots or fewer runs its base pass on a forced-wide plan, as on wide_route."""
+    if not getattr(sc, "tangent_hull_white", False) or not hasattr(sc.backend, "tangent_paths_wide_hw"):
+        return False
+    slots = sc.model._slots()
+    if not 1 <= len(slots) <= _abi.WIDE_MAX_SLOTS or not any(sp.kind == _abi.MODEL_HW for sp in slots):
+        return False
+    scheme = sc.simulation_scheme.name
+    if scheme == "EULER":
+        kinds = (_abi.MODEL_BS, _abi.MODEL_VASICEK, _abi.MODEL_HW, _abi.MODEL_CIRPP, _abi.MODEL_CIRPP_DET)
+    elif scheme == "ANALYTICAL":
+        entries = getattr(sc.model, "_analytic_factor_entries", None)
+        if entries is None or entries(1.0) is None:
+            return False
+        kinds = (_abi.MODEL_BS, _abi.MODEL_VASICEK, _abi.MODEL_HW)
+    else:
+        return False
+    return all(sp.sim_dim == 1 and sp.kind in kinds for sp in slots) \
+        and not any(getattr(p, "is_storage", False) for p in sc.products)
+
+
+def live_parameters(dd) -> list:
+    """Host only: the parameters some descriptor tangent block of `dd` (descriptor_tangents: [...][P]) is non-zero for, ascending.
+    Every other parameter reaches no number a kernel reads: its sensitivities are exact zeros without a pass (hull_white_route: the
+    curve nodes beyond the book's horizon)"""
+    P = next(iter(dd.values())).shape[-1]
+    return [j for j in range(P) if any(np.any(v[..., j] != 0) for v in dd.values())]
+
+
 def active_slots(plan, dslot, dinit, daux, dchol=None) -> list:
     """Host only: the slots mcx_tangent_paths_wide launches a block row for, ascending — slot r is active iff any entry of its dslot
     row, its dinit rows, its daux rows over all sub-steps or (dchol given: ANALYTICAL) row r of dchol over all factors is non-zero.
@@ -437,7 +476,7 @@ def _tangent_book_routes(sc):
     heston_route: it only widens the scheme gate here.)"""
     if sc.requires_higher_order_derivatives:
         raise _NoTangentForm("second order")
-    if _wide_model(sc.model) and not wide_route(sc):
+    if _wide_model(sc.model) and not wide_route(sc) and not hull_white_route(sc):
         raise _NoTangentForm("wide model")          # bump-and-revalue; the library would refuse after a wasted base run
     # Schwartz two-factor dual paths serve books that hold a storage; every other book keeps the route it had (no tangent form)
     s2f = hasattr(sc.model, "_cholesky_entries") and hasattr(sc.backend, "tangent_paths_s2f") \
@@ -446,7 +485,8 @@ def _tangent_book_routes(sc):
     # ANALYTICAL: the factor of the per-dt covariance depends on the parameters; mcx_tangent_paths_chol carries its tangent for
     # Black-Scholes and Vasicek slots whose models give it in closed form
     chol = not s2f and hasattr(sc.backend, "tangent_paths_chol") and _analytic_factor_form(sc.model, sc.simulation_scheme)
-    if sc.simulation_scheme.name != "EULER" and not (s2f and sc.simulation_scheme.name == "ANALYTICAL") and not chol and not heston_route(sc):
+    if sc.simulation_scheme.name != "EULER" and not (s2f and sc.simulation_scheme.name == "ANALYTICAL") and not chol and not heston_route(sc) \
+            and not hull_white_route(sc):
         raise _NoTangentForm("scheme")
     if any(m.metric_type not in _SCATTER or not m._native for m in sc.risk_metrics.metrics):
         raise _NoTangentForm("metric")
@@ -458,7 +498,7 @@ def _tangent_book_routes(sc):
     return s2f, chol, batched
 
 
-def _descriptors_like(base, model, smoothing, shape0, dtype=np.float64, complex_step=None, bump=None):
+def _descriptors_like(base, model, smoothing, shape0, dtype=np.float64, complex_step=None, bump=None, factor=False):
     """the host descriptors of `base` under a copy of `model` at theta_j + i h (complex_step: (j, h)) or with theta_j replaced
     (bump: (j, value)); the copy must keep the descriptor structure `shape0`"""
     m = copy.deepcopy(model)
@@ -467,21 +507,21 @@ def _descriptors_like(base, model, smoothing, shape0, dtype=np.float64, complex_
         _set_complex_step(m, *complex_step)
     else:
         _set_param(m, *bump)
-    ev, shape = _host_descriptors(base, m, dtype=dtype)
+    ev, shape = _host_descriptors(base, m, dtype=dtype, factor=factor)
     if shape != shape0:
         raise _NoTangentForm("descriptor structure depends on the parameters")
     return ev
 
 
-def descriptor_tangents(base, model, smoothing, mode=None):
+def descriptor_tangents(base, model, smoothing, mode=None, factor=False):
     """Host only: (d0, dd), every descriptor block of the compiled controller `base` (_host_descriptors) and its derivative
     [...][P] with respect to the P parameters of `model`.  mode (default: the environment's MCX_DESCRIPTOR_FD, else "complex"):
     "complex": the closed forms are analytic in the parameters, so d f / d theta = Im f(theta + i h) / h with h far below rounding —
     ONE evaluation per parameter, no subtractive cancellation (exact to the last bits); a model whose closed forms are written
     with real-only functions (TypeError) falls back to "4": 4-point central differences with a wide step (truncation O(h^4) ~
     1e-12, rounding eps/h ~ 1e-13 relative).  Anything else: the 2-point formula (h = 1e-6 left 1e-5 relative noise on
-    d CVA / d sigma_cir: CIR++ sensitivities are small residuals of large cancelling terms)."""
-    d0, shape0 = _host_descriptors(base, model)
+    d CVA / d sigma_cir: CIR++ sensitivities are small residuals of large cancelling terms).  factor: _host_descriptors'."""
+    d0, shape0 = _host_descriptors(base, model, factor=factor)
     theta = [float(p.detach()) for p in model.get_model_params()]
     dd = {k: np.zeros(v.shape + (len(theta),)) for k, v in d0.items()}
     mode = os.environ.get("MCX_DESCRIPTOR_FD", "complex") if mode is None else mode
@@ -489,7 +529,7 @@ def descriptor_tangents(base, model, smoothing, mode=None):
         try:
             for j, th in enumerate(theta):
                 h = 1e-30 * max(abs(th), 1e-2)
-                ev = _descriptors_like(base, model, smoothing, shape0, np.complex128, complex_step=(j, h))
+                ev = _descriptors_like(base, model, smoothing, shape0, np.complex128, complex_step=(j, h), factor=factor)
                 for k in dd:
                     dd[k][..., j] = ev[k].imag / h
             return d0, dd
@@ -498,7 +538,7 @@ def descriptor_tangents(base, model, smoothing, mode=None):
     four_point = mode == "4"
     for j, th in enumerate(theta):
         h = (1e-3 if four_point else 1e-4) * max(abs(th), 1e-2)
-        ev = {mult: _descriptors_like(base, model, smoothing, shape0, bump=(j, th + mult * h))
+        ev = {mult: _descriptors_like(base, model, smoothing, shape0, bump=(j, th + mult * h), factor=factor)
               for mult in ((1, -1, 2, -2) if four_point else (1, -1))}
         for k in dd:
             if four_point:
@@ -561,7 +601,7 @@ def payoff_forms_armed(sc, be) -> bool:
     so such a book keeps the library's refusal, and with it the NotImplementedError of storage books"""
     return bool(getattr(sc, "tangent_payoffs", False)) and hasattr(be, "book_set_payoff_tangents") \
         and not any(getattr(p, "is_storage", False) for p in sc.products) \
-        and not heston_route(sc) and not wide_route(sc)      # the payoff forms on Heston / wide dual paths: not compared either
+        and not heston_route(sc) and not wide_route(sc) and not hull_white_route(sc)      # the payoff forms on Heston / wide / Hull-White dual paths: not compared either
 
 
 def pad_chunk(a, sel):
@@ -581,7 +621,8 @@ def _dual_paths(ctx, chunk, seed, off, n, inject_z, inject_u=None):
     uniforms of the same simulation (pre-simulation or main), which only the Heston QE step consumes"""
     be, sim, c = ctx.be, ctx.base._sim, chunk
     if ctx.wide:                              # (pre-simulation and main pass of a chunk have the same active slots)
-        paths, dpaths, ctx.active[c.sel[0]] = be.tangent_paths_wide(sim, c.dslot, c.dinit, c.daux, c.dchol, seed, off, n, inject_z)
+        entry = be.tangent_paths_wide_hw if hull_white_route(ctx.sc) else be.tangent_paths_wide
+        paths, dpaths, ctx.active[c.sel[0]] = entry(sim, c.dslot, c.dinit, c.daux, c.dchol, seed, off, n, inject_z)
         return paths, dpaths
     if ctx.heston:
         return be.tangent_paths_heston(sim, c.dslot, c.dinit, c.daux, c.dchol, seed, off, n, inject_z, inject_u)
@@ -813,13 +854,15 @@ def run_with_tangent_book(sc):
     NP = _abi.TANGENT_NP
     # the wide route: a model of 5 to 8 slots has no narrow dual path kernel, so the base controller's plan is forced wide (the
     # paths are the narrow kernel's bit for bit, but the book then runs unfused); a model of more than 8 slots is wide already
-    wide = wide_route(sc)
+    # the Hull-White route is the wide route on mcx_tangent_paths_wide_hw, from one slot on, in passes over the live parameters only
+    hw = hull_white_route(sc)
+    wide = wide_route(sc) or hw
     base = _clone_controller(sc, sc.model, sc.reference_float32_cf_cache, force_wide=wide and not _wide_model(sc.model))
     res0 = base.run_simulation()
     if base.book_plan.n_basis > 4:
         raise _NoTangentForm("basis")
     # `base` is compiled: its sub-step schedule and atoms are re-evaluated under the bumped models
-    _d0, dd = descriptor_tangents(base, sc.model, getattr(sc.model, "perform_smoothing", False))
+    _d0, dd = descriptor_tangents(base, sc.model, getattr(sc.model, "perform_smoothing", False), factor=hw)
     t_desc = time.perf_counter() - t0
     t_pre = t_main = 0.0
     P, n_coeffs = len(sc.model.get_model_params()), len(base.book_plan.coeffs)
@@ -837,9 +880,12 @@ def run_with_tangent_book(sc):
         dpayoff = payoff_tangents(base, sc.model, getattr(sc.model, "perform_smoothing", False))
     ctx = _BookPass(sc, base, be, shard, s2f, chol, batched, rows, base_coeffs, dpayoff, heston_route(sc), wide, {})
     n_batched = 0
+    # a parameter no descriptor number depends on (a Hull-White curve node beyond the horizon) keeps its zero rows without a pass
+    todo = live_parameters(dd) if hw else list(range(P))
+    chunks = [todo[c0:c0 + NP] for c0 in range(0, len(todo), NP)]
     try:
-        for c0 in range(0, P, NP):
-            chunk = _parameter_chunk(ctx, dd, list(range(c0, min(c0 + NP, P))))
+        for sel in chunks:
+            chunk = _parameter_chunk(ctx, dd, sel)
             if dpayoff is not None:
                 be.book_set_payoff_tangents(base.book, be.from_numpy(pad_chunk(dpayoff, chunk.sel)))
             t1 = time.perf_counter()
@@ -857,11 +903,13 @@ def run_with_tangent_book(sc):
         if dpayoff is not None:
             be.book_set_payoff_tangents(base.book, None)
     sc.sim_plan, sc.last_state = base.sim_plan, base.last_state
-    sc.timings = dict(total=time.perf_counter() - t0, tangent=True, forward_mode_passes=(P + NP - 1) // NP,
+    sc.timings = dict(total=time.perf_counter() - t0, tangent=True, forward_mode_passes=len(chunks),
                       base_run_and_descriptor_derivatives=t_desc, presim_and_regression=t_pre, main=t_main,
                       batched_lsm_jobs=n_batched)
     if wide:
-        sc.timings["wide_active_slots"] = [ctx.active[c0] for c0 in range(0, P, NP)]
+        sc.timings["wide_active_slots"] = [ctx.active[sel[0]] for sel in chunks]
+    if hw:
+        sc.timings["dead_parameters"] = sorted(set(range(P)) - set(todo))
     g = [[[tuple(ev) for ev in per_metric] for per_metric in per_ns] for per_ns in grads]
     return sc._package([[[tuple(v) for v in evals] for evals in per_metric] for per_metric in res0.results], g, [])
 

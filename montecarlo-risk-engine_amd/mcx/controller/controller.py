@@ -294,6 +294,11 @@ class SimulationController:
         # a model of 5 to 8 slots then runs its base pass on a forced-wide plan, i.e. unfused.  Never armed together with
         # tangent_payoffs (aad.payoff_forms_armed)
         self.tangent_wide = False
+        # differentiate=True: True sends a book under 1 to 32 one-factor sub-models of which at least one is Hull-White (EULER: next to
+        # Black-Scholes, Vasicek, CIR++; ANALYTICAL: a single Hull-White model; no storage) through the forward-mode book pass on
+        # mcx_tangent_paths_wide_hw (mcx/aad.py hull_white_route), in passes over the live parameters only; False: such a book keeps
+        # bump-and-revalue.  A model without a Hull-White slot is never touched.  Never armed together with tangent_payoffs
+        self.tangent_hull_white = False
         self._force_wide_plan = False    # set by aad._clone_controller only: build the SimPlan with force_wide=True
         # The reference compiles nothing: every run_simulation() sees the current state of its products / metrics.  Re-using the
         # compiled descriptors and the uploaded book of the previous run is an opt-in for callers that re-run an UNCHANGED

@@ -20,13 +20,15 @@ from .. import _abi
 from ..common.enums import SimulationScheme
 from ..common.packages import FLOAT, device
 from ..request_interface.request_types import AtomicRequestType as RT
-from .model import AtomCoef, Model, SlotSpec
+from .model import cexp, clog, csqrt, AtomCoef, Model, SlotSpec
 
 
 class HullWhiteModel(Model):
     def __init__(self, calibration_date: float, rate: float, initial_forward_curve, forward_curve_derivative,
                  mean_reversion: float, volatility: float, asset_id: str | None = None, curve_times=None):
         super().__init__(calibration_date=calibration_date, state_dim=2, asset_ids=[asset_id])
+        # the curve as constructed: length and parameter names only.  Every closed form reads the nodes through the parameters
+        # (`_curve`), which is what a bump or a complex step moves (mcx/aad.py)
         self._f = [float(v) for v in initial_forward_curve]
         self._df = [float(v) for v in forward_curve_derivative]
         assert len(self._f) == len(self._df) >= 2
@@ -57,10 +59,19 @@ class HullWhiteModel(Model):
         idx = min(max(idx, 0), len(ts) - 2)
         return curve[idx] + (curve[idx + 1] - curve[idx]) * (t - ts[idx]) / (ts[idx + 1] - ts[idx])
 
+    def _curve(self, t: float, base: int):
+        """`interpolate` on the curve whose nodes are the model parameters base .. base + n (3: forward_curve, 3 + n: its derivative),
+        read through `_pf`: a bumped or complex-stepped node reaches every closed form.  Only the two nodes of the segment are read"""
+        ts = self._t
+        idx = int(np.searchsorted(ts, t)) - 1
+        idx = min(max(idx, 0), len(ts) - 2)
+        lo, hi = self._pf(base + idx), self._pf(base + idx + 1)
+        return lo + (hi - lo) * (t - ts[idx]) / (ts[idx + 1] - ts[idx])
+
     def compute_theta(self, t: float) -> float:
-        a, sigma = self._pf(2), self._pf(1)
-        return self.interpolate(t, self._df) + a * self.interpolate(t, self._f) \
-            + (sigma ** 2 / (2 * a)) * (1 - math.exp(-2 * a * t))
+        a, sigma, n = self._pf(2), self._pf(1), len(self._t)
+        return self._curve(t, 3 + n) + a * self._curve(t, 3) \
+            + (sigma ** 2 / (2 * a)) * (1 - cexp(-2 * a * t))
 
     def _int_forward(self, t: float) -> float:
         """int_0^t f(0,s) ds of the piecewise-linear (extrapolated) forward curve, exact"""
@@ -68,28 +79,35 @@ class HullWhiteModel(Model):
         knots = [0.0] + [x for x in ts if 0.0 < x < t] + [t]
         total = 0.0
         for lo, hi in zip(knots[:-1], knots[1:]):
-            total += 0.5 * (self.interpolate(lo, self._f) + self.interpolate(hi, self._f)) * (hi - lo)
+            total += 0.5 * (self._curve(lo, 3) + self._curve(hi, 3)) * (hi - lo)
         return total
 
     def discount_curve(self, t: float) -> float:
-        return math.exp(-self._int_forward(t - self.t0()))
+        return cexp(-self._int_forward(t - self.t0()))
 
     def _zcb_coeffs(self, time1: float, time2: float) -> tuple[float, float]:
         a, sigma = self._pf(2), self._pf(1)
         t = time1 - self.t0()
         tau = time2 - time1
-        B = (1 - math.exp(-a * tau)) / a
-        alpha = math.log(self.discount_curve(time2) / self.discount_curve(time1)) + B * self.interpolate(t, self._f) \
-            - (sigma ** 2 / (4 * a)) * (1 - math.exp(-2 * a * t)) * B ** 2
+        B = (1 - cexp(-a * tau)) / a
+        # log(P(0,T2) / P(0,T1)) as the parent wrote it (exp, divide, log): the same bits at real parameters, and complex-safe
+        alpha = clog(self.discount_curve(time2) / self.discount_curve(time1)) + B * self._curve(t, 3) \
+            - (sigma ** 2 / (4 * a)) * (1 - cexp(-2 * a * t)) * B ** 2
         return alpha, B
 
     def compute_bond_price(self, time1, time2, rate):
         alpha, B = self._zcb_coeffs(float(time1), float(time2))
-        return math.exp(alpha) * torch.exp(-B * torch.as_tensor(rate, dtype=FLOAT, device=device))
+        return cexp(alpha) * torch.exp(-B * torch.as_tensor(rate, dtype=FLOAT, device=device))
 
     def _get_covariance_matrix(self, delta_t) -> torch.Tensor:
         a, sigma = self._pf(2), self._pf(1)
         return torch.tensor([[(sigma ** 2 / (2 * a)) * (1 - math.exp(-2 * a * float(delta_t)))]], dtype=FLOAT)
+
+    def _analytic_factor_entries(self, delta_t):
+        """the ANALYTICAL scheme's factor in closed form, complex-safe (vasicek.py; read by the Hull-White forward-mode route only:
+        mcx/aad.py hull_white_route — the narrow dual path kernels have no Hull-White step, aad._analytic_factor_form stays False)"""
+        a, sigma = self._pf(2), self._pf(1)
+        return [[csqrt((sigma ** 2 / (2 * a)) * (1 - cexp(-2 * a * float(delta_t))))]]
 
     # ---- native hooks -------------------------------------------------------------------------------------------
     def _slots(self):
@@ -102,7 +120,7 @@ class HullWhiteModel(Model):
         a = self._pf(2)
         theta = self.compute_theta(t1 - self.t0())
         if scheme == SimulationScheme.ANALYTICAL:
-            E = math.exp(-a * dt)
+            E = cexp(-a * dt)
             return [[E, theta * (1 - E) / a]]          # r' = r E + theta(t1)(1-E)/a + w      hull_white.py:76-83
         return [[theta]]                               # r' = r + (theta(t1) - a r) dt + ...  hull_white.py:104-108
 
