@@ -733,6 +733,23 @@ int  mcx_reduce_cva(mcx_handle* h, const mcx_book* book, const mcx_unsecured_des
                     const int32_t* h_surv_atoms, const int32_t* h_cond_atoms, double recovery,
                     const double* d_expo_ns, const double* d_paths, int64_t n_paths, int64_t ld_expo, int64_t ld_paths,
                     mcx_acc* h_out, void* stream);
+/* mcx_reduce_xva     : bilateral xVA in one pass over the unsecured exposures u_m, c = counterparty, o = own name, per path
+ *                      with S_n = S_n(0,t_m), q_n = 1 - S_n(t_m,t_{m+1}) and the sums over m < n_dates-1:
+ *                        h_out[0] cva     = (1-R_c) sum relu( u_m) S_c q_c          (== mcx_reduce_cva)
+ *                        h_out[1] dva     = (1-R_o) sum relu(-u_m) S_o q_o
+ *                        h_out[2] cva_ftd = (1-R_c) sum relu( u_m) S_c q_c S_o      (first to default)
+ *                        h_out[3] dva_ftd = (1-R_o) sum relu(-u_m) S_o q_o S_c
+ *                        h_out[4] bcva    = cva_ftd - dva_ftd, PER PATH (positive = cost)
+ *                      h_surv_x / h_cond_x: [n_dates-1] atom ids in `book`; a pair may be NULL (both or neither): that name never
+ *                      defaults (S = 1, q = 0).  One launch + the second stage of every K4 reduction; no float atomics.
+ *                      Refusals (h_out untouched): -1 a NULL handle / book / descriptor / buffer / h_out; -2 a leading dimension
+ *                      below n_paths, half a pair of atom lists, an atom id or an exposure row out of range.  n_paths <= 0
+ *                      zeroes h_out[5]. */
+int  mcx_reduce_xva(mcx_handle* h, const mcx_book* book, const mcx_unsecured_desc* u,
+                    const int32_t* h_surv_c, const int32_t* h_cond_c, double recovery_c,
+                    const int32_t* h_surv_o, const int32_t* h_cond_o, double recovery_o,
+                    const double* d_expo_ns, const double* d_paths, int64_t n_paths, int64_t ld_expo, int64_t ld_paths,
+                    mcx_acc* h_out, void* stream);
 /* materialise unsecured exposures for pluggable metrics: d_out [n_dates][ld_out] */
 int  mcx_unsecured(mcx_handle* h, const mcx_unsecured_desc* u, const double* d_expo_ns, int64_t n_paths, int64_t ld,
                    double* d_out, int64_t ld_out, void* stream);

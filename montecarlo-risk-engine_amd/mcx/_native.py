@@ -29,7 +29,7 @@ _EXPORTS = [
     "mcx_storage_create", "mcx_storage_destroy", "mcx_storage_lsm_step", "mcx_storage_lsm_run", "mcx_storage_eval",
     "mcx_storage_lsm_step_batch", "mcx_storage_lsm_solve_batch", "mcx_storage_lsm_run_batch",
     "mcx_tangent_storage_lsm_step", "mcx_tangent_storage_eval", "mcx_tangent_paths_s2f", "mcx_tangent_paths_heston", "mcx_tangent_paths_wide", "mcx_tangent_paths_wide_hw",
-    "mcx_reduce_vector", "mcx_reduce_profiles", "mcx_reduce_cva", "mcx_unsecured", "mcx_select_hist", "mcx_select_hist_dev", "mcx_select_narrow", "mcx_select_bracket", "mcx_select_hist_rows",
+    "mcx_reduce_vector", "mcx_reduce_profiles", "mcx_reduce_cva", "mcx_reduce_xva", "mcx_unsecured", "mcx_select_hist", "mcx_select_hist_dev", "mcx_select_narrow", "mcx_select_bracket", "mcx_select_hist_rows",
 ]
 
 
@@ -1011,6 +1011,22 @@ class HipBackend:
             self.h, book.ptr, C.byref(unsec.desc), _abi.ptr(sa), _abi.ptr(ca), C.c_double(recovery),
             _vp(expo_ns.data_ptr()), _vp(paths.data_ptr()), C.c_int64(n), C.c_int64(_ld(expo_ns)), C.c_int64(_ld(paths)),
             _abi.ptr(out), self._stream()), "mcx_reduce_cva")
+        return out
+
+    def reduce_xva(self, book, unsec, cp_atoms, recovery: float, own_atoms, own_recovery: float, expo_ns: torch.Tensor,
+                   paths: torch.Tensor) -> np.ndarray:
+        """mcx_reduce_xva: the records of (cva, dva, cva_ftd, dva_ftd, bcva).  cp_atoms / own_atoms: (surv, cond) atom id lists
+        of the counterparty and of the own name, or None for a name that never defaults"""
+        n = expo_ns.shape[1]
+        unsec.desc.n_rows = expo_ns.shape[0]
+        (sc, cc), (so, co) = [(None, None) if side is None else tuple(np.ascontiguousarray(x, dtype=np.int32) for x in side)
+                              for side in (cp_atoms, own_atoms)]
+        out = np.zeros(5, dtype=_abi.ACC_DTYPE)
+        self._check(self.lib.mcx_reduce_xva(
+            self.h, book.ptr, C.byref(unsec.desc), _abi.ptr(sc), _abi.ptr(cc), C.c_double(recovery), _abi.ptr(so), _abi.ptr(co),
+            C.c_double(own_recovery),
+            _vp(expo_ns.data_ptr()), _vp(paths.data_ptr()), C.c_int64(n), C.c_int64(_ld(expo_ns)), C.c_int64(_ld(paths)),
+            _abi.ptr(out), self._stream()), "mcx_reduce_xva")
         return out
 
     def unsecured(self, unsec, expo_ns: torch.Tensor) -> torch.Tensor:

@@ -666,6 +666,20 @@ class SimulationController:
                     surv.append(comp.atom(m.survival_prob_requests[label], m.counterparty_id, mt[k]))
                     cond.append(comp.atom(m.cond_survival_prob_requests[label], m.counterparty_id, mt[k]))
                 self._cva_atoms[m_i] = (surv, cond)
+        # the same two atoms per date for the names of DVAMetric / BilateralCVAMetric (mcx_reduce_xva): metric -> the two argument
+        # pairs of reduce_xva, (((surv, cond) | None, recovery) of the counterparty, ((surv, cond), recovery) of the own name).  Through atoms, not request handles: metrics on one name do not collide here
+        self._xva_atoms = {}
+
+        def side(name, s_req, c_req):
+            ks = range(len(mt) - 1)
+            return ([comp.atom(s_req[(k, name)], name, mt[k]) for k in ks], [comp.atom(c_req[(k, name)], name, mt[k]) for k in ks])
+        for m_i, m in enumerate(rm.metrics):
+            if m.metric_type == MetricType.DVA and m._native:
+                # (no counterparty: it never defaults; DVAMetric.recovery_rate is the own name's)
+                self._xva_atoms[m_i] = ((None, 0.0), (side(m.own_id, m.survival_prob_requests, m.cond_survival_prob_requests), m.recovery_rate))
+            elif m.metric_type == MetricType.BCVA and m._native:
+                self._xva_atoms[m_i] = ((side(m.counterparty_id, m.survival_prob_requests, m.cond_survival_prob_requests), m.recovery_rate),
+                                        (side(m.own_id, m.own_survival_prob_requests, m.own_cond_survival_prob_requests), m.own_recovery_rate))
         self._comp = comp
         n_state = sum(s.state_dim for s in self.model._slots())
         self._plan_args = (prods, len(self.netting_sets), E if want_expo else 0, off, want_cfs, want_expo, n_state)
@@ -1127,7 +1141,9 @@ class SimulationController:
 
     # ---- main simulation: metrics (controller.py:506-563) ----------------------------------------------------------
     def _zero_metric_result(self, metric: Metric):
-        n = 1 if metric.metric_type in {MetricType.PV, MetricType.CVA, MetricType.EEPE} else len(self.metric_exposure_timeline)
+        if metric.metric_type == MetricType.BCVA:
+            return [(0.0, 0.0) for _ in metric.EVALUATIONS]
+        n = 1 if metric.metric_type in {MetricType.PV, MetricType.CVA, MetricType.DVA, MetricType.EEPE} else len(self.metric_exposure_timeline)
         return [(0.0, 0.0) for _ in range(n)]
 
     def _radix_select(self, shard: Shard, E: int, n_sel: int, rem, hist_pass, digits=_SELECT_DIGITS, keys=False) -> np.ndarray:
@@ -1267,8 +1283,8 @@ class SimulationController:
         out = []
         for m_i, metric in enumerate(rm.metrics):
             mt = metric.metric_type
-            if mt == MetricType.CVA and ns.counterparty_id is not None \
-                    and getattr(metric, "counterparty_id", None) != ns.counterparty_id:
+            if mt in (MetricType.CVA, MetricType.BCVA) and ns.counterparty_id is not None \
+                    and getattr(metric, "counterparty_id", None) != ns.counterparty_id:   # (the own name never gates; nor does DVA)
                 out.append(self._zero_metric_result(metric))                           # controller.py:536-542
                 continue
             if mt == MetricType.PV and metric.evaluation_type == Metric.EvaluationType.ANALYTICAL:
@@ -1277,7 +1293,8 @@ class SimulationController:
                     val, err = mean_and_error(pv_records())
                 out.append([(analytical_acc[m_i] + val, err)])
                 continue
-            if not metric._native:
+            # (DVA / bilateral CVA on a backend without reduce_xva: the plugin route with the metric's host form)
+            if not metric._native or (mt in (MetricType.DVA, MetricType.BCVA) and not hasattr(be, "reduce_xva")):
                 out.append(self._evaluate_plugin_metric(metric, ns, unsec, expo_ns, cfs, ns_i, paths))
                 continue
             if mt == MetricType.PV:
@@ -1299,6 +1316,11 @@ class SimulationController:
                     surv, cond = self._cva_atoms[m_i]
                     rec = be.reduce_cva(self.book, unsec, surv, cond, metric.recovery_rate, expo_ns, paths)
                     out.append([mean_and_error(shard.all_gather_np(rec.view(np.float64)))])
+            elif mt in (MetricType.DVA, MetricType.BCVA):
+                (cp_atoms, cp_recovery), (own_atoms, own_recovery) = self._xva_atoms[m_i]
+                rec = be.reduce_xva(self.book, unsec, cp_atoms, cp_recovery, own_atoms, own_recovery, expo_ns, paths)
+                g = shard.all_gather_np(rec.view(np.float64).reshape(5, 4))          # [world][5][4]
+                out.append([mean_and_error(g[:, e]) for e in (range(5) if mt == MetricType.BCVA else (1,))])
             elif mt == MetricType.PFE:
                 q = metric.q_index(n_total)
                 edge = q == 0 or q == n_total - 1
@@ -1376,6 +1398,8 @@ class SimulationController:
         if len(self.netting_sets) > _abi.FUSED_MAX_NS or any(ns.is_collateralized() for ns in self.netting_sets):
             return None
         if not all(m._native for m in rm.metrics):
+            return None
+        if any(m.metric_type in (MetricType.DVA, MetricType.BCVA) for m in rm.metrics):   # no fused form: K1 -> K2 -> K4 (k4_xva)
             return None
         want_expo = rm.requires_exposure_profiles()
         kinds = {m.metric_type for m in rm.metrics}

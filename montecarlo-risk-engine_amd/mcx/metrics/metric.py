@@ -23,6 +23,8 @@ class MetricType(Enum):
     PFE = "Potential Future Exposure"
     EEPE = "Effective Expected Positive Exposure"
     CVA = "Credit Valuation Adjustment"
+    DVA = "Debit Valuation Adjustment"
+    BCVA = "Bilateral Credit Valuation Adjustment"
 
 
 def combine_acc(recs: np.ndarray) -> tuple[float, float, float]:

@@ -22,7 +22,7 @@ class RiskMetrics:
         kinds = {m.metric_type for m in metrics}
         self.metrics = metrics
         self.any_pv = MetricType.PV in kinds
-        self.any_xva = MetricType.CVA in kinds
+        self.any_xva = bool(kinds & {MetricType.CVA, MetricType.DVA, MetricType.BCVA})
         self.any_exposure = bool(kinds - {MetricType.PV})
         if self.any_exposure and dates.size == 0:
             raise AssertionError("For exposure simulation at least one exposure time point needs to be provided.")
