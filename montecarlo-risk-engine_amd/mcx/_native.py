@@ -589,18 +589,20 @@ class HipBackend:
 
     def tangent_lsm_step(self, book, product: int, roll_begin: int, roll_end: int, num_atom: int, x_atom: int, shift: float,
                          scale: float, datoms: torch.Tensor, paths: torch.Tensor, dpaths: torch.Tensor, W: torch.Tensor,
-                         dW: torch.Tensor) -> np.ndarray:
+                         dW: torch.Tensor, n_paths: int | None = None) -> np.ndarray:
         """one backward step of an exercise product's regression in dual numbers (mcx_tangent_lsm_step): W [S][n], dW [NP][S][n]
-        are rolled in place; returns the moments [1+NP][(2K-1) + S K]"""
+        are rolled in place; returns the moments [1+NP][(2K-1) + S K].  n_paths: the paths of the [T][D][ld] tensors that count
+        (default: all ld of them)"""
         K, S = book.plan.n_basis, W.shape[0]
         NP = _abi.TANGENT_NP
-        n = paths.shape[2]
-        assert W.is_contiguous() and dW.is_contiguous() and dW.shape == (NP, S, W.shape[1]) and W.shape[1] >= n
+        ld = paths.shape[2]
+        n = ld if n_paths is None else int(n_paths)
+        assert n <= ld and W.is_contiguous() and dW.is_contiguous() and dW.shape == (NP, S, W.shape[1]) and W.shape[1] >= n
         out = np.zeros((1 + NP, (2 * K - 1) + S * K))
         self._check(self.lib.mcx_tangent_lsm_step(
             self.h, book.ptr, C.c_int32(product), C.c_int32(roll_begin), C.c_int32(roll_end), C.c_int32(num_atom), C.c_int32(x_atom),
             C.c_double(shift), C.c_double(scale), _vp(datoms.data_ptr()), _vp(paths.data_ptr()), _vp(dpaths.data_ptr()),
-            C.c_int64(n), C.c_int64(n), C.c_int32(paths.shape[0]), _vp(W.data_ptr()), _vp(dW.data_ptr()), C.c_int64(W.shape[1]),
+            C.c_int64(n), C.c_int64(ld), C.c_int32(paths.shape[0]), _vp(W.data_ptr()), _vp(dW.data_ptr()), C.c_int64(W.shape[1]),
             _abi.ptr(out), self._stream()), "mcx_tangent_lsm_step")
         return out
 
@@ -621,44 +623,59 @@ class HipBackend:
             self._stream()), "mcx_tangent_eval")
         return cfs, expo
 
-    def tangent_pick(self, rows, threshold: float, targets, expo: torch.Tensor, ns_i: int, delayed=None, collateralized=False) -> np.ndarray:
-        """-> [n_dates][1+NP]: (local index of the path realising the order statistic or -1, its tangent)"""
+    def tangent_pick(self, rows, threshold: float, targets, expo: torch.Tensor, ns_i: int, delayed=None, collateralized=False,
+                     n_paths: int | None = None) -> np.ndarray:
+        """-> [n_dates][1+NP]: (local index of the path realising the order statistic or -1, its tangent).  n_paths: the paths of
+        expo [1+NP][NS][rows][ld] that count (default: all ld of them)"""
         r = np.ascontiguousarray(rows, dtype=np.int32)
         dl = None if delayed is None else np.ascontiguousarray(delayed, dtype=np.int32)
         tg = np.ascontiguousarray(targets, dtype=np.float64)
         out = np.zeros((len(r), 1 + _abi.TANGENT_NP))
-        n = expo.shape[3]
+        ld = expo.shape[3]
+        n = ld if n_paths is None else int(n_paths)
+        assert n <= ld
         stride = expo.shape[1] * expo.shape[2] * expo.shape[3]
         self._check(self.lib.mcx_tangent_pick(self.h, _abi.ptr(r), _abi.ptr(dl) if dl is not None else None, C.c_int32(int(collateralized)),
                                               C.c_int32(len(r)), C.c_double(threshold), _abi.ptr(tg), _vp(expo[0, ns_i].data_ptr()),
-                                              C.c_int64(stride), C.c_int64(n), C.c_int64(n), _abi.ptr(out), self._stream()), "mcx_tangent_pick")
+                                              C.c_int64(stride), C.c_int64(n), C.c_int64(ld), _abi.ptr(out), self._stream()), "mcx_tangent_pick")
         return out
 
     def tangent_cva(self, book, datoms: torch.Tensor, rows, surv, cond, threshold: float, recovery: float, expo: torch.Tensor,
-                    ns_i: int, paths: torch.Tensor, dpaths: torch.Tensor, delayed=None, collateralized=False) -> torch.Tensor:
-        n = paths.shape[2]
+                    ns_i: int, paths: torch.Tensor, dpaths: torch.Tensor, delayed=None, collateralized=False,
+                    n_paths: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """n_paths: the paths of the [..][ld] tensors (paths, dpaths, expo, out share ld) that count (default: all ld of them);
+        out [1+NP][ld]: written in place when given"""
+        ld = paths.shape[2]
+        n = ld if n_paths is None else int(n_paths)
+        assert n <= ld and expo.shape[3] == ld
         dl = None if delayed is None else np.ascontiguousarray(delayed, dtype=np.int32)
         r, s, c = (np.ascontiguousarray(x, dtype=np.int32) for x in (rows, surv, cond))
-        out = self.empty(1 + _abi.TANGENT_NP, n)
+        if out is None:
+            out = self.empty(1 + _abi.TANGENT_NP, ld)
+        assert out.is_contiguous() and tuple(out.shape) == (1 + _abi.TANGENT_NP, ld)
         stride = expo.shape[1] * expo.shape[2] * expo.shape[3]
         self._check(self.lib.mcx_tangent_cva(
             self.h, book.ptr, _vp(datoms.data_ptr()), _abi.ptr(r), _abi.ptr(s), _abi.ptr(c),
             _abi.ptr(dl) if dl is not None else None, C.c_int32(int(collateralized)), C.c_int32(len(r)),
             C.c_double(threshold), C.c_double(recovery), _vp(expo[0, ns_i].data_ptr()), C.c_int64(stride), _vp(paths.data_ptr()),
-            _vp(dpaths.data_ptr()), C.c_int64(n), C.c_int64(n), C.c_int32(paths.shape[0]), _vp(out.data_ptr()), self._stream()),
+            _vp(dpaths.data_ptr()), C.c_int64(n), C.c_int64(ld), C.c_int32(paths.shape[0]), _vp(out.data_ptr()), self._stream()),
             "mcx_tangent_cva")
         return out
 
-    def tangent_profiles(self, rows, threshold: float, expo: torch.Tensor, ns_i: int, delayed=None, collateralized=False) -> np.ndarray:
-        """-> [n_dates][2][NP] local sums of 1[u>0] du (EPE) and 1[u<0] du (ENE)"""
+    def tangent_profiles(self, rows, threshold: float, expo: torch.Tensor, ns_i: int, delayed=None, collateralized=False,
+                         n_paths: int | None = None) -> np.ndarray:
+        """-> [n_dates][2][NP] local sums of 1[u>0] du (EPE) and 1[u<0] du (ENE).  n_paths: the paths of expo [1+NP][NS][rows][ld]
+        that count (default: all ld of them)"""
         r = np.ascontiguousarray(rows, dtype=np.int32)
         dl = None if delayed is None else np.ascontiguousarray(delayed, dtype=np.int32)
         out = np.zeros((len(r), 2, _abi.TANGENT_NP))
-        n = expo.shape[3]
+        ld = expo.shape[3]
+        n = ld if n_paths is None else int(n_paths)
+        assert n <= ld
         stride = expo.shape[1] * expo.shape[2] * expo.shape[3]
         self._check(self.lib.mcx_tangent_profiles(self.h, _abi.ptr(r), _abi.ptr(dl) if dl is not None else None,
                                                   C.c_int32(int(collateralized)), C.c_int32(len(r)), C.c_double(threshold),
-                                                  _vp(expo[0, ns_i].data_ptr()), C.c_int64(stride), C.c_int64(n), C.c_int64(n),
+                                                  _vp(expo[0, ns_i].data_ptr()), C.c_int64(stride), C.c_int64(n), C.c_int64(ld),
                                                   _abi.ptr(out), self._stream()), "mcx_tangent_profiles")
         return out
 
