@@ -158,22 +158,23 @@ extern "C" int mcx_rng_draws(mcx_handle* h, uint64_t seed, uint64_t path0, int64
     return 0;
 }
 
-extern "C" int mcx_sim_create(mcx_handle* h, const mcx_sim_desc* d, mcx_sim** out)
+// ---- what mcx_sim_create and mcx_sim_create_wide (k1_wide.hip) check and derive alike; `who` fronts every message -------------
+// The slot layout and the step maps that exist per model (the reference's simulate_time_step_* overrides; model.py:102-141 leaves the
+// others unimplemented): the kernels read scheme-specific derived step constants, an unsupported pair would run on zeros.  wide: the
+// one-factor kinds alone, the further restriction of a wide model.
+int mcx_sim_check_slots(mcx_handle* h, const char* who, const mcx_slot* slots, int n_slots, int n_state, int scheme, bool wide)
 {
-    if (!h || !d || !out) return -1;
-    if (d->n_slots < 1 || d->n_slots > MCX_MAX_SLOTS || d->n_z > MCX_MAX_Z || d->n_state > MCX_MAX_STATE)
-        MCX_FAIL(h, -2, "mcx_sim_create: dimensions out of range (slots %d, z %d, state %d)", d->n_slots, d->n_z, d->n_state);
-    if (!(d->n_slots == 1 || d->n_z == d->n_slots))
-        MCX_FAIL(h, -3, "mcx_sim_create: a multi-model configuration needs simulation_dim == 1 per sub-model");
+    for (int s = 0; wide && s < n_slots; ++s) {
+        const int kind = slots[s].kind;
+        if (kind != MCX_MODEL_BS && kind != MCX_MODEL_VASICEK && kind != MCX_MODEL_HW && kind != MCX_MODEL_CIRPP && kind != MCX_MODEL_CIRPP_DET)
+            MCX_FAIL(h, -2, "%s: slot %d (model kind %d) is not a one-factor kind of a wide model", who, s, kind);
+    }
     int so = 0;
-    for (int s = 0; s < d->n_slots; ++s) {
-        const int sd = mcx_kind_state_dim(d->slots[s].kind);
-        if (d->slots[s].kind == MCX_MODEL_S2F && d->n_slots != 1) MCX_FAIL(h, -3, "mcx_sim_create: the Schwartz two-factor model runs alone");
-        if (d->slots[s].state_off != so) MCX_FAIL(h, -4, "mcx_sim_create: state offsets must be packed");
-        so += sd;
-        // the step maps that exist per model (the reference's simulate_time_step_* overrides; model.py:102-141 leaves the others
-        // unimplemented): the kernels read scheme-specific derived step constants, an unsupported pair would run on zeros
-        const int kind = d->slots[s].kind, sc = d->scheme;
+    for (int s = 0; s < n_slots; ++s) {
+        const int kind = slots[s].kind, sc = scheme;
+        if (kind == MCX_MODEL_S2F && n_slots != 1) MCX_FAIL(h, -3, "%s: the Schwartz two-factor model runs alone", who);
+        if (slots[s].state_off != so) MCX_FAIL(h, -4, "%s: state offsets must be packed", who);
+        so += mcx_kind_state_dim(kind);
         bool ok;
         switch (kind) {
         case MCX_MODEL_HESTON: ok = sc == MCX_SCHEME_EULER || sc == MCX_SCHEME_QE; break;
@@ -183,17 +184,55 @@ extern "C" int mcx_sim_create(mcx_handle* h, const mcx_sim_desc* d, mcx_sim** ou
             ok = sc == MCX_SCHEME_EULER || sc == MCX_SCHEME_ANALYTICAL; break;
         default: ok = false; break;
         }
-        if (!ok) MCX_FAIL(h, -6, "mcx_sim_create: slot %d (model kind %d) has no step map for scheme %d", s, kind, sc);
+        if (!ok) MCX_FAIL(h, -6, "%s: slot %d (model kind %d) has no step map for scheme %d", who, s, kind, sc);
     }
-    if (so != d->n_state) MCX_FAIL(h, -4, "mcx_sim_create: n_state does not match the slots");
-    for (int k = 0; k < d->n_steps; ++k) {
-        if (d->steps[k].store_idx >= d->n_dates || d->steps[k].chol_idx < 0 || d->steps[k].chol_idx >= d->n_chol)
-            MCX_FAIL(h, -5, "mcx_sim_create: step %d references date/cholesky out of range", k);
+    if (so != n_state) MCX_FAIL(h, -4, "%s: n_state does not match the slots", who);
+    return 0;
+}
+
+int mcx_sim_check_steps(mcx_handle* h, const char* who, const mcx_step* steps, int n_steps, int n_dates, int n_chol, int scheme)
+{
+    for (int k = 0; k < n_steps; ++k) {
+        if (steps[k].store_idx >= n_dates || steps[k].chol_idx < 0 || steps[k].chol_idx >= n_chol)
+            MCX_FAIL(h, -5, "%s: step %d references date/cholesky out of range", who, k);
         // EULER / QE correlate every sub-step with the factor of the one correlation matrix (model.py:66-73): the kernels read
         // factor 0 without waiting for the step record
-        if ((d->scheme == MCX_SCHEME_EULER || d->scheme == MCX_SCHEME_QE) && d->steps[k].chol_idx != 0)
-            MCX_FAIL(h, -5, "mcx_sim_create: step %d: the EULER / QE schemes use Cholesky factor 0 for every sub-step", k);
+        if ((scheme == MCX_SCHEME_EULER || scheme == MCX_SCHEME_QE) && steps[k].chol_idx != 0)
+            MCX_FAIL(h, -5, "%s: step %d: the EULER / QE schemes use Cholesky factor 0 for every sub-step", who, k);
     }
+    return 0;
+}
+
+// the device image of the aux rows [n_steps][n_slots][MCX_AUX]: the caller's, with the derived constants of the Euler maps
+// (mcx_internal.h MCX_AUX_C0 .. C2) in their entries under EULER
+std::vector<double> mcx_sim_device_aux(const mcx_slot* slots, int n_slots, const mcx_step* steps, int n_steps, const double* h_aux, int scheme)
+{
+    std::vector<double> aux(h_aux, h_aux + (size_t)n_steps * n_slots * MCX_AUX);
+    for (int k = 0; scheme == MCX_SCHEME_EULER && k < n_steps; ++k)
+        for (int q = 0; q < n_slots; ++q) {
+            double* a = aux.data() + ((size_t)k * n_slots + q) * MCX_AUX;
+            const double* p = slots[q].p;
+            const double dt = steps[k].dt, sq = steps[k].sqrt_dt;
+            switch (slots[q].kind) {
+            case MCX_MODEL_BS: a[MCX_AUX_C0] = p[2] * dt; a[MCX_AUX_C2] = p[1] * sq; break;
+            case MCX_MODEL_VASICEK: a[MCX_AUX_C0] = p[3] * p[2] * dt; a[MCX_AUX_C1] = -(p[3] * dt); a[MCX_AUX_C2] = p[1] * sq; break;
+            case MCX_MODEL_CIRPP: a[MCX_AUX_C0] = p[0] * p[1] * dt; a[MCX_AUX_C1] = -(p[0] * dt); a[MCX_AUX_C2] = p[2] * sq; break;
+            default: break;
+            }
+        }
+    return aux;
+}
+
+extern "C" int mcx_sim_create(mcx_handle* h, const mcx_sim_desc* d, mcx_sim** out)
+{
+    const char* who = "mcx_sim_create";
+    if (!h || !d || !out) return -1;
+    if (d->n_slots < 1 || d->n_slots > MCX_MAX_SLOTS || d->n_z > MCX_MAX_Z || d->n_state > MCX_MAX_STATE)
+        MCX_FAIL(h, -2, "mcx_sim_create: dimensions out of range (slots %d, z %d, state %d)", d->n_slots, d->n_z, d->n_state);
+    if (!(d->n_slots == 1 || d->n_z == d->n_slots))
+        MCX_FAIL(h, -3, "mcx_sim_create: a multi-model configuration needs simulation_dim == 1 per sub-model");
+    if (int rc = mcx_sim_check_slots(h, who, d->slots, d->n_slots, d->n_state, d->scheme, false)) return rc;
+    if (int rc = mcx_sim_check_steps(h, who, d->steps, d->n_steps, d->n_dates, d->n_chol, d->scheme)) return rc;
     MCX_HIP(h, hipSetDevice(h->device));
     mcx_sim* sim = new mcx_sim();
     sim->desc = *d;
@@ -213,21 +252,7 @@ extern "C" int mcx_sim_create(mcx_handle* h, const mcx_sim_desc* d, mcx_sim** ou
     if (e == hipSuccess) e = hipMalloc(&sim->d_aux, nb_aux);
     if (e == hipSuccess && d->n_steps > 0) e = hipMemcpy(sim->d_steps, d->steps, sizeof(mcx_step) * d->n_steps, hipMemcpyHostToDevice);
     if (e == hipSuccess && d->n_steps > 0) {
-        std::vector<double> aux(d->aux, d->aux + (size_t)d->n_steps * d->n_slots * MCX_AUX);
-        if (d->scheme == MCX_SCHEME_EULER) {
-            for (int k = 0; k < d->n_steps; ++k)
-                for (int q = 0; q < d->n_slots; ++q) {
-                    double* a = aux.data() + ((size_t)k * d->n_slots + q) * MCX_AUX;
-                    const double* p = d->slots[q].p;
-                    const double dt = d->steps[k].dt, sq = d->steps[k].sqrt_dt;
-                    switch (d->slots[q].kind) {
-                    case MCX_MODEL_BS: a[MCX_AUX_C0] = p[2] * dt; a[MCX_AUX_C2] = p[1] * sq; break;
-                    case MCX_MODEL_VASICEK: a[MCX_AUX_C0] = p[3] * p[2] * dt; a[MCX_AUX_C1] = -(p[3] * dt); a[MCX_AUX_C2] = p[1] * sq; break;
-                    case MCX_MODEL_CIRPP: a[MCX_AUX_C0] = p[0] * p[1] * dt; a[MCX_AUX_C1] = -(p[0] * dt); a[MCX_AUX_C2] = p[2] * sq; break;
-                    default: break;
-                    }
-                }
-        }
+        const std::vector<double> aux = mcx_sim_device_aux(d->slots, d->n_slots, d->steps, d->n_steps, d->aux, d->scheme);
         e = hipMemcpy(sim->d_aux, aux.data(), sizeof(double) * aux.size(), hipMemcpyHostToDevice);
     }
     if (e == hipSuccess && d->n_chol > 0)

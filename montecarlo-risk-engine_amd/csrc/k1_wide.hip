@@ -159,11 +159,6 @@ void launch_wide(const WideArgs& a, bool inject, hipStream_t s)
     else hipLaunchKernelGGL((k1_paths_wide<CAP, false>), dim3(grid), dim3(MCX_BLOCK), 0, s, a);
 }
 
-bool wide_kind_ok(int kind)
-{
-    return kind == MCX_MODEL_BS || kind == MCX_MODEL_VASICEK || kind == MCX_MODEL_HW || kind == MCX_MODEL_CIRPP || kind == MCX_MODEL_CIRPP_DET;
-}
-
 }  // namespace
 
 extern "C" int mcx_sim_create_wide(mcx_handle* h, const mcx_wide_sim_desc* d, mcx_sim** out)
@@ -172,29 +167,8 @@ extern "C" int mcx_sim_create_wide(mcx_handle* h, const mcx_wide_sim_desc* d, mc
     if (d->n_slots < 1 || d->n_slots > MCX_WIDE_MAX_SLOTS || d->n_z != d->n_slots || d->n_state > MCX_WIDE_MAX_STATE || d->n_uniform != 0 || !d->slots)
         MCX_FAIL(h, -2, "mcx_sim_create_wide: dimensions out of range (slots %d, z %d, state %d): 1 .. MCX_WIDE_MAX_SLOTS = %d one-factor slots",
                  d->n_slots, d->n_z, d->n_state, MCX_WIDE_MAX_SLOTS);
-    for (int s = 0; s < d->n_slots; ++s)
-        if (!wide_kind_ok(d->slots[s].kind))
-            MCX_FAIL(h, -2, "mcx_sim_create_wide: slot %d (model kind %d) is not a one-factor kind of a wide model", s, d->slots[s].kind);
-    int so = 0;
-    for (int s = 0; s < d->n_slots; ++s) {
-        if (d->slots[s].state_off != so) MCX_FAIL(h, -4, "mcx_sim_create_wide: state offsets must be packed");
-        so += mcx_kind_state_dim(d->slots[s].kind);
-        const int kind = d->slots[s].kind, sc = d->scheme;
-        bool ok;
-        switch (kind) {           // the (kind, scheme) pairs of mcx_sim_create
-        case MCX_MODEL_CIRPP: ok = sc == MCX_SCHEME_EULER; break;
-        case MCX_MODEL_CIRPP_DET: ok = sc >= MCX_SCHEME_EULER && sc <= MCX_SCHEME_QE; break;
-        default: ok = sc == MCX_SCHEME_EULER || sc == MCX_SCHEME_ANALYTICAL; break;
-        }
-        if (!ok) MCX_FAIL(h, -6, "mcx_sim_create_wide: slot %d (model kind %d) has no step map for scheme %d", s, kind, sc);
-    }
-    if (so != d->n_state) MCX_FAIL(h, -4, "mcx_sim_create_wide: n_state does not match the slots");
-    for (int k = 0; k < d->n_steps; ++k) {
-        if (d->steps[k].store_idx >= d->n_dates || d->steps[k].chol_idx < 0 || d->steps[k].chol_idx >= d->n_chol)
-            MCX_FAIL(h, -5, "mcx_sim_create_wide: step %d references date/cholesky out of range", k);
-        if ((d->scheme == MCX_SCHEME_EULER || d->scheme == MCX_SCHEME_QE) && d->steps[k].chol_idx != 0)
-            MCX_FAIL(h, -5, "mcx_sim_create_wide: step %d: the EULER / QE schemes use Cholesky factor 0 for every sub-step", k);
-    }
+    if (int rc = mcx_sim_check_slots(h, "mcx_sim_create_wide", d->slots, d->n_slots, d->n_state, d->scheme, true)) return rc;
+    if (int rc = mcx_sim_check_steps(h, "mcx_sim_create_wide", d->steps, d->n_steps, d->n_dates, d->n_chol, d->scheme)) return rc;
     MCX_HIP(h, hipSetDevice(h->device));
     mcx_sim* sim = new mcx_sim();
     memset(&sim->desc, 0, sizeof(sim->desc));          // desc.slots stays empty: every reader checks `wide` first
@@ -219,21 +193,7 @@ extern "C" int mcx_sim_create_wide(mcx_handle* h, const mcx_wide_sim_desc* d, mc
     }
     if (e == hipSuccess && n_steps) e = hipMemcpy(sim->d_steps, d->steps, sizeof(mcx_step) * n_steps, hipMemcpyHostToDevice);
     if (e == hipSuccess && n_steps) {
-        std::vector<double> aux(d->aux, d->aux + n_steps * ns * MCX_AUX);
-        if (d->scheme == MCX_SCHEME_EULER) {           // the derived Euler constants, as mcx_sim_create fills them
-            for (size_t k = 0; k < n_steps; ++k)
-                for (int q = 0; q < ns; ++q) {
-                    double* a = aux.data() + (k * ns + q) * MCX_AUX;
-                    const double* p = d->slots[q].p;
-                    const double dt = d->steps[k].dt, sq = d->steps[k].sqrt_dt;
-                    switch (d->slots[q].kind) {
-                    case MCX_MODEL_BS: a[MCX_AUX_C0] = p[2] * dt; a[MCX_AUX_C2] = p[1] * sq; break;
-                    case MCX_MODEL_VASICEK: a[MCX_AUX_C0] = p[3] * p[2] * dt; a[MCX_AUX_C1] = -(p[3] * dt); a[MCX_AUX_C2] = p[1] * sq; break;
-                    case MCX_MODEL_CIRPP: a[MCX_AUX_C0] = p[0] * p[1] * dt; a[MCX_AUX_C1] = -(p[0] * dt); a[MCX_AUX_C2] = p[2] * sq; break;
-                    default: break;
-                    }
-                }
-        }
+        const std::vector<double> aux = mcx_sim_device_aux(d->slots, ns, d->steps, (int)n_steps, d->aux, d->scheme);
         e = hipMemcpy(sim->d_aux, aux.data(), sizeof(double) * aux.size(), hipMemcpyHostToDevice);
     }
     if (e == hipSuccess && d->n_chol > 0)

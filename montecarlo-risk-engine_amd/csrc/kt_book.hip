@@ -22,21 +22,9 @@
 
 #include <algorithm>
 
-#include "mcx_dual.h"
+#include "mcx_dual_step.h"
 
 namespace {
-
-constexpr int NP = MCX_TANGENT_NP;
-typedef Dual<NP> DN;
-
-__device__ __forceinline__ DN ld_dual(double v, const double* __restrict__ d)      // wave-uniform derivative row -> scalar loads
-{
-    DN r;
-    r.v = v;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) r.d[q] = ldk(d + q);
-    return r;
-}
 
 // ---- paths -------------------------------------------------------------------------------------------------------------
 struct KTPArgs {
@@ -110,63 +98,21 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_paths(const KTPArgs a)
         const double dt = sp.dt, sq = sp.sqrt_dt;
 #pragma unroll
         for (int s = 0; s < NSLOT; ++s) {
-            const double* __restrict__ p = k.slots[s].p;
-            const double* __restrict__ dp = a.dslot + (int64_t)s * MCX_SLOT_NPARAM * NP;
-            const double* __restrict__ ax = k.aux + ((int64_t)step * NSLOT + s) * MCX_AUX;
-            const double* __restrict__ dax = a.daux + ((int64_t)step * NSLOT + s) * MCX_AUX * NP;
-            const double zs = zc[s < NZ ? s : 0];
-            DN& s0 = reg[2 * s];
-            DN& s1 = reg[2 * s + 1];
-            switch (k.slots[s].kind) {
-            case MCX_MODEL_BS: {                                          // black_scholes.py:79-85
-                const DN sigma = ld_dual(p[1], dp + 1 * NP), rate = ld_dual(p[2], dp + 2 * NP);
-                s0 = s0 + (rate * s0 * dt + sigma * s0 * (sq * zs));
-                break;
-            }
-            case MCX_MODEL_VASICEK: {                                     // vasicek.py:88-112
-                const DN sigma = ld_dual(p[1], dp + 1 * NP), mean = ld_dual(p[2], dp + 2 * NP), speed = ld_dual(p[3], dp + 3 * NP);
-                const DN r = s0;
-                s1 = s1 + r * dt;
-                s0 = r + speed * (mean - r) * dt + sigma * (sq * zs);
-                break;
-            }
-            case MCX_MODEL_CIRPP: {                                       // cirpp.py:188-198
-                const DN kappa = ld_dual(p[0], dp + 0 * NP), theta = ld_dual(p[1], dp + 1 * NP), sigma = ld_dual(p[2], dp + 2 * NP);
-                const DN psi = ld_dual(ldk(ax + 0), dax + 0 * NP);
-                const DN y = s0;
-                const DN sy = dsqrt(dclamp_min(y, 0.0));
-                const DN yn = y + kappa * (theta - y) * dt + sigma * sy * (sq * zs);
-                s1 = s1 + (y + psi) * dt;
-                s0 = dclamp_min(yn, 1e-12);
-                break;
-            }
-            case MCX_MODEL_CIRPP_DET: {                                   // cirpp.py:155-172
-                s1 = s1 + ld_dual(ldk(ax + 0), dax + 0 * NP) * dt;
-                s0 = ld_dual(ldk(ax + 1), dax + 1 * NP);
-                break;
-            }
-            default: break;
-            }
+            const DualKarg p{k.slots[s].p, a.dslot + (int64_t)s * MCX_SLOT_NPARAM * NP};
+            const DualTable ax{k.aux + ((int64_t)step * NSLOT + s) * MCX_AUX, a.daux + ((int64_t)step * NSLOT + s) * MCX_AUX * NP};
+            dual_step_euler<false>(k.slots[s].kind, p, ax, dt, sq, zc[s < NZ ? s : 0], reg[2 * s], reg[2 * s + 1]);
         }
         const int st = sp.store_idx;
         if (st >= 0) ktp_store<NSLOT>(a, st, i, reg);
     }
 }
 
-// acc + l z for a dual factor entry and a plain normal: every image is one multiply-add, as the primal product's (k1_paths.hip)
-__device__ __forceinline__ DN ktp_fma(const DN& l, double z, const DN& acc)
-{
-    DN r;
-    r.v = fma(l.v, z, acc.v);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) r.d[q] = fma(l.d[q], z, acc.d[q]);
-    return r;
-}
-
 // kt_paths in its second mode: the ANALYTICAL scheme of Black-Scholes and Vasicek slots, one normal per slot.  The factor of the
 // per-dt covariance depends on the parameters: row s of it is a dual number (dchol next to k.chol, both wave-uniform), and the step
-// maps are the primal analytic branches of step_slot (mcx_device.h) in dual numbers.  Initial state, draws (the same normals as the
-// EULER mode and as K1: one Box-Muller pair per two, an odd NZ drops the last sine) and stores as kt_paths, whose code stays as it was.
+// maps are the primal analytic branches of step_slot (mcx_device.h) in dual numbers (dual_step_analytical of mcx_dual_step.h, next to
+// kt_paths' dual_step_euler).  Initial state, draws (the same normals as the EULER mode and as K1: one Box-Muller pair per two, an odd
+// NZ drops the last sine) and stores as kt_paths.  Those two loops are written out in both kernels on purpose: as one shared function
+// the initial-state loop changed the compiled code of all 16 instantiations of the two kernels, the draw loop that of 10.
 struct KTPCholArgs {
     KTPArgs p;
     const double* __restrict__ dchol;   // [n_chol][n_z][n_z][NP]
@@ -216,21 +162,9 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_paths_chol(const KTPCholArgs ca)
             DN zs = dconst<NP>(0.0);                                          // (L z)_s with the factor's tangent
 #pragma unroll
             for (int c = 0; c <= s; ++c) zs = ktp_fma(ld_dual(ldk(L + s * NZ + c), dL + (int64_t)(s * NZ + c) * NP), z[c], zs);
-            const double* __restrict__ p = k.slots[s].p;
-            const double* __restrict__ dp = a.dslot + (int64_t)s * MCX_SLOT_NPARAM * NP;
-            const double* __restrict__ ax = k.aux + ((int64_t)step * NSLOT + s) * MCX_AUX;
-            const double* __restrict__ dax = a.daux + ((int64_t)step * NSLOT + s) * MCX_AUX * NP;
-            DN& s0 = reg[2 * s];
-            DN& s1 = reg[2 * s + 1];
-            if (k.slots[s].kind == MCX_MODEL_BS) {                            // black_scholes.py:61-67
-                const DN drift = ld_dual(ldk(ax + 0), dax + 0 * NP), ito = ld_dual(ldk(ax + 1), dax + 1 * NP);
-                s0 = s0 * dexp(drift + (zs - ito));
-            } else {                                                          // MCX_MODEL_VASICEK, vasicek.py:76-86
-                const DN mean = ld_dual(p[2], dp + 2 * NP), decay = ld_dual(ldk(ax + 0), dax + 0 * NP);
-                const DN r = s0;
-                s1 = s1 + r * dt;
-                s0 = (mean + (r - mean) * decay) + zs;
-            }
+            const DualKarg p{k.slots[s].p, a.dslot + (int64_t)s * MCX_SLOT_NPARAM * NP};
+            const DualTable ax{k.aux + ((int64_t)step * NSLOT + s) * MCX_AUX, a.daux + ((int64_t)step * NSLOT + s) * MCX_AUX * NP};
+            dual_step_analytical<false>(k.slots[s].kind == MCX_MODEL_BS, k.slots[s].kind, p, ax, dt, zs, reg[2 * s], reg[2 * s + 1]);
         }
         const int st = sp.store_idx;
         if (st >= 0) ktp_store<NSLOT>(a, st, i, reg);
@@ -1086,51 +1020,30 @@ int ktp_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const do
               uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths, double* d_dpaths, int64_t ld, const double* d_inject_z,
               void* stream, const char* who, bool chol_entry)
 {
-    if (!h || !sim || !h_dslot || !h_dinit || !h_daux || !d_paths || !d_dpaths) return -1;
-    MCX_REFUSE_WIDE(h, sim, "mcx_tangent_paths / mcx_tangent_paths_chol");
+    if (int rc = mcx_tangent_check_args(h, sim, h_dslot, h_dinit, h_daux, h_dchol, chol_entry ? 1u << MCX_SCHEME_ANALYTICAL : 0u, d_paths,
+                                        d_dpaths, n_paths, ld, who, false, "mcx_tangent_paths / mcx_tangent_paths_chol"))
+        return rc > 0 ? 0 : rc;
     const mcx_sim_desc& sd = sim->desc;
     const bool analytic = chol_entry && sd.scheme == MCX_SCHEME_ANALYTICAL;
-    if (analytic && !h_dchol) return -1;
-    if (n_paths <= 0) return 0;
-    if (ld < n_paths) MCX_FAIL(h, -2, "%s: ld < n_paths", who);
     if (sd.scheme != MCX_SCHEME_EULER && !analytic)
         MCX_FAIL(h, MCX_E_NOT_FUSABLE, chol_entry ? "%s: scheme %d: EULER or ANALYTICAL scheme only" : "%s: EULER scheme only", who, (int)sd.scheme);
-    for (int s = 0; s < sd.n_slots; ++s) {
-        const int kd = sd.slots[s].kind;
-        if (analytic) {
-            if (kd != MCX_MODEL_BS && kd != MCX_MODEL_VASICEK)
-                MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: slot %d: model kind %d has no analytic tangent step", who, s, kd);
-        } else if (kd != MCX_MODEL_BS && kd != MCX_MODEL_VASICEK && kd != MCX_MODEL_CIRPP && kd != MCX_MODEL_CIRPP_DET)
-            MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: slot %d: model kind %d has no tangent step", who, s, kd);
-    }
+    if (int rc = mcx_tangent_check_kinds(h, who, sd.slots, sd.n_slots, analytic, false, nullptr)) return rc;
     if (sd.n_z != sd.n_slots) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: one normal per slot expected", who);
     if (sd.n_slots < 1 || sd.n_slots > 4) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: %d slots have no instantiation", who, sd.n_slots);
-    if (analytic) {                                       // the kernel indexes h_dchol by the steps' factor index
-        if (sd.n_chol < 1) MCX_FAIL(h, -2, "%s: no Cholesky factor", who);
-        for (int k = 0; k < sd.n_steps; ++k)
-            if (sim->h_steps[k].chol_idx < 0 || sim->h_steps[k].chol_idx >= sd.n_chol) MCX_FAIL(h, -2, "%s: step %d: factor out of range", who, k);
-    }
+    if (analytic)                                         // the kernel indexes h_dchol by the steps' factor index
+        if (int rc = mcx_tangent_check_steps(h, who, sim, sd.n_chol, false)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    KTPArgs a;
-    memset(&a, 0, sizeof(a));
+    KTPCholArgs ac;
+    memset(&ac, 0, sizeof(ac));
+    KTPArgs& a = ac.p;
     mcx_fill_k1_args(sim, seed, path_offset, n_paths, ld, d_paths, d_inject_z, nullptr, &a.k1);
-    a.dslot = (const double*)mcx_upload_table(h, 0, h_dslot, sizeof(double) * (size_t)sd.n_slots * MCX_SLOT_NPARAM * NP, s);
-    a.dinit = (const double*)mcx_upload_table(h, 1, h_dinit, sizeof(double) * (size_t)sd.n_state * NP, s);
-    a.daux = (const double*)mcx_upload_table(h, 2, h_daux, sizeof(double) * (size_t)sd.n_steps * sd.n_slots * MCX_AUX * NP, s);
-    if (!a.dslot || !a.dinit || !a.daux) return -100;
-    const double* dchol = nullptr;
-    if (analytic) {
-        dchol = (const double*)mcx_upload_table(h, 3, h_dchol, sizeof(double) * (size_t)sd.n_chol * sd.n_z * sd.n_z * NP, s);
-        if (!dchol) return -100;
-    }
+    mcx_tangent_tables t;
+    if (int rc = mcx_tangent_upload(h, sd, h_dslot, h_dinit, h_daux, analytic ? h_dchol : nullptr, s, &t)) return rc;
+    a.dslot = t.dslot; a.dinit = t.dinit; a.daux = t.daux; ac.dchol = t.dchol;
     a.dpaths = d_dpaths; a.pstride = (int64_t)sd.n_dates * sd.n_state * ld; a.n_slots = sd.n_slots;
     const int grid = (int)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK);
     const bool inj = d_inject_z != nullptr;
-    if (analytic) {
-        KTPCholArgs ac;
-        ac.p = a; ac.dchol = dchol;
-        MCX_DISPATCH(NS, sd.n_slots, 4, launch_ktp_chol<NS, NS>(ac, grid, inj, s));
-    }
+    if (analytic) { MCX_DISPATCH(NS, sd.n_slots, 4, launch_ktp_chol<NS, NS>(ac, grid, inj, s)); }
     else { MCX_DISPATCH(NS, sd.n_slots, 4, launch_ktp<NS, NS>(a, grid, inj, s)); }
     MCX_HIP(h, hipGetLastError());
     MCX_HIP(h, hipStreamSynchronize(s));
@@ -1138,6 +1051,67 @@ int ktp_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const do
 }
 
 }  // namespace
+
+// ---- shared by the dual path entry points of kt_book.hip, kt_storage.hip and kt_wide.hip (mcx_internal.h) ----------------------
+int mcx_tangent_check_args(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                           const double* h_dchol, unsigned dchol_schemes, const double* d_paths, const double* d_dpaths, int64_t n_paths,
+                           int64_t ld, const char* who, bool wide_entry, const char* narrow_who)
+{
+    if (!h || !sim || !h_dslot || !h_dinit || !h_daux || !d_paths || !d_dpaths) return -1;
+    if (wide_entry) {
+        if (!sim->wide)
+            MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: a narrow sim (mcx_sim_create) goes to mcx_tangent_paths / mcx_tangent_paths_chol; this entry "
+                     "point takes a wide sim (mcx_sim_create_wide)", who);
+    } else MCX_REFUSE_WIDE(h, sim, narrow_who);
+    const int sc = sim->desc.scheme;
+    if (!h_dchol && sc >= 0 && sc < 32 && (dchol_schemes >> sc & 1u)) return -1;
+    if (n_paths <= 0) return 1;
+    if (ld < n_paths) MCX_FAIL(h, -2, "%s: ld < n_paths", who);
+    return 0;
+}
+
+int mcx_tangent_check_kinds(mcx_handle* h, const char* who, const mcx_slot* slots, int n_slots, bool analytic, bool allow_hw, bool* has_hw)
+{
+    if (has_hw) *has_hw = false;
+    for (int s = 0; s < n_slots; ++s) {
+        const int kd = slots[s].kind;
+        if (allow_hw && kd == MCX_MODEL_HW) {
+            if (has_hw) *has_hw = true;
+            continue;
+        }
+        if (analytic) {
+            if (kd != MCX_MODEL_BS && kd != MCX_MODEL_VASICEK)
+                MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: slot %d: model kind %d has no analytic tangent step", who, s, kd);
+        } else if (kd != MCX_MODEL_BS && kd != MCX_MODEL_VASICEK && kd != MCX_MODEL_CIRPP && kd != MCX_MODEL_CIRPP_DET)
+            MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: slot %d: model kind %d has no tangent step", who, s, kd);
+    }
+    return 0;
+}
+
+int mcx_tangent_check_steps(mcx_handle* h, const char* who, const mcx_sim* sim, int n_factors, bool stores)
+{
+    const mcx_sim_desc& sd = sim->desc;
+    if (sd.n_chol < 1) MCX_FAIL(h, -2, "%s: no Cholesky factor", who);
+    for (int k = 0; k < sd.n_steps; ++k) {
+        const mcx_step& sp = sim->h_steps[k];
+        const bool factor_ok = sp.chol_idx >= 0 && sp.chol_idx < n_factors;
+        if (!stores && !factor_ok) MCX_FAIL(h, -2, "%s: step %d: factor out of range", who, k);
+        if (stores && (!factor_ok || sp.store_idx >= sd.n_dates)) MCX_FAIL(h, -2, "%s: step %d out of range", who, k);
+    }
+    return 0;
+}
+
+int mcx_tangent_upload(mcx_handle* h, const mcx_sim_desc& sd, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                       const double* h_dchol, hipStream_t s, mcx_tangent_tables* out)
+{
+    const size_t row = sizeof(double) * NP;
+    out->dslot = (const double*)mcx_upload_table(h, 0, h_dslot, row * sd.n_slots * MCX_SLOT_NPARAM, s);
+    out->dinit = (const double*)mcx_upload_table(h, 1, h_dinit, row * sd.n_state, s);
+    out->daux = (const double*)mcx_upload_table(h, 2, h_daux, row * sd.n_steps * sd.n_slots * MCX_AUX, s);
+    if (!out->dslot || !out->dinit || !out->daux) return -100;
+    out->dchol = h_dchol ? (const double*)mcx_upload_table(h, 3, h_dchol, row * sd.n_chol * sd.n_z * sd.n_z, s) : nullptr;
+    return h_dchol && !out->dchol ? -100 : 0;
+}
 
 extern "C" int mcx_tangent_paths(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
                                  uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths, double* d_dpaths, int64_t ld,
@@ -1161,37 +1135,27 @@ extern "C" int mcx_tangent_paths_heston(mcx_handle* h, const mcx_sim* sim, const
                                         double* d_dpaths, int64_t ld, const double* d_inject_z, const double* d_inject_u, void* stream)
 {
     const char* who = "mcx_tangent_paths_heston";
-    if (!h || !sim || !h_dslot || !h_dinit || !h_daux || !d_paths || !d_dpaths) return -1;
-    MCX_REFUSE_WIDE(h, sim, "mcx_tangent_paths_heston");
+    if (int rc = mcx_tangent_check_args(h, sim, h_dslot, h_dinit, h_daux, h_dchol, 1u << MCX_SCHEME_EULER, d_paths, d_dpaths, n_paths, ld, who,
+                                        false, who))
+        return rc > 0 ? 0 : rc;
     const mcx_sim_desc& sd = sim->desc;
     const bool euler = sd.scheme == MCX_SCHEME_EULER, qe = sd.scheme == MCX_SCHEME_QE;
-    if (euler && !h_dchol) return -1;
-    if (n_paths <= 0) return 0;
-    if (ld < n_paths) MCX_FAIL(h, -2, "%s: ld < n_paths", who);
     if (sd.n_slots != 1 || sd.slots[0].kind != MCX_MODEL_HESTON || sd.n_z != 2 || sd.n_state != 2 || sd.slots[0].state_off != 0)
         MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: a single Heston slot expected (%d slots, slot 0 of model kind %d)", who, (int)sd.n_slots,
                  sd.n_slots > 0 ? (int)sd.slots[0].kind : 0);
     if (!euler && !qe) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: scheme %d: EULER or QE scheme only", who, (int)sd.scheme);
     if (qe && sd.n_uniform != 1) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: one uniform per sub-step expected under QE", who);
     if (qe && d_inject_z && !d_inject_u) MCX_FAIL(h, -3, "%s: inject_u required with inject_z under QE", who);
-    if (sd.n_chol < 1) MCX_FAIL(h, -2, "%s: no Cholesky factor", who);
-    for (int k = 0; k < sd.n_steps; ++k) {                // the kernel reads factor 0 (one factor per EULER / QE run) and stores by store_idx
-        const mcx_step& sp = sim->h_steps[k];
-        if (sp.chol_idx != 0 || sp.store_idx >= sd.n_dates) MCX_FAIL(h, -2, "%s: step %d out of range", who, k);
-    }
+    // the kernel reads factor 0 (one factor per EULER / QE run) and stores by store_idx
+    if (int rc = mcx_tangent_check_steps(h, who, sim, 1, true)) return rc;
     hipStream_t s = (hipStream_t)stream;
     KTPCholArgs ac;
     memset(&ac, 0, sizeof(ac));
     KTPArgs& a = ac.p;
     mcx_fill_k1_args(sim, seed, path_offset, n_paths, ld, d_paths, d_inject_z, d_inject_u, &a.k1);
-    a.dslot = (const double*)mcx_upload_table(h, 0, h_dslot, sizeof(double) * (size_t)MCX_SLOT_NPARAM * NP, s);
-    a.dinit = (const double*)mcx_upload_table(h, 1, h_dinit, sizeof(double) * (size_t)2 * NP, s);
-    a.daux = (const double*)mcx_upload_table(h, 2, h_daux, sizeof(double) * (size_t)sd.n_steps * MCX_AUX * NP, s);
-    if (!a.dslot || !a.dinit || !a.daux) return -100;
-    if (euler) {
-        ac.dchol = (const double*)mcx_upload_table(h, 3, h_dchol, sizeof(double) * (size_t)sd.n_chol * 4 * NP, s);
-        if (!ac.dchol) return -100;
-    }
+    mcx_tangent_tables t;
+    if (int rc = mcx_tangent_upload(h, sd, h_dslot, h_dinit, h_daux, euler ? h_dchol : nullptr, s, &t)) return rc;
+    a.dslot = t.dslot; a.dinit = t.dinit; a.daux = t.daux; ac.dchol = t.dchol;
     a.dpaths = d_dpaths; a.pstride = (int64_t)sd.n_dates * 2 * ld; a.n_slots = 1;
     const int grid = (int)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK);
     const bool inj = d_inject_z != nullptr;

@@ -493,29 +493,21 @@ extern "C" int mcx_tangent_paths_s2f(mcx_handle* h, const mcx_sim* sim, const do
                                      double* d_dpaths, int64_t ld, const double* d_inject_z, void* stream)
 {
     const char* who = "mcx_tangent_paths_s2f";
-    if (!h || !sim || !h_dslot || !h_dinit || !h_daux || !h_dchol || !d_paths || !d_dpaths) return -1;
-    MCX_REFUSE_WIDE(h, sim, "mcx_tangent_paths_s2f");
-    if (n_paths <= 0) return 0;
-    if (ld < n_paths) MCX_FAIL(h, -2, "%s: ld < n_paths", who);
+    if (!h_dchol) return -1;                              // (read under both schemes)
+    if (int rc = mcx_tangent_check_args(h, sim, h_dslot, h_dinit, h_daux, h_dchol, 0u, d_paths, d_dpaths, n_paths, ld, who, false, who))
+        return rc > 0 ? 0 : rc;
     const mcx_sim_desc& sd = sim->desc;
     if (sd.n_slots != 1 || sd.slots[0].kind != MCX_MODEL_S2F || sd.n_z != 2 || sd.n_state != 3)
         MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: a single Schwartz two-factor slot expected", who);
     if (sd.scheme != MCX_SCHEME_EULER && sd.scheme != MCX_SCHEME_ANALYTICAL) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: EULER or ANALYTICAL scheme", who);
-    if (sd.n_chol < 1) MCX_FAIL(h, -2, "%s: no Cholesky factor", who);
-    for (int k = 0; k < sd.n_steps; ++k) {
-        const mcx_step& sp = sim->h_steps[k];
-        if (sp.chol_idx < 0 || sp.chol_idx >= sd.n_chol || sp.store_idx >= sd.n_dates) MCX_FAIL(h, -2, "%s: step %d out of range", who, k);
-    }
+    if (int rc = mcx_tangent_check_steps(h, who, sim, sd.n_chol, true)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const void* dslot = mcx_upload_table(h, 0, h_dslot, sizeof(double) * (size_t)MCX_SLOT_NPARAM * NP, s);
-    const void* dinit = mcx_upload_table(h, 1, h_dinit, sizeof(double) * (size_t)3 * NP, s);
-    const void* daux = mcx_upload_table(h, 2, h_daux, sizeof(double) * (size_t)sd.n_steps * MCX_AUX * NP, s);
-    const void* dchol = mcx_upload_table(h, 3, h_dchol, sizeof(double) * (size_t)sd.n_chol * 4 * NP, s);
-    if (!dslot || !dinit || !daux || !dchol) return -100;
+    mcx_tangent_tables t;
+    if (int rc = mcx_tangent_upload(h, sd, h_dslot, h_dinit, h_daux, h_dchol, s, &t)) return rc;
     KTSPathArgs a;
     memset(&a, 0, sizeof(a));
     mcx_fill_k1_args(sim, seed, path_offset, n_paths, ld, d_paths, d_inject_z, nullptr, &a.k1);
-    a.dslot = (const double*)dslot; a.dinit = (const double*)dinit; a.daux = (const double*)daux; a.dchol = (const double*)dchol;
+    a.dslot = t.dslot; a.dinit = t.dinit; a.daux = t.daux; a.dchol = t.dchol;
     a.dpaths = d_dpaths; a.pstride = (int64_t)sd.n_dates * 3 * ld;
     const int grid = (int)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK);
     if (d_inject_z) hipLaunchKernelGGL((kts_paths<true>), dim3(grid), dim3(MCX_BLOCK), 0, s, a);

@@ -11,16 +11,21 @@
 // A chunk of NP parameters therefore touches a few slots (all of them only for the shared rate of BlackScholesMulti): the dual path
 // tensor is sparse by columns.  The grid is (ceil(n / MCX_BLOCK), n_active); blockIdx.y picks a slot r from the device list of the
 // ACTIVE slots (built on the host from the tables), and one lane owns one path of that one slot:
-//   * slot record, dslot / dinit / daux rows: wave-uniform scalar loads at the point of use (ld_dual of kt_book.hip);
+//   * slot record, dslot / dinit / daux rows: wave-uniform scalar loads at the point of use (ld_dual of mcx_dual_step.h);
 //   * zc_r is formed by STREAMING the draws: for q = 0 .. r >> 1 one draw_pair<true, 7, true> on the counters (path, sub-step, q) —
 //     k1_paths_wide's call — or the injected block, accumulated as k1_paths_wide accumulates (L[r][0] z[0], then fma ascending in c;
 //     EULER row 0 is z[0] itself; an odd row end drops the pair's second normal).  No z[] array, nothing indexed at run time;
-//   * ANALYTICAL: zc is a dual number, the factor's row r carries its tangent (ktp_fma of kt_book.hip); EULER: a plain double (the
+//   * ANALYTICAL: zc is a dual number, the factor's row r carries its tangent (ktp_fma of mcx_dual_step.h); EULER: a plain double (the
 //     correlations are not model parameters);
-//   * the dual step of the slot's kind — the four EULER cases of kt_paths, the two ANALYTICAL cases of kt_paths_chol, RESTATED (sharing
-//     them through a header would have to leave every kernel of kt_book.hip with its register allocation); the two Hull-White steps
-//     (no narrow kernel has them) only in the instantiations with HW = true, which mcx_tangent_paths_wide_hw launches for a sim
-//     that holds a Hull-White slot: the plain instantiations keep the instruction stream they had without them;
+//   * the dual step of the slot's kind is the narrow kernels' own: dual_step_euler / dual_step_analytical of mcx_dual_step.h, which
+//     kt_paths and kt_paths_chol call too, here with the slot parameters read from the device table (DualTable) where the narrow
+//     kernels read the kernel-argument segment (DualKarg).  ld_dual and ktp_fma live there as well.  Sharing left every kernel of
+//     kt_book.hip instruction for instruction as it was, and this kernel's four instantiations identical (INJECT) or with the same
+//     opcode sequence under other register names (Philox): profiles/dual_step_asm_compare.md.  The two Hull-White steps (no narrow
+//     kernel has them) sit behind the maps' HW flag, set only in the instantiations which mcx_tangent_paths_wide_hw launches for a
+//     sim that holds a Hull-White slot: the plain instantiations keep the instruction stream they had without them.
+//     NOT shared, on purpose: the prologue of kt_paths / kt_paths_chol (initial state, draws) is still written out in both — one
+//     function for the initial-state loop changed the code of all 16 of their instantiations, one for the draw loop 10 of them;
 //   * only the TANGENT images of the slot's state columns are written (c, and c + 1 unless Black-Scholes: wide_store's placement).  The
 //     value image is the primal kernel's (mcx_wide_generate), so image 0 is K1's bytes; the columns of inactive slots stay at the
 //     zero the entry point's memset wrote.
@@ -28,31 +33,9 @@
 // costs sum_{r in A} ((r >> 1) + 1) pairs per path-step against n_slots / 2 of one primal run.
 #include <algorithm>
 
-#include "mcx_dual.h"
+#include "mcx_dual_step.h"
 
 namespace {
-
-constexpr int NP = MCX_TANGENT_NP;
-typedef Dual<NP> DN;
-
-__device__ __forceinline__ DN ld_dual(double v, const double* __restrict__ d)      // wave-uniform derivative row -> scalar loads
-{
-    DN r;
-    r.v = v;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) r.d[q] = ldk(d + q);
-    return r;
-}
-
-// acc + l z for a dual factor entry and a plain normal: every image is one multiply-add, as the primal product's (k1_wide.hip)
-__device__ __forceinline__ DN ktp_fma(const DN& l, double z, const DN& acc)
-{
-    DN r;
-    r.v = fma(l.v, z, acc.v);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) r.d[q] = fma(l.d[q], z, acc.d[q]);
-    return r;
-}
 
 struct KTWArgs {
     const mcx_slot* __restrict__ slots;        // device [n_slots] (mcx_sim::d_slots)
@@ -138,64 +121,10 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_paths_wide(const KTWArgs a)
                 if (both) zd = ktp_fma(ld_dual(ldk(Lr + c0 + 1), dLr + (int64_t)(c0 + 1) * NP), z1, zd);
             }
         }
-        const double* __restrict__ ax = a.aux + ((int64_t)step * ns + r) * MCX_AUX;
-        const double* __restrict__ dax = a.daux + ((int64_t)step * ns + r) * MCX_AUX * NP;
-        const double dt = sp.dt, sq = sp.sqrt_dt;
-        if (euler) {
-            switch (kind) {
-            case MCX_MODEL_BS: {                                          // black_scholes.py:79-85
-                const DN sigma = ld_dual(ldk(p + 1), dp + 1 * NP), rate = ld_dual(ldk(p + 2), dp + 2 * NP);
-                s0 = s0 + (rate * s0 * dt + sigma * s0 * (sq * zv));
-                break;
-            }
-            case MCX_MODEL_VASICEK: {                                     // vasicek.py:88-112
-                const DN sigma = ld_dual(ldk(p + 1), dp + 1 * NP), mean = ld_dual(ldk(p + 2), dp + 2 * NP);
-                const DN speed = ld_dual(ldk(p + 3), dp + 3 * NP);
-                const DN x = s0;
-                s1 = s1 + x * dt;
-                s0 = x + speed * (mean - x) * dt + sigma * (sq * zv);
-                break;
-            }
-            case MCX_MODEL_CIRPP: {                                       // cirpp.py:188-198
-                const DN kappa = ld_dual(ldk(p + 0), dp + 0 * NP), theta = ld_dual(ldk(p + 1), dp + 1 * NP);
-                const DN sigma = ld_dual(ldk(p + 2), dp + 2 * NP);
-                const DN psi = ld_dual(ldk(ax + 0), dax + 0 * NP);
-                const DN y = s0;
-                const DN sy = dsqrt(dclamp_min(y, 0.0));
-                const DN yn = y + kappa * (theta - y) * dt + sigma * sy * (sq * zv);
-                s1 = s1 + (y + psi) * dt;
-                s0 = dclamp_min(yn, 1e-12);
-                break;
-            }
-            case MCX_MODEL_CIRPP_DET: {                                   // cirpp.py:155-172
-                s1 = s1 + ld_dual(ldk(ax + 0), dax + 0 * NP) * dt;
-                s0 = ld_dual(ldk(ax + 1), dax + 1 * NP);
-                break;
-            }
-            default:
-                if (HW && kind == MCX_MODEL_HW) {                         // mcx_device.h case MCX_MODEL_HW in dual numbers; theta_k = aux[0]
-                    const DN sigma = ld_dual(ldk(p + 1), dp + 1 * NP), speed = ld_dual(ldk(p + 3), dp + 3 * NP);
-                    const DN theta = ld_dual(ldk(ax + 0), dax + 0 * NP);
-                    const DN x = s0;
-                    s1 = s1 + x * dt;
-                    s0 = x + (theta - speed * x) * dt + sigma * (sq * zv);
-                }
-                break;                                                    // (the entry point refuses every other kind)
-            }
-        } else if (bs) {                                                  // black_scholes.py:61-67
-            const DN drift = ld_dual(ldk(ax + 0), dax + 0 * NP), ito = ld_dual(ldk(ax + 1), dax + 1 * NP);
-            s0 = s0 * dexp(drift + (zd - ito));
-        } else if (HW && kind == MCX_MODEL_HW) {                          // r' = r E + shift + w, hull_white.py _step_aux
-            const DN decay = ld_dual(ldk(ax + 0), dax + 0 * NP), shift = ld_dual(ldk(ax + 1), dax + 1 * NP);
-            const DN x = s0;
-            s1 = s1 + x * dt;
-            s0 = (x * decay + shift) + zd;
-        } else {                                                          // MCX_MODEL_VASICEK, vasicek.py:76-86
-            const DN mean = ld_dual(ldk(p + 2), dp + 2 * NP), decay = ld_dual(ldk(ax + 0), dax + 0 * NP);
-            const DN x = s0;
-            s1 = s1 + x * dt;
-            s0 = (mean + (x - mean) * decay) + zd;
-        }
+        const DualTable ps{p, dp};
+        const DualTable ax{a.aux + ((int64_t)step * ns + r) * MCX_AUX, a.daux + ((int64_t)step * ns + r) * MCX_AUX * NP};
+        if (euler) dual_step_euler<HW>(kind, ps, ax, sp.dt, sp.sqrt_dt, zv, s0, s1);
+        else dual_step_analytical<HW>(bs, kind, ps, ax, sp.dt, zd, s0, s1);
         const int st = sp.store_idx;
         if (st >= 0) {
             ktw_store(a, st, col, i, s0);
@@ -218,40 +147,21 @@ int ktw_tangent_paths_wide(mcx_handle* h, const mcx_sim* sim, const double* h_ds
                            const double* h_dchol, uint64_t seed, uint64_t path_offset, int64_t n_paths, double* d_paths, double* d_dpaths,
                            int64_t ld, const double* d_inject_z, int32_t* n_active_out, void* stream, const char* who, bool allow_hw)
 {
-    if (!h || !sim || !h_dslot || !h_dinit || !h_daux || !d_paths || !d_dpaths) return -1;
-    if (!sim->wide)
-        MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: a narrow sim (mcx_sim_create) goes to mcx_tangent_paths / mcx_tangent_paths_chol; this entry "
-                 "point takes a wide sim (mcx_sim_create_wide)", who);
+    if (int rc = mcx_tangent_check_args(h, sim, h_dslot, h_dinit, h_daux, h_dchol, 1u << MCX_SCHEME_ANALYTICAL, d_paths, d_dpaths, n_paths, ld,
+                                        who, true, nullptr)) {
+        if (rc > 0 && n_active_out) *n_active_out = 0;
+        return rc > 0 ? 0 : rc;
+    }
     const mcx_sim_desc& sd = sim->desc;
     const bool euler = sd.scheme == MCX_SCHEME_EULER, analytic = sd.scheme == MCX_SCHEME_ANALYTICAL;
-    if (analytic && !h_dchol) return -1;
-    if (n_paths <= 0) {
-        if (n_active_out) *n_active_out = 0;
-        return 0;
-    }
-    if (ld < n_paths) MCX_FAIL(h, -2, "%s: ld < n_paths", who);
     if (!euler && !analytic) MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: scheme %d: EULER or ANALYTICAL scheme only", who, (int)sd.scheme);
     const int ns = sd.n_slots;
     if (ns < 1 || ns > MCX_WIDE_MAX_SLOTS || sd.n_z != ns || (int)sim->h_slots.size() != ns)
         MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: one normal per slot and 1 .. %d slots expected", who, MCX_WIDE_MAX_SLOTS);
     bool has_hw = false;
-    for (int s = 0; s < ns; ++s) {
-        const int kd = sim->h_slots[s].kind;
-        if (allow_hw && kd == MCX_MODEL_HW) {
-            has_hw = true;
-            continue;
-        }
-        if (analytic) {
-            if (kd != MCX_MODEL_BS && kd != MCX_MODEL_VASICEK)
-                MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: slot %d: model kind %d has no analytic tangent step", who, s, kd);
-        } else if (kd != MCX_MODEL_BS && kd != MCX_MODEL_VASICEK && kd != MCX_MODEL_CIRPP && kd != MCX_MODEL_CIRPP_DET)
-            MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: slot %d: model kind %d has no tangent step", who, s, kd);
-    }
-    if (sd.n_chol < 1) MCX_FAIL(h, -2, "%s: no Cholesky factor", who);
-    for (int k = 0; k < sd.n_steps; ++k) {                // the kernel indexes the factors and the dates by the steps' records
-        const mcx_step& sp = sim->h_steps[k];
-        if (sp.chol_idx < 0 || sp.chol_idx >= sd.n_chol || sp.store_idx >= sd.n_dates) MCX_FAIL(h, -2, "%s: step %d out of range", who, k);
-    }
+    if (int rc = mcx_tangent_check_kinds(h, who, sim->h_slots.data(), ns, analytic, allow_hw, &has_hw)) return rc;
+    // the kernel indexes the factors and the dates by the steps' records
+    if (int rc = mcx_tangent_check_steps(h, who, sim, sd.n_chol, true)) return rc;
     // the active slots: those a non-zero entry of the tables reaches
     int32_t active[MCX_WIDE_MAX_SLOTS];
     int n_active = 0;
@@ -267,15 +177,10 @@ int ktw_tangent_paths_wide(mcx_handle* h, const mcx_sim* sim, const double* h_ds
     KTWArgs a;
     memset(&a, 0, sizeof(a));
     if (n_active > 0) {
-        a.dslot = (const double*)mcx_upload_table(h, 0, h_dslot, sizeof(double) * (size_t)ns * MCX_SLOT_NPARAM * NP, s);
-        a.dinit = (const double*)mcx_upload_table(h, 1, h_dinit, sizeof(double) * (size_t)sd.n_state * NP, s);
-        a.daux = (const double*)mcx_upload_table(h, 2, h_daux, sizeof(double) * (size_t)sd.n_steps * ns * MCX_AUX * NP, s);
-        if (!a.dslot || !a.dinit || !a.daux) return -100;
-        a.dchol = a.dslot;                                 // (EULER: never read)
-        if (analytic) {
-            a.dchol = (const double*)mcx_upload_table(h, 3, h_dchol, sizeof(double) * (size_t)sd.n_chol * ns * ns * NP, s);
-            if (!a.dchol) return -100;
-        }
+        mcx_tangent_tables t;
+        if (int rc = mcx_tangent_upload(h, sd, h_dslot, h_dinit, h_daux, analytic ? h_dchol : nullptr, s, &t)) return rc;
+        a.dslot = t.dslot; a.dinit = t.dinit; a.daux = t.daux;
+        a.dchol = analytic ? t.dchol : t.dslot;            // (EULER: never read)
         a.active = (const int32_t*)mcx_stage_small(h, active, sizeof(int32_t) * (size_t)n_active, s);
         if (!a.active) return -100;
     }

@@ -194,12 +194,39 @@ struct mcx_sim {
 #define MCX_REFUSE_WIDE(h, sim, who)                                                                                          \
     do {                                                                                                                      \
         if ((sim)->wide)                                                                                                      \
-            MCX_FAIL(h, MCX_E_NOT_FUSABLE, who ": a wide model (%d slots; this entry point takes at most MCX_MAX_SLOTS = %d) runs "  \
-                     "through mcx_generate_paths and the unfused passes only", (sim)->desc.n_slots, MCX_MAX_SLOTS);            \
+            MCX_FAIL(h, MCX_E_NOT_FUSABLE, "%s: a wide model (%d slots; this entry point takes at most MCX_MAX_SLOTS = %d) runs "   \
+                     "through mcx_generate_paths and the unfused passes only", who, (sim)->desc.n_slots, MCX_MAX_SLOTS);       \
     } while (0)
+// k1_paths.hip: what mcx_sim_create and mcx_sim_create_wide check and derive alike (`who` fronts every message; wide: the one-factor
+// kinds only).  mcx_sim_device_aux: the aux rows as the kernels read them, the derived Euler constants above filled in
+int mcx_sim_check_slots(mcx_handle* h, const char* who, const mcx_slot* slots, int n_slots, int n_state, int scheme, bool wide);
+int mcx_sim_check_steps(mcx_handle* h, const char* who, const mcx_step* steps, int n_steps, int n_dates, int n_chol, int scheme);
+std::vector<double> mcx_sim_device_aux(const mcx_slot* slots, int n_slots, const mcx_step* steps, int n_steps, const double* h_aux, int scheme);
 // k1_wide.hip: the launch behind mcx_generate_paths / mcx_generate_paths_from_state for a wide sim
 int mcx_wide_generate(mcx_handle* h, const mcx_sim* sim, uint64_t seed, uint64_t path_offset, int64_t n_paths, int64_t ld,
                       const double* d_init_state, double* d_paths, const double* d_inject_z, void* stream);
+
+// kt_book.hip: what the dual path entry points (mcx_tangent_paths, _chol, _heston, _s2f, _wide, _wide_hw) check and upload alike; `who`
+// fronts every message.  Each entry point calls them in this order and adds its own checks before the upload: every check comes
+// before the first upload, the uploads before any output is written.
+//   mcx_tangent_check_args : -1 for a null argument (h_dchol counts under the schemes of the mask dchol_schemes, bit 1 << MCX_SCHEME_*);
+//       the refusal of a sim of the other width (wide_entry: the entry point takes a wide sim; else narrow_who names the narrow entry
+//       points in the refusal); 1 where n_paths <= 0 — nothing to do, the caller returns 0; -2 "ld < n_paths"; 0: go on
+//   mcx_tangent_check_kinds: every slot's kind has a dual step under the scheme (analytic: ANALYTICAL, else EULER); allow_hw: the
+//       caller's kernel holds the Hull-White steps too, *has_hw (nullable) tells whether a slot needs them
+//   mcx_tangent_check_steps: a factor exists and every step record stays inside what the kernel indexes by it: the factor index below
+//       n_factors (the sim's count, or 1 where the kernel reads factor 0 alone) and, with `stores`, the date index
+//   mcx_tangent_upload     : the call's derivative tables into the handle's table slots 0 .. 3 (mcx_upload_table), sized by the sim:
+//       dslot [n_slots][MCX_SLOT_NPARAM][NP], dinit [n_state][NP], daux [n_steps][n_slots][MCX_AUX][NP], dchol [n_chol][n_z][n_z][NP]
+//       (h_dchol == nullptr: not uploaded, out->dchol = nullptr); 0 or -100 with the handle's error
+struct mcx_tangent_tables { const double *dslot, *dinit, *daux, *dchol; };
+int mcx_tangent_check_args(mcx_handle* h, const mcx_sim* sim, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                           const double* h_dchol, unsigned dchol_schemes, const double* d_paths, const double* d_dpaths, int64_t n_paths,
+                           int64_t ld, const char* who, bool wide_entry, const char* narrow_who);
+int mcx_tangent_check_kinds(mcx_handle* h, const char* who, const mcx_slot* slots, int n_slots, bool analytic, bool allow_hw, bool* has_hw);
+int mcx_tangent_check_steps(mcx_handle* h, const char* who, const mcx_sim* sim, int n_factors, bool stores);
+int mcx_tangent_upload(mcx_handle* h, const mcx_sim_desc& sd, const double* h_dslot, const double* h_dinit, const double* h_daux,
+                       const double* h_dchol, hipStream_t s, mcx_tangent_tables* out);
 
 // ---- device helpers -------------------------------------------------------------------------------------------------
 // Read-only, wave-uniform table loads.  Kernel tables (sub-step table, Cholesky factors, event program, coefficients) are

@@ -71,8 +71,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_lsm_dates_moments.argtypes = [vp, vp, vp, i32, vp, i32, vp, i64, i64, vp, i64, i64, vp, i32, vp]
     lib.mcx_lsm_dates_run.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, i64, i64, vp, i64, i64, vp, i32, vp]
     lib.mcx_book_set_payoff_tangents.argtypes = [vp, vp, vp, vp]
-    lib.mcx_tangent_paths_s2f.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
-    lib.mcx_tangent_paths_chol.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
+    lib.mcx_tangent_paths.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
+    lib.mcx_tangent_paths_s2f.argtypes = lib.mcx_tangent_paths_chol.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_tangent_paths_heston.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp, vp]
     lib.mcx_tangent_paths_wide.argtypes = lib.mcx_tangent_paths_wide_hw.argtypes = _abi.TANGENT_PATHS_WIDE_ARGTYPES
     lib.mcx_sim_describe.argtypes = [C.c_void_p, C.c_void_p]
@@ -462,41 +462,38 @@ class HipBackend:
         return cfs, dcfs
 
     # ---- forward-mode pass through the exposure path (csrc/kt_book.hip) ----------------------------------------------
+    def _tangent_paths(self, entry: str, sim, dslot, dinit, daux, dchol, seed, path_offset, n_paths, inject_z, out=None, ld=None,
+                       dims=None, extra=()):
+        """what the tangent_paths* methods share: the derivative tables made contiguous and held against their shapes (dims: the
+        (n_slots, n_state, n_z) the entry point is written for, where that is not the plan's), (paths, dpaths) allocated or adopted
+        from `out` with the leading dimension ld, and the call — the library's list is the same for every entry point but for
+        mcx_tangent_paths, which takes no dchol, and for the arguments `extra` in front of the stream"""
+        plan, NP = sim.plan, _abi.TANGENT_NP
+        n_slots, n_state, n_z = dims if dims is not None else (plan.n_slots, plan.n_state, plan.n_z)
+        paths, dpaths = out if out is not None else (self.empty(plan.n_dates, plan.n_state, n_paths),
+                                                     self.empty(NP, plan.n_dates, plan.n_state, n_paths))
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (dslot, dinit, daux)]
+        assert a[0].shape == (n_slots, _abi.SLOT_NPARAM, NP) and a[1].shape == (n_state, NP)
+        assert a[2].shape == (plan.n_steps, n_slots, _abi.AUX, NP)
+        if dchol is not None:
+            dchol = np.ascontiguousarray(dchol, dtype=np.float64)
+            assert dchol.shape == (len(plan.chol), n_z, n_z, NP)
+        tables = [_abi.ptr(x) for x in a] + ([_abi.ptr(dchol) if dchol is not None else None] if entry != "mcx_tangent_paths" else [])
+        self._check(getattr(self.lib, entry)(
+            self.h, sim.ptr, *tables, seed, path_offset, n_paths, paths.data_ptr(), dpaths.data_ptr(), n_paths if ld is None else ld,
+            inject_z.data_ptr() if inject_z is not None else None, *extra, self._stream()), entry)
+        return paths, dpaths
+
     def tangent_paths(self, sim, dslot: np.ndarray, dinit: np.ndarray, daux: np.ndarray, seed: int, path_offset: int,
                       n_paths: int, inject_z=None):
-        plan = sim.plan
-        NP = _abi.TANGENT_NP
-        paths = self.empty(plan.n_dates, plan.n_state, n_paths)
-        dpaths = self.empty(NP, plan.n_dates, plan.n_state, n_paths)
-        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (dslot, dinit, daux)]
-        assert a[0].shape == (plan.n_slots, _abi.SLOT_NPARAM, NP) and a[1].shape == (plan.n_state, NP)
-        assert a[2].shape == (plan.n_steps, plan.n_slots, _abi.AUX, NP)
-        self._check(self.lib.mcx_tangent_paths(
-            self.h, sim.ptr, _abi.ptr(a[0]), _abi.ptr(a[1]), _abi.ptr(a[2]), C.c_uint64(seed), C.c_uint64(path_offset),
-            C.c_int64(n_paths), _vp(paths.data_ptr()), _vp(dpaths.data_ptr()), C.c_int64(n_paths),
-            _vp(inject_z.data_ptr() if inject_z is not None else 0), self._stream()), "mcx_tangent_paths")
-        return paths, dpaths
+        return self._tangent_paths("mcx_tangent_paths", sim, dslot, dinit, daux, None, seed, path_offset, n_paths, inject_z)
 
     def tangent_paths_chol(self, sim, dslot: np.ndarray, dinit: np.ndarray, daux: np.ndarray, dchol: np.ndarray | None, seed: int,
                            path_offset: int, n_paths: int, inject_z=None, out=None, ld: int | None = None):
         """tangent_paths with the tangent of the Cholesky factors, dchol [n_chol][n_z][n_z][NP] (mcx_tangent_paths_chol): the
         ANALYTICAL scheme of Black-Scholes / Vasicek slots; under EULER dchol may be None and the call is tangent_paths.
         out: (paths, dpaths) to write into instead of fresh tensors; ld: their leading dimension when it is not n_paths"""
-        plan = sim.plan
-        NP = _abi.TANGENT_NP
-        paths, dpaths = out if out is not None else (self.empty(plan.n_dates, plan.n_state, n_paths),
-                                                     self.empty(NP, plan.n_dates, plan.n_state, n_paths))
-        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (dslot, dinit, daux)]
-        assert a[0].shape == (plan.n_slots, _abi.SLOT_NPARAM, NP) and a[1].shape == (plan.n_state, NP)
-        assert a[2].shape == (plan.n_steps, plan.n_slots, _abi.AUX, NP)
-        if dchol is not None:
-            dchol = np.ascontiguousarray(dchol, dtype=np.float64)
-            assert dchol.shape == (len(plan.chol), plan.n_z, plan.n_z, NP)
-        self._check(self.lib.mcx_tangent_paths_chol(
-            self.h, sim.ptr, _abi.ptr(a[0]), _abi.ptr(a[1]), _abi.ptr(a[2]), _abi.ptr(dchol) if dchol is not None else None, seed,
-            path_offset, n_paths, paths.data_ptr(), dpaths.data_ptr(), n_paths if ld is None else ld,
-            inject_z.data_ptr() if inject_z is not None else None, self._stream()), "mcx_tangent_paths_chol")
-        return paths, dpaths
+        return self._tangent_paths("mcx_tangent_paths_chol", sim, dslot, dinit, daux, dchol, seed, path_offset, n_paths, inject_z, out, ld)
 
     def tangent_paths_wide(self, sim, dslot: np.ndarray, dinit: np.ndarray, daux: np.ndarray, dchol: np.ndarray | None, seed: int,
                            path_offset: int, n_paths: int, inject_z=None, out=None, ld: int | None = None,
@@ -505,21 +502,9 @@ class HipBackend:
         MCX_WIDE_MAX_SLOTS slots; dchol is read under ANALYTICAL only.  The value image is the primal path kernel's, the tangent images
         are zero except in the state columns of the ACTIVE slots (those a non-zero table entry reaches).
         -> (paths, dpaths, number of active slots)"""
-        plan = sim.plan
-        NP = _abi.TANGENT_NP
-        paths, dpaths = out if out is not None else (self.empty(plan.n_dates, plan.n_state, n_paths),
-                                                     self.empty(NP, plan.n_dates, plan.n_state, n_paths))
-        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (dslot, dinit, daux)]
-        assert a[0].shape == (plan.n_slots, _abi.SLOT_NPARAM, NP) and a[1].shape == (plan.n_state, NP)
-        assert a[2].shape == (plan.n_steps, plan.n_slots, _abi.AUX, NP)
-        if dchol is not None:
-            dchol = np.ascontiguousarray(dchol, dtype=np.float64)
-            assert dchol.shape == (len(plan.chol), plan.n_z, plan.n_z, NP)
         n_active = C.c_int32(-1)
-        self._check(getattr(self.lib, entry)(
-            self.h, sim.ptr, _abi.ptr(a[0]), _abi.ptr(a[1]), _abi.ptr(a[2]), _abi.ptr(dchol) if dchol is not None else None, seed,
-            path_offset, n_paths, paths.data_ptr(), dpaths.data_ptr(), n_paths if ld is None else ld,
-            inject_z.data_ptr() if inject_z is not None else None, C.byref(n_active), self._stream()), entry)
+        paths, dpaths = self._tangent_paths(entry, sim, dslot, dinit, daux, dchol, seed, path_offset, n_paths, inject_z, out, ld,
+                                            extra=(C.byref(n_active),))
         return paths, dpaths, int(n_active.value)
 
     def tangent_paths_wide_hw(self, sim, dslot, dinit, daux, dchol, seed: int, path_offset: int, n_paths: int, inject_z=None, out=None,
@@ -535,24 +520,11 @@ class HipBackend:
         per sub-step.  dchol [n_chol][2][2][NP]: the tangent of chol([[1, rho], [rho, 1]]), read under EULER only (QE: may be None).
         inject_z [n_steps][2][ld], inject_u [n_steps][ld].  out: (paths, dpaths) to write into instead of fresh tensors; ld: the
         leading dimension of the tensors, injected draws included, when it is not n_paths"""
-        plan = sim.plan
-        NP = _abi.TANGENT_NP
-        paths, dpaths = out if out is not None else (self.empty(plan.n_dates, plan.n_state, n_paths),
-                                                     self.empty(NP, plan.n_dates, plan.n_state, n_paths))
-        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (dslot, dinit, daux)]
-        assert a[0].shape == (1, _abi.SLOT_NPARAM, NP) and a[1].shape == (2, NP) and a[2].shape == (plan.n_steps, 1, _abi.AUX, NP)
-        if dchol is not None:
-            dchol = np.ascontiguousarray(dchol, dtype=np.float64)
-            assert dchol.shape == (len(plan.chol), 2, 2, NP)
         width = n_paths if ld is None else ld
-        for t, rows in ((inject_z, (plan.n_steps, 2)), (inject_u, (plan.n_steps,))):
+        for t, rows in ((inject_z, (sim.plan.n_steps, 2)), (inject_u, (sim.plan.n_steps,))):
             assert t is None or (t.stride(-1) == 1 and tuple(t.shape[:-1]) == rows and _ld(t) == width and t.shape[-1] == n_paths)
-        self._check(self.lib.mcx_tangent_paths_heston(
-            self.h, sim.ptr, _abi.ptr(a[0]), _abi.ptr(a[1]), _abi.ptr(a[2]), _abi.ptr(dchol) if dchol is not None else None, seed,
-            path_offset, n_paths, paths.data_ptr(), dpaths.data_ptr(), width,
-            inject_z.data_ptr() if inject_z is not None else None, inject_u.data_ptr() if inject_u is not None else None,
-            self._stream()), "mcx_tangent_paths_heston")
-        return paths, dpaths
+        return self._tangent_paths("mcx_tangent_paths_heston", sim, dslot, dinit, daux, dchol, seed, path_offset, n_paths, inject_z, out, ld,
+                                   dims=(1, 2, 2), extra=(inject_u.data_ptr() if inject_u is not None else None,))
 
     def tangent_lsm(self, book, product: int, first_event: int, num_atom: int, x_atom: int, shift: float, scale: float,
                     datoms: torch.Tensor, paths: torch.Tensor, dpaths: torch.Tensor, n_paths: int | None = None) -> np.ndarray:
@@ -976,18 +948,7 @@ class HipBackend:
     def tangent_paths_s2f(self, sim, dslot: np.ndarray, dinit: np.ndarray, daux: np.ndarray, dchol: np.ndarray, seed: int,
                           path_offset: int, n_paths: int, inject_z=None):
         """tangent_paths for a single Schwartz two-factor slot, EULER or ANALYTICAL (mcx_tangent_paths_s2f); dchol [n_chol][2][2][NP]"""
-        plan = sim.plan
-        NP = _abi.TANGENT_NP
-        paths = self.empty(plan.n_dates, plan.n_state, n_paths)
-        dpaths = self.empty(NP, plan.n_dates, plan.n_state, n_paths)
-        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (dslot, dinit, daux, dchol)]
-        assert a[0].shape == (1, _abi.SLOT_NPARAM, NP) and a[1].shape == (3, NP) and a[2].shape == (plan.n_steps, 1, _abi.AUX, NP)
-        assert a[3].shape == (len(plan.chol), 2, 2, NP)
-        self._check(self.lib.mcx_tangent_paths_s2f(
-            self.h, sim.ptr, _abi.ptr(a[0]), _abi.ptr(a[1]), _abi.ptr(a[2]), _abi.ptr(a[3]), seed, path_offset, n_paths,
-            paths.data_ptr(), dpaths.data_ptr(), n_paths, inject_z.data_ptr() if inject_z is not None else None, self._stream()),
-            "mcx_tangent_paths_s2f")
-        return paths, dpaths
+        return self._tangent_paths("mcx_tangent_paths_s2f", sim, dslot, dinit, daux, dchol, seed, path_offset, n_paths, inject_z, dims=(1, 3, 2))
 
     def book_get_coeffs(self, book) -> np.ndarray:
         out = np.zeros(len(book.plan.coeffs))

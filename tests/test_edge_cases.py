@@ -282,10 +282,17 @@ def test_library_rejects_scheme_without_step_map_and_short_replay_buffers(hip):
     try:
         for bad in (1, 3, 2):                          # MILSTEIN, QE, ANALYTICAL for Vasicek + CIR++
             desc.scheme = bad
-            with pytest.raises(RuntimeError, match="no step map"):
+            with pytest.raises(RuntimeError, match="mcx_sim_create: slot .* has no step map"):
                 hip.sim_create(sc.sim_plan)
     finally:
         desc.scheme = saved
+    saved = desc.slots[1].state_off
+    try:
+        desc.slots[1].state_off = saved + 1
+        with pytest.raises(RuntimeError, match="mcx_sim_create: state offsets must be packed"):
+            hip.sim_create(sc.sim_plan)
+    finally:
+        desc.slots[1].state_off = saved
     hip.sim_create(sc.sim_plan)
     sb, _ = cases.make_controller("bermudan_swaption", hip, inject=False)
     sb.prepare()

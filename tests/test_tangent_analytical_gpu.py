@@ -177,6 +177,24 @@ def _refused(hip, model, scheme, n=64, dchol="zeros", ld=None):
     return e.value
 
 
+def _refused_ld(hip, entry, model, scheme, n=64):
+    """mcx_tangent_paths / mcx_tangent_paths_s2f (their wrappers always pass ld = n_paths) as a C caller would call them, with
+    ld = n - 1 on zero tables and sentinel outputs; returns the error after checking that nothing was written"""
+    plan = SimPlan(model, TIMELINE, scheme, 1)
+    sim = hip.sim_create(plan)
+    out = (torch.full((plan.n_dates, plan.n_state, n), 7.0, dtype=torch.float64, device=hip.device),
+           torch.full((NP, plan.n_dates, plan.n_state, n), 7.0, dtype=torch.float64, device=hip.device))
+    tables = [np.zeros((plan.n_slots, _abi.SLOT_NPARAM, NP)), np.zeros((plan.n_state, NP)), np.zeros((plan.n_steps, plan.n_slots, _abi.AUX, NP))]
+    if entry != "mcx_tangent_paths":
+        tables.append(np.zeros((len(plan.chol), plan.n_z, plan.n_z, NP)))
+    with pytest.raises(McxError) as e:
+        hip._check(getattr(hip.lib, entry)(hip.h, sim.ptr, *[_abi.ptr(t) for t in tables], 43, 0, n, out[0].data_ptr(), out[1].data_ptr(),
+                                           n - 1, None, None), entry)
+    hip.synchronize()
+    assert bool((out[0] == 7.0).all()) and bool((out[1] == 7.0).all())
+    return e.value
+
+
 def test_refusals(hip):
     from test_hull_white import _hw
     who = "mcx_tangent_paths_chol:"
@@ -191,6 +209,9 @@ def test_refusals(hip):
     assert _refused(hip, bs, cases.A, dchol=None).code == -1
     e = _refused(hip, bs, cases.A, ld=63)
     assert e.code == -2 and who in str(e) and "ld < n_paths" in str(e), str(e)
+    for entry, model in (("mcx_tangent_paths", bs), ("mcx_tangent_paths_s2f", cases.s2f_european()[1])):
+        e = _refused_ld(hip, entry, model, cases.E)
+        assert e.code == -2 and f"{entry}: ld < n_paths" in str(e), str(e)
 
 
 # ---- end to end ---------------------------------------------------------------------------------------------------------------------

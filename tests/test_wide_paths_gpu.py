@@ -211,6 +211,7 @@ def test_every_return_code_of_sim_create_wide(hip):
         assert _create_wide(hip, plan, slots=slot_copy(3, "kind", kind)) == (-2, None), kind
     assert "MCX_WIDE_MAX_SLOTS" in hip.lib.mcx_last_error(hip.h).decode() or "wide" in hip.lib.mcx_last_error(hip.h).decode()
     assert _create_wide(hip, plan, slots=slot_copy(2, "state_off", 7)) == (-4, None)
+    assert "mcx_sim_create_wide: state offsets must be packed" in hip.lib.mcx_last_error(hip.h).decode()
     assert _create_wide(hip, plan, field("n_state", plan.n_state + 1)) == (-4, None)
     def with_step(f, v, **more):
         st = plan.steps.copy()
@@ -230,6 +231,7 @@ def test_every_return_code_of_sim_create_wide(hip):
     chol2 = np.ascontiguousarray(np.concatenate([plan.chol, plan.chol]))                        # a second factor exists, but ...
     assert _create_wide(hip, plan, with_step("chol_idx", 1, n_chol=2, chol=chol2.ctypes.data)) == (-5, None)    # ... EULER uses factor 0
     assert _create_wide(hip, plan, field("scheme", _abi.SCHEME_ANALYTICAL)) == (-6, None)       # CIR++ has no analytical step map
+    assert "mcx_sim_create_wide: slot" in hip.lib.mcx_last_error(hip.h).decode() and "has no step map" in hip.lib.mcx_last_error(hip.h).decode()
     # 1 .. 8 slots are accepted: the equality tests use it
     assert _create_wide(hip, wc.plan_of("vas_1_analytical", force_wide=True))[0] == 0
     assert _create_wide(hip, wc.plan_of("mix_8_euler", force_wide=True))[0] == 0
