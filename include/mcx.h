@@ -590,6 +590,27 @@ int  mcx_tangent_cva(mcx_handle* h, const mcx_book* book, const double* d_datoms
                      int32_t n_dates_metric, double threshold, double recovery, const double* d_expo_ns,
                      int64_t expo_tangent_stride, const double* d_paths, const double* d_dpaths, int64_t n_paths, int64_t ld,
                      int32_t n_dates, double* d_out, void* stream);
+/* Bilateral xVA with tangents, the dual of mcx_reduce_xva: one launch over the dual unsecured exposures x_m of one netting set, with
+ * c = counterparty, o = own name, S_n = S_n(0,t_m), q_n = 1 - S_n(t_m,t_{m+1}) as dual atoms and the sums over m < n_dates_metric-1:
+ *   cva = (1-R_c) sum pos(x_m) S_c q_c           dva = (1-R_o) sum neg(x_m) S_o q_o
+ *   cva_ftd = (1-R_c) sum pos(x_m) S_c q_c S_o   dva_ftd = (1-R_o) sum neg(x_m) S_o q_o S_c      bcva = cva_ftd - dva_ftd per path
+ * pos(x) = x where x.v > 0, neg(x) = -x where x.v < 0, both zero with zero tangents at x.v == 0 (torch.relu; mcx_tangent_cva).
+ * h_out [5][1+NP]: the SUMS over the local paths of the value image and of the NP tangent images of the five records, in the order
+ * above (the caller adds the ranks and divides by the global path count).  Block partials added in block order, no float atomics: two
+ * calls return identical bytes.  A pair h_surv_x / h_cond_x ([n_dates_metric-1] atom ids in `book`) may be NULL (both or neither): that
+ * name never defaults (S = 1, q = 0, zero tangents).  n_paths <= 0 or n_dates_metric <= 1: 25 zeros, nothing launched.  No device
+ * allocation per call.  Refusals (h_out untouched): -1 a NULL handle / book / buffer / h_rows / h_out; -2 ld < n_paths, half a pair
+ * of atom lists, an atom id or an exposure row (delayed rows included; a delayed row < 0 means no collateral yet) out of range, the
+ * workspace too small. */
+int  mcx_tangent_xva(mcx_handle* h, const mcx_book* book, const double* d_datoms,
+                     const int32_t* h_rows, const int32_t* h_delayed /* nullable */, int32_t collateralized,
+                     int32_t n_dates_metric, double threshold,
+                     const int32_t* h_surv_c, const int32_t* h_cond_c, double recovery_c,   /* both or neither NULL */
+                     const int32_t* h_surv_o, const int32_t* h_cond_o, double recovery_o,
+                     const double* d_expo_ns, int64_t expo_tangent_stride,
+                     const double* d_paths, const double* d_dpaths, int64_t n_paths, int64_t ld, int32_t n_dates,
+                     double* h_out /* [5][1+NP]: sums over the local paths, records cva, dva, cva_ftd, dva_ftd, bcva */,
+                     void* stream);
 
 /* K3 — Longstaff-Schwartz normal equations (controller/controller.py:316-374).
  * mcx_lsm_stats: h_out[2*i+0] = min x_i, h_out[2*i+1] = max x_i over local paths for each explanatory atom (basis centring /

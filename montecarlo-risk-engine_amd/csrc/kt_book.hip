@@ -8,6 +8,8 @@
 //              G c = r  =>  dc = G^-1 (dr - dG c)); mcx_tangent_lsm is its one-job case
 //   kt_eval  : the book's cashflow / polynomial-exposure events with dual atoms and dual coefficients
 //   kt_cva   : sum_m relu(thr(E_m)) S(0,t_m) (1 - S(t_m,t_m+1)) (1-R) per path with tangents (cva_metric.py:62-100)
+//   kt_xva   : the five bilateral xVA records (cva, dva, their first-to-default forms, bcva) with tangents, summed over the paths in
+//              the same launch (the dual of k4_xva.hip; mcx/metrics/bcva_metric.py)
 // The derivatives of every host-computed descriptor number (model parameters per slot, psi(t) tables, initial state, the
 // closed-form coefficients of each atom) arrive as arrays next to the primal descriptors (mcx/aad.py builds them).
 //   kt_lsm_step : the same for products with exercise rights (Bermudan / American / FlexiCall): the cashflow cache rolled back
@@ -784,6 +786,110 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_cva(const KTCArgs a)
     dstore(a.out, a.out + a.b.ld, a.b.ld, i, cva * a.lgd);
 }
 
+// ---- bilateral xVA with tangents: the dual of k4_xva (k4_xva.hip) ---------------------------------------------------------------
+// Per path, c the counterparty, o the own name, x_m the dual unsecured exposure and the sums over m = 0 .. n_dates-2:
+//   cva = lgd_c sum pos(x_m) S_c q_c      dva = lgd_o sum neg(x_m) S_o q_o      cva_ftd = lgd_c sum pos(x_m) (S_c q_c) S_o
+//   dva_ftd = lgd_o sum neg(x_m) (S_o q_o) S_c      bcva = cva_ftd - dva_ftd
+// pos(x) = x where x.v > 0, neg(x) = -x where x.v < 0, both zero (value and tangents) at x.v == 0: torch.relu, as kt_cva.
+// A lane owns a path (grid stride), walks the dates once and keeps the four dual accumulators in registers; the 5 (1+NP) plain sums
+// over the block's paths follow in the same launch: wave shuffles, then the wave totals of every entry added in wave order by one
+// thread per entry; one partial per block, no float atomics.  The products are written as k4_xva writes them (S q first, then times
+// the other name's S, lgd at the end), so that swapping the names and negating every exposure image runs the same arithmetic on
+// the other accumulator; bcva is the difference of the two scaled legs in a statement of its own (no contraction).
+// The reduction uses wave_sum and a [4 waves][25] table in LDS (800 B) behind ONE barrier, not block_sum: that helper takes two
+// barriers per entry, 50 for the 25 sums.
+#define KTX_R 5                                  // records: cva, dva, cva_ftd, dva_ftd, bcva
+#define KTX_N (KTX_R * (1 + NP))                 // sums per block: [record][image]
+// blocks of one launch.  The kernel holds 2 waves per SIMD (169 VGPRs, profiles/xva_tangent_resource_usage.txt: the 25 sums, four
+// dual accumulators, the dual weights and the dual exposure are live in the date loop; forcing 3 or 4 waves spills to scratch), i.e.
+// 2 blocks of 4 waves per CU: 2 x 256 CUs of the MI355X fill every wave slot the kernel can hold in ONE round, and more paths than
+// 512 x 256 take the grid stride.  A constant, not a multiple of the device's CU count: the partials [grid][25] and their sum fit
+// the workspace on every device, and the sums of a book do not depend on the device's size
+constexpr int KT_XVA_GRID_CAP = 512;
+// the partials of a full grid fit the handle's workspace and its pinned buffer: mcx_tangent_xva's workspace refusal cannot be reached
+static_assert(sizeof(double) * KT_XVA_GRID_CAP * KTX_N <= MCX_WS_BYTES && sizeof(double) * KT_XVA_GRID_CAP * KTX_N <= MCX_PINNED_BYTES,
+              "kt_xva: the block partials of a full grid exceed the handle's workspace or pinned buffer");
+
+struct KTXSide {                                 // one name: atom ids per date (device, [n_dates-1]); surv == nullptr: never defaults
+    const int32_t* __restrict__ surv;
+    const int32_t* __restrict__ cond;
+    double lgd;
+};
+
+struct KTXArgs {
+    KTBook b;
+    const double* __restrict__ expo;           // [1+NP][n_rows][ld] of ONE netting set (stride ex_stride between tangents)
+    const int32_t* __restrict__ rows;
+    const int32_t* __restrict__ delayed;
+    KTXSide c, o;
+    double* __restrict__ partials;             // [gridDim.x][KTX_R][1+NP]
+    int64_t ex_stride;
+    double threshold;
+    int32_t n_dates, collateralized;
+};
+
+// S(0, t_m) and q = 1 - S(t_m, t_m+1) of one name; a name without atoms: the dual constants 1 and 0
+__device__ __forceinline__ void ktx_side(const KTBook& b, const KTXSide& s, int m, int64_t i, DN& S, DN& q)
+{
+    S = dconst<NP>(1.0); q = dconst<NP>(0.0);
+    if (s.surv) {                                                   // wave-uniform
+        const int sa = ldk(s.surv + m), ca = ldk(s.cond + m);
+        S = kt_atom(b, ldk_struct(&b.atoms[sa]), sa, i);
+        q = 1.0 - kt_atom(b, ldk_struct(&b.atoms[ca]), ca, i);
+    }
+}
+
+__global__ __launch_bounds__(MCX_BLOCK) void kt_xva(const KTXArgs a)
+{
+    __shared__ double wsum[MCX_BLOCK / MCX_WAVE][KTX_N];
+    double acc[KTX_N];
+#pragma unroll
+    for (int k = 0; k < KTX_N; ++k) acc[k] = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x; i < a.b.n; i += (int64_t)gridDim.x * MCX_BLOCK) {
+        DN cva = dconst<NP>(0.0), dva = dconst<NP>(0.0), cftd = dconst<NP>(0.0), dftd = dconst<NP>(0.0);
+        for (int m = 0; m < a.n_dates - 1; ++m) {
+            const DN x = kt_unsecured(a.expo, a.ex_stride, a.rows, a.delayed, a.collateralized, a.threshold, a.b.ld, m, i);
+            DN ep = dconst<NP>(0.0), en = dconst<NP>(0.0);          // relu: the gradient passes where the leg is strictly positive
+            if (x.v > 0.0) ep = x;
+            else if (x.v < 0.0) en = 0.0 - x;
+            // one name's two atoms at a time: q is dead once the weight S q is formed (the live set decides the occupancy)
+            DN Sc, So, q;
+            ktx_side(a.b, a.c, m, i, Sc, q);
+            const DN wc = Sc * q;
+            ktx_side(a.b, a.o, m, i, So, q);
+            const DN wo = So * q;
+            cva = cva + ep * wc;
+            dva = dva + en * wo;
+            cftd = cftd + ep * (wc * So);
+            dftd = dftd + en * (wo * Sc);
+        }
+        DN v[KTX_R];
+        v[0] = cva * a.c.lgd;
+        v[1] = dva * a.o.lgd;
+        v[2] = cftd * a.c.lgd;
+        v[3] = dftd * a.o.lgd;
+        v[4] = v[2] - v[3];
+#pragma unroll
+        for (int r = 0; r < KTX_R; ++r) {
+            acc[r * (1 + NP)] += v[r].v;
+#pragma unroll
+            for (int q = 0; q < NP; ++q) acc[r * (1 + NP) + 1 + q] += v[r].d[q];
+        }
+    }
+    const int lane = threadIdx.x & (MCX_WAVE - 1), w = threadIdx.x / MCX_WAVE;
+#pragma unroll
+    for (int k = 0; k < KTX_N; ++k) {
+        const double t = wave_sum(acc[k]);
+        if (lane == 0) wsum[w][k] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < KTX_N) {
+        double t = 0.0;
+        for (int q = 0; q < MCX_BLOCK / MCX_WAVE; ++q) t += wsum[q][threadIdx.x];
+        a.partials[(int64_t)blockIdx.x * KTX_N + threadIdx.x] = t;
+    }
+}
+
 // ---- EPE / ENE profile tangents: sum_i 1[u > 0] du and sum_i 1[u < 0] du per metric date (epe_metric.py, ene_metric.py) -----
 struct KTFArgs {
     const double* __restrict__ expo;           // [1+NP][n_rows][ld] of one netting set
@@ -1012,6 +1118,14 @@ bool kt_upload_rows(mcx_handle* h, const int32_t* h_rows, const int32_t* h_delay
     a->rows = (const int32_t*)mcx_upload_table(h, 0, h_rows, sizeof(int32_t) * (size_t)n, s);
     a->delayed = h_delayed ? (const int32_t*)mcx_upload_table(h, 1, h_delayed, sizeof(int32_t) * (size_t)n, s) : nullptr;
     return a->rows && (a->delayed || !h_delayed);
+}
+
+// the survival / conditional-survival atom ids of one name, [n] each, against the book (mcx_tangent_cva, mcx_tangent_xva)
+int kt_check_name_atoms(mcx_handle* h, const mcx_book* b, const char* who, const int32_t* h_surv, const int32_t* h_cond, int n)
+{
+    for (int m = 0; m < n; ++m)
+        if (h_surv[m] < 0 || h_surv[m] >= b->n_atoms || h_cond[m] < 0 || h_cond[m] >= b->n_atoms) MCX_FAIL(h, -2, "%s: atom out of range", who);
+    return 0;
 }
 
 // mcx_tangent_paths and mcx_tangent_paths_chol.  `chol_entry`: the latter, which also takes the ANALYTICAL scheme of Black-Scholes /
@@ -1283,8 +1397,7 @@ extern "C" int mcx_tangent_cva(mcx_handle* h, const mcx_book* b, const double* d
 {
     if (!h || !b || !d_datoms || !h_rows || !h_surv || !h_cond || !d_expo_ns || !d_paths || !d_dpaths || !d_out) return -1;
     if (n_paths <= 0 || n_dates_metric < 1) return 0;
-    for (int m = 0; m < n_dates_metric - 1; ++m)
-        if (h_surv[m] < 0 || h_surv[m] >= b->n_atoms || h_cond[m] < 0 || h_cond[m] >= b->n_atoms) MCX_FAIL(h, -2, "mcx_tangent_cva: atom out of range");
+    if (int rc = kt_check_name_atoms(h, b, "mcx_tangent_cva", h_surv, h_cond, n_dates_metric - 1)) return rc;
     hipStream_t s = (hipStream_t)stream;
     KTCArgs a;
     memset(&a, 0, sizeof(a));
@@ -1298,6 +1411,63 @@ extern "C" int mcx_tangent_cva(mcx_handle* h, const mcx_book* b, const double* d
     hipLaunchKernelGGL(kt_cva, dim3((unsigned)((n_paths + MCX_BLOCK - 1) / MCX_BLOCK)), dim3(MCX_BLOCK), 0, s, a);
     MCX_HIP(h, hipGetLastError());
     MCX_HIP(h, hipStreamSynchronize(s));
+    return 0;
+}
+
+extern "C" int mcx_tangent_xva(mcx_handle* h, const mcx_book* b, const double* d_datoms, const int32_t* h_rows, const int32_t* h_delayed,
+                               int32_t collateralized, int32_t n_dates_metric, double threshold,
+                               const int32_t* h_surv_c, const int32_t* h_cond_c, double recovery_c,
+                               const int32_t* h_surv_o, const int32_t* h_cond_o, double recovery_o,
+                               const double* d_expo_ns, int64_t expo_tangent_stride, const double* d_paths, const double* d_dpaths,
+                               int64_t n_paths, int64_t ld, int32_t n_dates, double* h_out, void* stream)
+{
+    const char* who = "mcx_tangent_xva";
+    if (!h || !b || !d_datoms || !h_rows || !d_expo_ns || !d_paths || !d_dpaths || !h_out) return -1;
+    if (n_paths <= 0 || n_dates_metric <= 1) { memset(h_out, 0, sizeof(double) * KTX_N); return 0; }
+    // every check comes before the first upload: a refused call enqueues nothing and leaves h_out as it was
+    if (ld < n_paths) MCX_FAIL(h, -2, "%s: leading dimension < n_paths", who);
+    if (!h_surv_c != !h_cond_c || !h_surv_o != !h_cond_o)
+        MCX_FAIL(h, -2, "%s: the survival and conditional-survival atoms of a name come together (both or neither)", who);
+    const int nd = n_dates_metric - 1;
+    if (h_surv_c) if (int rc = kt_check_name_atoms(h, b, who, h_surv_c, h_cond_c, nd)) return rc;
+    if (h_surv_o) if (int rc = kt_check_name_atoms(h, b, who, h_surv_o, h_cond_o, nd)) return rc;
+    for (int m = 0; m < n_dates_metric; ++m)          // the rows index the netting set's exposure block of the book
+        if (h_rows[m] < 0 || h_rows[m] >= b->n_expo_rows || (h_delayed && h_delayed[m] >= b->n_expo_rows))
+            MCX_FAIL(h, -2, "%s: exposure row of metric date %d out of range", who, m);
+    hipStream_t s = (hipStream_t)stream;
+    const int grid = mcx_grid_for(n_paths, MCX_BLOCK, KT_XVA_GRID_CAP);
+    KTXArgs a;
+    memset(&a, 0, sizeof(a));
+    const size_t part_bytes = sizeof(double) * (size_t)grid * KTX_N;
+    if (part_bytes > h->ws_bytes || part_bytes > h->pinned_bytes) MCX_FAIL(h, -2, "%s: workspace too small", who);
+    a.partials = h->d_ws;
+    if (int rc = fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b)) return rc;
+    if (!kt_upload_rows(h, h_rows, h_delayed, n_dates_metric, &a, s)) return -100;
+    a.c.lgd = 1.0 - recovery_c; a.o.lgd = 1.0 - recovery_o;
+    if (h_surv_c || h_surv_o) {                       // the atom ids of both names in one staged table
+        std::vector<int32_t> ids;
+        const int32_t* lists[4] = {h_surv_c, h_cond_c, h_surv_o, h_cond_o};
+        for (int q = 0; q < 4; ++q)
+            if (lists[q]) ids.insert(ids.end(), lists[q], lists[q] + nd);
+        const int32_t* d_ids = (const int32_t*)mcx_stage_small(h, ids.data(), sizeof(int32_t) * ids.size(), s);
+        if (!d_ids) return -100;
+        if (h_surv_c) { a.c.surv = d_ids; a.c.cond = d_ids + nd; d_ids += 2 * nd; }
+        if (h_surv_o) { a.o.surv = d_ids; a.o.cond = d_ids + nd; }
+    }
+    a.expo = d_expo_ns; a.ex_stride = expo_tangent_stride; a.threshold = threshold;
+    a.n_dates = n_dates_metric; a.collateralized = collateralized;
+    hipLaunchKernelGGL(kt_xva, dim3(grid), dim3(MCX_BLOCK), 0, s, a);
+    MCX_HIP(h, hipGetLastError());
+    // the block partials (at most 512 x 25 doubles) through the pinned buffer, added in block order on the host as
+    // mcx_tangent_profiles adds its own (mcx_partials_to_host's k_sum_partials took 0.124 ms here against the kernel's 0.490 ms at
+    // 1,048,576 paths: profiles/xva_tangent_finishing_launch.csv)
+    MCX_HIP(h, hipMemcpyAsync(h->h_pinned, a.partials, part_bytes, hipMemcpyDeviceToHost, s));
+    MCX_HIP(h, hipStreamSynchronize(s));
+    const double* part = (const double*)h->h_pinned;
+    double sums[KTX_N] = {};
+    for (int q = 0; q < grid; ++q)
+        for (int k = 0; k < KTX_N; ++k) sums[k] += part[(size_t)q * KTX_N + k];
+    memcpy(h_out, sums, sizeof(sums));
     return 0;
 }
 

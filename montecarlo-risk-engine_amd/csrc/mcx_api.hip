@@ -17,8 +17,8 @@ extern "C" int mcx_create(mcx_handle** out, int device_id)
     h->device = device_id;
     if (hipGetDeviceProperties(&h->prop, device_id) != hipSuccess) { delete h; return -4; }
     h->n_cu = h->prop.multiProcessorCount;
-    h->ws_bytes = 8u << 20;
-    h->pinned_bytes = 1u << 20;
+    h->ws_bytes = MCX_WS_BYTES;
+    h->pinned_bytes = MCX_PINNED_BYTES;
     h->small_bytes = 4u << 20; h->small_cursor = 0;
     h->small_stream = nullptr; h->small_stream_valid = false;
     h->d_ws = nullptr; h->h_pinned = nullptr; h->d_small = nullptr; h->h_small = nullptr; h->d_acc = nullptr; h->d_pinned_alias = nullptr;

@@ -17,6 +17,8 @@
 #define MCX_WAVE 64           // CDNA4 wavefront
 #define MCX_BLOCK 256         // 4 waves: one per SIMD of a CU
 #define MCX_MAX_PARTIAL_BLOCKS 1024
+// sizes of a handle's reduction workspace (d_ws) and of its pinned staging buffer (h_pinned), fixed at mcx_create
+constexpr size_t MCX_WS_BYTES = 8u << 20, MCX_PINNED_BYTES = 1u << 20;
 
 struct mcx_handle {
     int device;

@@ -20,6 +20,8 @@ mcx_tangent_paths_wide (csrc/kt_wide.hip: one block row per slot the chunk's par
 With `SimulationController.tangent_hull_white` a book under 1 to 32 one-factor sub-models of which at least one is Hull-White takes it
 on the dual paths of mcx_tangent_paths_wide_hw (`hull_white_route`), in passes over the LIVE parameters only: a curve node beyond the
 book's horizon reaches no descriptor number, its rows are exact zeros without a pass.
+With `SimulationController.tangent_xva` the five records of DVAMetric / BilateralCVAMetric take their tangents from mcx_tangent_xva
+(csrc/kt_book.hip kt_xva; `xva_route`, `_scatter_xva`) on whichever of these passes serves the book; without it such a metric bumps.
 
 Every other configuration (`run_with_bumps`): sensitivities through the LSM regression — CVA / EPE / PFE greeks, SURVEY §8f
 rank 1, reference test `tests/pytests/test_cva_large_netting_set_aad_vs_fd.py` — are computed by CENTRAL DIFFERENCES WITH
@@ -417,6 +419,18 @@ def wide_route(sc) -> bool:
         and not any(getattr(p, "is_storage", False) for p in sc.products)
 
 
+_XVA_TYPES = (MetricType.DVA, MetricType.BCVA)
+
+
+def xva_route(sc) -> bool:
+    """Host only: do DVAMetric / BilateralCVAMetric take their tangents from mcx_tangent_xva (csrc/kt_book.hip kt_xva, the dual of
+    k4_xva)?  Only with SimulationController.tangent_xva on a backend with the binding, and only for the native metrics (a subclass
+    with a host form of its own is evaluated by that form, which has no dual).  Otherwise one such metric sends the whole book to
+    bump-and-revalue.  Independent of the path routes: the scatter reads the dual images of a pass, whichever kernel made them."""
+    return bool(getattr(sc, "tangent_xva", False)) and hasattr(sc.backend, "tangent_xva") \
+        and all(m._native for m in sc.risk_metrics.metrics if m.metric_type in _XVA_TYPES)
+
+
 def hull_white_route(sc) -> bool:
     """Host only: do the book's dual paths come from mcx_tangent_paths_wide_hw (csrc/kt_wide.hip kt_paths_wide<., true>: the per-slot
     kernel with the two Hull-White dual steps)?  Only with SimulationController.tangent_hull_white on a backend with the binding, for
@@ -489,6 +503,8 @@ def _tangent_book_routes(sc):
             and not hull_white_route(sc):
         raise _NoTangentForm("scheme")
     if any(m.metric_type not in _SCATTER or not m._native for m in sc.risk_metrics.metrics):
+        raise _NoTangentForm("metric")
+    if any(m.metric_type in _XVA_TYPES for m in sc.risk_metrics.metrics) and not xva_route(sc):
         raise _NoTangentForm("metric")
     batched = _batch_tangent_lsm(sc)
     if any(p.get_num_states() > 1 for p in sc.products) and not hasattr(sc.backend, "tangent_lsm_step"):
@@ -832,8 +848,25 @@ def _scatter_cva(ctx, chunk, ns, m_i, m, img, out):
         out[0][j] = _mean_over_paths(ctx, cva[1 + q])
 
 
+def _scatter_xva(ctx, chunk, ns, m_i, m, img, out):
+    """DVAMetric / BilateralCVAMetric: the five records (cva, dva, cva_ftd, dva_ftd, bcva) with their tangents from ONE
+    mcx_tangent_xva launch and ONE collective of its 25 sums.  The netting set's counterparty gates the bilateral metric as it gates
+    CVAMetric (a gated set keeps its zero rows, nothing is launched); the own name never gates, and DVAMetric has no counterparty"""
+    if m.metric_type == MetricType.BCVA and ns.set.counterparty_id is not None and m.counterparty_id != ns.set.counterparty_id:
+        return
+    (cp_atoms, cp_recovery), (own_atoms, own_recovery) = ctx.base._xva_atoms[m_i]
+    sums = ctx.be.tangent_xva(ctx.base.book, chunk.datoms, ctx.rows, cp_atoms, cp_recovery, own_atoms, own_recovery, ns.set.threshold,
+                              img.expo, ns.i, img.paths, img.dpaths, ns.delayed, ns.coll)
+    mean = ctx.shard.all_reduce_np(sums) / float(ctx.sc.num_paths_mainsim)
+    records = range(5) if m.metric_type == MetricType.BCVA else (1,)          # BilateralCVAMetric.EVALUATIONS order; dva alone
+    for e_i, r in enumerate(records):
+        for q, j in enumerate(chunk.sel):
+            out[e_i][j] = float(mean[r, 1 + q])
+
+
 _SCATTER = {MetricType.PV: _scatter_pv, MetricType.CVA: _scatter_cva, MetricType.PFE: _scatter_pfe, MetricType.EPE: _scatter_profile,
-            MetricType.ENE: _scatter_profile, MetricType.CE: _scatter_profile, MetricType.EEPE: _scatter_profile}
+            MetricType.ENE: _scatter_profile, MetricType.CE: _scatter_profile, MetricType.EEPE: _scatter_profile,
+            MetricType.DVA: _scatter_xva, MetricType.BCVA: _scatter_xva}
 
 
 def _scatter_metric_tangents(ctx, chunk, img, grads):

@@ -299,6 +299,11 @@ class SimulationController:
         # mcx_tangent_paths_wide_hw (mcx/aad.py hull_white_route), in passes over the live parameters only; False: such a book keeps
         # bump-and-revalue.  A model without a Hull-White slot is never touched.  Never armed together with tangent_payoffs
         self.tangent_hull_white = False
+        # differentiate=True: True keeps a book whose RiskMetrics holds a native DVAMetric or BilateralCVAMetric on the forward-mode
+        # book pass: their five records take their tangents from mcx_tangent_xva (mcx/aad.py _scatter_xva), one launch and one
+        # collective per netting set, metric and pass; False: one such metric sends the whole book to bump-and-revalue.  Independent
+        # of the path-route flags above: the scatter reads only the dual images of a pass, so it composes with every route
+        self.tangent_xva = False
         self._force_wide_plan = False    # set by aad._clone_controller only: build the SimPlan with force_wide=True
         # The reference compiles nothing: every run_simulation() sees the current state of its products / metrics.  Re-using the
         # compiled descriptors and the uploaded book of the previous run is an opt-in for callers that re-run an UNCHANGED
