@@ -771,6 +771,24 @@ int  mcx_reduce_xva(mcx_handle* h, const mcx_book* book, const mcx_unsecured_des
                     const int32_t* h_surv_o, const int32_t* h_cond_o, double recovery_o,
                     const double* d_expo_ns, const double* d_paths, int64_t n_paths, int64_t ld_expo, int64_t ld_paths,
                     mcx_acc* h_out, void* stream);
+/* mcx_reduce_fva     : funding valuation adjustment in one pass over the unsecured exposures u_m, c = counterparty, o = own name,
+ *                      per path with w_m = S_c(0,t_m) S_o(0,t_m) and the sums over m < n_dates-1:
+ *                        h_out[0] fca = sum relu( u_m) w_m h_w_borrow[m]            (funding cost)
+ *                        h_out[1] fba = sum relu(-u_m) w_m h_w_lend[m]              (funding benefit)
+ *                        h_out[2] fva = fca - fba, PER PATH (positive = cost)
+ *                      h_surv_c / h_surv_o: [n_dates-1] atom ids in `book`, or NULL: that name never defaults (S = 1).
+ *                      h_w_borrow / h_w_lend: [n_dates-1] host tables of the deterministic funding weights
+ *                      1 - exp(-int_{t_m}^{t_m+1} s(u) du); any finite value is taken as it is.  One launch (csrc/k4_fva.hip) + the
+ *                      second stage of every K4 reduction; no float atomics, no device allocation.  Path-sliced views of padded
+ *                      tensors are accepted (ld_* >= n_paths).
+ *                      Refusals (h_out untouched): -1 a NULL handle / book / descriptor / buffer / weight table / h_out; -2 a
+ *                      leading dimension below n_paths, an atom id, an exposure row or a delayed row out of range, or a workspace
+ *                      too small for the partials.  n_paths <= 0 zeroes h_out[3] and launches nothing; n_dates == 1 gives three
+ *                      records whose mean is an exact 0. */
+int  mcx_reduce_fva(mcx_handle* h, const mcx_book* book, const mcx_unsecured_desc* u,
+                    const int32_t* h_surv_c, const int32_t* h_surv_o, const double* h_w_borrow, const double* h_w_lend,
+                    const double* d_expo_ns, const double* d_paths, int64_t n_paths, int64_t ld_expo, int64_t ld_paths,
+                    mcx_acc* h_out, void* stream);
 /* materialise unsecured exposures for pluggable metrics: d_out [n_dates][ld_out] */
 int  mcx_unsecured(mcx_handle* h, const mcx_unsecured_desc* u, const double* d_expo_ns, int64_t n_paths, int64_t ld,
                    double* d_out, int64_t ld_out, void* stream);

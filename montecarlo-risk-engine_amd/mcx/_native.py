@@ -29,7 +29,7 @@ _EXPORTS = [
     "mcx_storage_create", "mcx_storage_destroy", "mcx_storage_lsm_step", "mcx_storage_lsm_run", "mcx_storage_eval",
     "mcx_storage_lsm_step_batch", "mcx_storage_lsm_solve_batch", "mcx_storage_lsm_run_batch",
     "mcx_tangent_storage_lsm_step", "mcx_tangent_storage_eval", "mcx_tangent_paths_s2f", "mcx_tangent_paths_heston", "mcx_tangent_paths_wide", "mcx_tangent_paths_wide_hw",
-    "mcx_reduce_vector", "mcx_reduce_profiles", "mcx_reduce_cva", "mcx_reduce_xva", "mcx_unsecured", "mcx_select_hist", "mcx_select_hist_dev", "mcx_select_narrow", "mcx_select_bracket", "mcx_select_hist_rows",
+    "mcx_reduce_vector", "mcx_reduce_profiles", "mcx_reduce_cva", "mcx_reduce_xva", "mcx_reduce_fva", "mcx_unsecured", "mcx_select_hist", "mcx_select_hist_dev", "mcx_select_narrow", "mcx_select_bracket", "mcx_select_hist_rows",
 ]
 
 
@@ -72,6 +72,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_lsm_dates_run.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, i64, i64, vp, i64, i64, vp, i32, vp]
     lib.mcx_book_set_payoff_tangents.argtypes = [vp, vp, vp, vp]
     lib.mcx_tangent_xva.argtypes = [vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, f64, vp, vp, f64, vp, i64, vp, vp, i64, i64, i32, vp, vp]
+    lib.mcx_reduce_fva.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp]
     lib.mcx_tangent_paths.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_tangent_paths_s2f.argtypes = lib.mcx_tangent_paths_chol.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_tangent_paths_heston.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp, vp]
@@ -1032,6 +1033,23 @@ class HipBackend:
             C.c_double(own_recovery),
             _vp(expo_ns.data_ptr()), _vp(paths.data_ptr()), C.c_int64(n), C.c_int64(_ld(expo_ns)), C.c_int64(_ld(paths)),
             _abi.ptr(out), self._stream()), "mcx_reduce_xva")
+        return out
+
+    def reduce_fva(self, book, unsec, cp_surv, own_surv, w_borrow, w_lend, expo_ns: torch.Tensor, paths: torch.Tensor) -> np.ndarray:
+        """mcx_reduce_fva: the records of (fca, fba, fva).  cp_surv / own_surv: the S(0,t_k) atom id list of the counterparty and of
+        the own name, or None for a name that never defaults; w_borrow / w_lend: the n_dates-1 funding weights of each leg"""
+        n = expo_ns.shape[1]
+        unsec.desc.n_rows = expo_ns.shape[0]
+        sc, so = [None if ids is None else np.ascontiguousarray(ids, dtype=np.int32) for ids in (cp_surv, own_surv)]
+        wb, wl = [np.ascontiguousarray(w, dtype=np.float64).reshape(-1) for w in (w_borrow, w_lend)]
+        assert len(wb) == len(wl) == unsec.n_dates - 1, "one funding weight per interval of the metric timeline"
+        if unsec.n_dates == 1:                      # (an empty numpy array has no address to hand over)
+            wb = wl = np.zeros(1)
+        out = np.zeros(3, dtype=_abi.ACC_DTYPE)
+        self._check(self.lib.mcx_reduce_fva(
+            self.h, book.ptr, C.byref(unsec.desc), _abi.ptr(sc), _abi.ptr(so), _abi.ptr(wb), _abi.ptr(wl),
+            _vp(expo_ns.data_ptr()), _vp(paths.data_ptr()), C.c_int64(n), C.c_int64(_ld(expo_ns)), C.c_int64(_ld(paths)),
+            _abi.ptr(out), self._stream()), "mcx_reduce_fva")
         return out
 
     def unsecured(self, unsec, expo_ns: torch.Tensor) -> torch.Tensor:

@@ -18,7 +18,7 @@ _MODULES = [
     "maths.maths", "maths.regression",
     "metrics.metric", "metrics.risk_metrics", "metrics.pv_metric", "metrics.ce_metric", "metrics.epe_metric",
     "metrics.ene_metric", "metrics.eepe_metric", "metrics.pfe_metric", "metrics.cva_metric",
-    "metrics.dva_metric", "metrics.bcva_metric",
+    "metrics.dva_metric", "metrics.bcva_metric", "metrics.fva_metric",
     "models.model", "models.model_config", "models.black_scholes", "models.heston", "models.vasicek", "models.cirpp",
     "models.hull_white", "models.black_scholes_multi", "models.schwartz_two_factor",
     "products.product", "products.equity", "products.bond", "products.swap", "products.european_option",

@@ -25,7 +25,7 @@ from ..common.packages import FLOAT, device
 from ..engine.engine import MonteCarloEngine
 from ..helpers.host_threads import single_threaded_host
 from ..maths.regression import PolyomialRegression, RegressionFunction, regression_centering
-from ..metrics.metric import Metric, MetricType, mean_and_error
+from ..metrics.metric import Metric, MetricType, XvaMetricType, mean_and_error
 from ..metrics.risk_metrics import PathwisePrimitive, RiskMetrics
 from ..models.model import Model
 from ..models.model_config import ModelConfig
@@ -685,6 +685,14 @@ class SimulationController:
             elif m.metric_type == MetricType.BCVA and m._native:
                 self._xva_atoms[m_i] = ((side(m.counterparty_id, m.survival_prob_requests, m.cond_survival_prob_requests), m.recovery_rate),
                                         (side(m.own_id, m.own_survival_prob_requests, m.own_cond_survival_prob_requests), m.own_recovery_rate))
+        # FVAMetric (mcx_reduce_fva): the S(0,t_k) atom per date of each named party, metric -> (counterparty ids | None, own ids |
+        # None).  Through atoms again, so FVA and bilateral CVA on the same names share one RiskMetrics
+        self._fva_atoms = {}
+        for m_i, m in enumerate(rm.metrics):
+            if m.metric_type == XvaMetricType.FVA and m._native:
+                self._fva_atoms[m_i] = tuple(
+                    None if name is None else [comp.atom(reqs[(k, name)], name, mt[k]) for k in range(len(mt) - 1)]
+                    for name, reqs in ((m.counterparty_id, m.survival_prob_requests), (m.own_id, m.own_survival_prob_requests)))
         self._comp = comp
         n_state = sum(s.state_dim for s in self.model._slots())
         self._plan_args = (prods, len(self.netting_sets), E if want_expo else 0, off, want_cfs, want_expo, n_state)
@@ -1146,7 +1154,7 @@ class SimulationController:
 
     # ---- main simulation: metrics (controller.py:506-563) ----------------------------------------------------------
     def _zero_metric_result(self, metric: Metric):
-        if metric.metric_type == MetricType.BCVA:
+        if metric.metric_type in (MetricType.BCVA, XvaMetricType.FVA):
             return [(0.0, 0.0) for _ in metric.EVALUATIONS]
         n = 1 if metric.metric_type in {MetricType.PV, MetricType.CVA, MetricType.DVA, MetricType.EEPE} else len(self.metric_exposure_timeline)
         return [(0.0, 0.0) for _ in range(n)]
@@ -1292,6 +1300,12 @@ class SimulationController:
                     and getattr(metric, "counterparty_id", None) != ns.counterparty_id:   # (the own name never gates; nor does DVA)
                 out.append(self._zero_metric_result(metric))                           # controller.py:536-542
                 continue
+            # FVAMetric: gated like CVA, but only by a counterparty it names (None applies to every set); one metric date has no
+            # interval to fund, on either route
+            if mt == XvaMetricType.FVA and ((ns.counterparty_id is not None and metric.counterparty_id is not None
+                                             and metric.counterparty_id != ns.counterparty_id) or unsec.n_dates < 2):
+                out.append(self._zero_metric_result(metric))
+                continue
             if mt == MetricType.PV and metric.evaluation_type == Metric.EvaluationType.ANALYTICAL:
                 val, err = 0.0, 0.0
                 if has_pathwise:
@@ -1299,7 +1313,8 @@ class SimulationController:
                 out.append([(analytical_acc[m_i] + val, err)])
                 continue
             # (DVA / bilateral CVA on a backend without reduce_xva: the plugin route with the metric's host form)
-            if not metric._native or (mt in (MetricType.DVA, MetricType.BCVA) and not hasattr(be, "reduce_xva")):
+            if not metric._native or (mt in (MetricType.DVA, MetricType.BCVA) and not hasattr(be, "reduce_xva")) \
+                    or (mt == XvaMetricType.FVA and not hasattr(be, "reduce_fva")):
                 out.append(self._evaluate_plugin_metric(metric, ns, unsec, expo_ns, cfs, ns_i, paths))
                 continue
             if mt == MetricType.PV:
@@ -1326,6 +1341,11 @@ class SimulationController:
                 rec = be.reduce_xva(self.book, unsec, cp_atoms, cp_recovery, own_atoms, own_recovery, expo_ns, paths)
                 g = shard.all_gather_np(rec.view(np.float64).reshape(5, 4))          # [world][5][4]
                 out.append([mean_and_error(g[:, e]) for e in (range(5) if mt == MetricType.BCVA else (1,))])
+            elif mt == XvaMetricType.FVA:
+                cp_surv, own_surv = self._fva_atoms[m_i]
+                rec = be.reduce_fva(self.book, unsec, cp_surv, own_surv, metric.w_borrow, metric.w_lend, expo_ns, paths)
+                g = shard.all_gather_np(rec.view(np.float64).reshape(3, 4))          # [world][3][4]
+                out.append([mean_and_error(g[:, e]) for e in range(3)])
             elif mt == MetricType.PFE:
                 q = metric.q_index(n_total)
                 edge = q == 0 or q == n_total - 1
@@ -1405,6 +1425,8 @@ class SimulationController:
         if not all(m._native for m in rm.metrics):
             return None
         if any(m.metric_type in (MetricType.DVA, MetricType.BCVA) for m in rm.metrics):   # no fused form: K1 -> K2 -> K4 (k4_xva)
+            return None
+        if any(m.metric_type == XvaMetricType.FVA for m in rm.metrics):                    # nor for FVA: K1 -> K2 -> K4 (k4_fva)
             return None
         want_expo = rm.requires_exposure_profiles()
         kinds = {m.metric_type for m in rm.metrics}

@@ -2,7 +2,12 @@
 
 Built-in metrics are evaluated by fused HIP reductions (csrc/k4_reduce.hip, k5_select.hip); this module keeps the
 Metrics *API* (types, names, request registration, `evaluate` signature) and the host-side finalisation of the
-accumulator records the kernels return (mean and Monte-Carlo error, metric.py:26-35)."""
+accumulator records the kernels return (mean and Monte-Carlo error, metric.py:26-35).
+
+Two enums carry the metric types.  `MetricType` is the reference's member set plus DVA and BCVA and stays closed.  Later members of
+the xVA stack live in `XvaMetricType` (FVA so far).  Every dispatch on `metric.metric_type` (controller.py, aad.py) compares members
+or tests membership in a set, tuple or dict and none indexes a table, so a member of the second enum falls through every branch
+written for the first, and `Metric.get_name()` still gives its lower-case name ("fva")."""
 from __future__ import annotations
 
 import math
@@ -25,6 +30,10 @@ class MetricType(Enum):
     CVA = "Credit Valuation Adjustment"
     DVA = "Debit Valuation Adjustment"
     BCVA = "Bilateral Credit Valuation Adjustment"
+
+
+class XvaMetricType(Enum):
+    FVA = "Funding Valuation Adjustment"
 
 
 def combine_acc(recs: np.ndarray) -> tuple[float, float, float]:

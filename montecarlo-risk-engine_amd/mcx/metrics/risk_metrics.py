@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from ..common.packages import FLOAT, device
-from .metric import Metric, MetricType
+from .metric import Metric, MetricType, XvaMetricType
 
 
 class PathwisePrimitive(Enum):
@@ -22,7 +22,9 @@ class RiskMetrics:
         kinds = {m.metric_type for m in metrics}
         self.metrics = metrics
         self.any_pv = MetricType.PV in kinds
-        self.any_xva = bool(kinds & {MetricType.CVA, MetricType.DVA, MetricType.BCVA})
+        # (an FVAMetric needs credit models only for the parties it names: with no names it runs under any model)
+        self.any_xva = bool(kinds & {MetricType.CVA, MetricType.DVA, MetricType.BCVA}) or any(
+            m.metric_type == XvaMetricType.FVA and m.get_counterparty_ids() for m in metrics)
         self.any_exposure = bool(kinds - {MetricType.PV})
         if self.any_exposure and dates.size == 0:
             raise AssertionError("For exposure simulation at least one exposure time point needs to be provided.")
