@@ -611,6 +611,26 @@ int  mcx_tangent_xva(mcx_handle* h, const mcx_book* book, const double* d_datoms
                      const double* d_paths, const double* d_dpaths, int64_t n_paths, int64_t ld, int32_t n_dates,
                      double* h_out /* [5][1+NP]: sums over the local paths, records cva, dva, cva_ftd, dva_ftd, bcva */,
                      void* stream);
+/* FVA with tangents, the dual of mcx_reduce_fva: one launch over the dual unsecured exposures x_m of one netting set, with
+ * S_n = S_n(0,t_m) as dual atoms, the funding weights phi_b / phi_l as constants (no tangent) and the sums over m < n_dates_metric-1:
+ *   w = S_c S_o      fca = sum pos(x_m) (w phi_b(m))      fba = sum neg(x_m) (w phi_l(m))      fva = fca - fba per path
+ * pos / neg as mcx_tangent_xva (torch.relu: zero in every image at x.v == 0, the closed threshold band included).
+ * h_out [3][1+NP]: the SUMS over the local paths of the value image and of the NP tangent images of (fca, fba, fva) (the caller adds
+ * the ranks and divides by the global path count).  Block partials added in block order, no float atomics: two calls return identical
+ * bytes.  h_surv_c / h_surv_o ([n_dates_metric-1] atom ids in `book`) may each be NULL: that name never defaults (S = 1, zero
+ * tangents).  h_w_borrow / h_w_lend: [n_dates_metric-1], host.  n_paths <= 0 or n_dates_metric <= 1: 15 zeros, nothing launched.  No
+ * device allocation per call.  Refusals (h_out untouched, a message set): -1 a NULL handle / book / buffer / h_rows / weight table /
+ * h_out; -2 ld < n_paths, an atom id or an exposure row (delayed rows included; a delayed row < 0 means no collateral yet) out of
+ * range, the workspace too small. */
+int  mcx_tangent_fva(mcx_handle* h, const mcx_book* book, const double* d_datoms,
+                     const int32_t* h_rows, const int32_t* h_delayed /* nullable */, int32_t collateralized,
+                     int32_t n_dates_metric, double threshold,
+                     const int32_t* h_surv_c /* nullable */, const int32_t* h_surv_o /* nullable */,
+                     const double* h_w_borrow, const double* h_w_lend,
+                     const double* d_expo_ns, int64_t expo_tangent_stride,
+                     const double* d_paths, const double* d_dpaths, int64_t n_paths, int64_t ld, int32_t n_dates,
+                     double* h_out /* [3][1+NP]: sums over the local paths, records fca, fba, fva */,
+                     void* stream);
 
 /* K3 — Longstaff-Schwartz normal equations (controller/controller.py:316-374).
  * mcx_lsm_stats: h_out[2*i+0] = min x_i, h_out[2*i+1] = max x_i over local paths for each explanatory atom (basis centring /

@@ -890,6 +890,95 @@ __global__ __launch_bounds__(MCX_BLOCK) void kt_xva(const KTXArgs a)
     }
 }
 
+// ---- FVA with tangents: the dual of k4_fva (k4_fva.hip) -------------------------------------------------------------------------
+// Per path, c the counterparty, o the own name, x_m the dual unsecured exposure and the sums over m = 0 .. n_dates-2:
+//   w = S_c(0,t_m) S_o(0,t_m)      fca = sum pos(x_m) (w phi_b(m))      fba = sum neg(x_m) (w phi_l(m))      fva = fca - fba
+// pos / neg as kt_xva (torch.relu: both legs zero in every image at x.v == 0, the closed threshold band included).  A name without
+// atoms is the dual constant 1 (wave-uniform test).  The weights phi are constants of the model parameters: plain doubles without a
+// tangent, read wave-uniformly (scalar loads) from a staged table, as k4_fva reads them.
+// The products are the Dual operators of mcx_dual.h, not explicit fma: under -ffp-contract=on a tangent a.d b.v + a.v b.d contracts
+// inside the operator, but the product of a summand and its addition to the accumulator are two statements and stay two roundings
+// (k4_fva's value leg is one fma: the two value images agree to a rounding per date, not bit for bit).  The association is k4_fva's
+// (w, then w phi, then times the leg), so swapping the two weight tables and negating every exposure image runs the same arithmetic
+// on the other accumulator; with no names and unit weights every product is exact and fca is the sequential sum of pos(x_m), image
+// by image.  fva is the difference of the two finished legs in a statement of its own.
+// Launch shape and reduction: those of kt_xva (a lane owns a path with a grid stride; wave_sum, a [4 waves][15] table in LDS, 480 B,
+// behind ONE barrier; one partial per block, no float atomics).
+#define KTV_R 3                                  // records: fca, fba, fva (FVAMetric.EVALUATIONS)
+#define KTV_N (KTV_R * (1 + NP))                 // sums per block: [record][image]
+// blocks of one launch.  The kernel holds 4 waves per SIMD (profiles/fva_tangent_resource_usage.txt), i.e. 4 blocks of 4 waves per
+// CU: 4 x 256 CUs of the MI355X fill every wave slot the kernel can hold in ONE round; more paths than 1024 x 256 take the grid
+// stride.  A constant, as KT_XVA_GRID_CAP: the sums of a book do not depend on the device's size
+constexpr int KT_FVA_GRID_CAP = 1024;
+// the partials of a full grid fit the handle's workspace and its pinned buffer: mcx_tangent_fva's workspace refusal cannot be reached
+static_assert(sizeof(double) * KT_FVA_GRID_CAP * KTV_N <= MCX_WS_BYTES && sizeof(double) * KT_FVA_GRID_CAP * KTV_N <= MCX_PINNED_BYTES,
+              "kt_fva: the block partials of a full grid exceed the handle's workspace or pinned buffer");
+
+struct KTVArgs {
+    KTBook b;
+    const double* __restrict__ expo;           // [1+NP][n_rows][ld] of ONE netting set (stride ex_stride between tangents)
+    const int32_t* __restrict__ rows;
+    const int32_t* __restrict__ delayed;
+    const int32_t* __restrict__ surv_c;        // device [n_dates-1] atom ids of S_c(0,t_m), or nullptr: the counterparty never defaults
+    const int32_t* __restrict__ surv_o;        // the same for the own name
+    const double* __restrict__ w_borrow;       // device [n_dates-1]
+    const double* __restrict__ w_lend;
+    double* __restrict__ partials;             // [gridDim.x][KTV_R][1+NP]
+    int64_t ex_stride;
+    double threshold;
+    int32_t n_dates, collateralized;
+};
+
+__global__ __launch_bounds__(MCX_BLOCK) void kt_fva(const KTVArgs a)
+{
+    __shared__ double wsum[MCX_BLOCK / MCX_WAVE][KTV_N];
+    double acc[KTV_N];
+#pragma unroll
+    for (int k = 0; k < KTV_N; ++k) acc[k] = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * MCX_BLOCK + threadIdx.x; i < a.b.n; i += (int64_t)gridDim.x * MCX_BLOCK) {
+        DN fca = dconst<NP>(0.0), fba = dconst<NP>(0.0);
+        for (int m = 0; m < a.n_dates - 1; ++m) {
+            const DN x = kt_unsecured(a.expo, a.ex_stride, a.rows, a.delayed, a.collateralized, a.threshold, a.b.ld, m, i);
+            DN ep = dconst<NP>(0.0), en = dconst<NP>(0.0);          // relu: the gradient passes where the leg is strictly positive
+            if (x.v > 0.0) ep = x;
+            else if (x.v < 0.0) en = 0.0 - x;
+            DN Sc = dconst<NP>(1.0), So = dconst<NP>(1.0);
+            if (a.surv_c) {                                         // wave-uniform tests
+                const int sa = ldk(a.surv_c + m);
+                Sc = kt_atom(a.b, ldk_struct(&a.b.atoms[sa]), sa, i);
+            }
+            if (a.surv_o) {
+                const int sa = ldk(a.surv_o + m);
+                So = kt_atom(a.b, ldk_struct(&a.b.atoms[sa]), sa, i);
+            }
+            const DN w = Sc * So;
+            const DN wb = w * ldk(a.w_borrow + m), wl = w * ldk(a.w_lend + m);
+            fca = fca + ep * wb;
+            fba = fba + en * wl;
+        }
+        const DN fva = fca - fba;
+        acc[0] += fca.v; acc[1 + NP] += fba.v; acc[2 * (1 + NP)] += fva.v;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            acc[1 + q] += fca.d[q];
+            acc[(1 + NP) + 1 + q] += fba.d[q];
+            acc[2 * (1 + NP) + 1 + q] += fva.d[q];
+        }
+    }
+    const int lane = threadIdx.x & (MCX_WAVE - 1), w = threadIdx.x / MCX_WAVE;
+#pragma unroll
+    for (int k = 0; k < KTV_N; ++k) {
+        const double t = wave_sum(acc[k]);
+        if (lane == 0) wsum[w][k] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < KTV_N) {
+        double t = 0.0;
+        for (int q = 0; q < MCX_BLOCK / MCX_WAVE; ++q) t += wsum[q][threadIdx.x];
+        a.partials[(int64_t)blockIdx.x * KTV_N + threadIdx.x] = t;
+    }
+}
+
 // ---- EPE / ENE profile tangents: sum_i 1[u > 0] du and sum_i 1[u < 0] du per metric date (epe_metric.py, ene_metric.py) -----
 struct KTFArgs {
     const double* __restrict__ expo;           // [1+NP][n_rows][ld] of one netting set
@@ -1467,6 +1556,68 @@ extern "C" int mcx_tangent_xva(mcx_handle* h, const mcx_book* b, const double* d
     double sums[KTX_N] = {};
     for (int q = 0; q < grid; ++q)
         for (int k = 0; k < KTX_N; ++k) sums[k] += part[(size_t)q * KTX_N + k];
+    memcpy(h_out, sums, sizeof(sums));
+    return 0;
+}
+
+extern "C" int mcx_tangent_fva(mcx_handle* h, const mcx_book* b, const double* d_datoms, const int32_t* h_rows, const int32_t* h_delayed,
+                               int32_t collateralized, int32_t n_dates_metric, double threshold,
+                               const int32_t* h_surv_c, const int32_t* h_surv_o, const double* h_w_borrow, const double* h_w_lend,
+                               const double* d_expo_ns, int64_t expo_tangent_stride, const double* d_paths, const double* d_dpaths,
+                               int64_t n_paths, int64_t ld, int32_t n_dates, double* h_out, void* stream)
+{
+    const char* who = "mcx_tangent_fva";
+    if (!h) return -1;
+    if (!b || !d_datoms || !h_rows || !h_w_borrow || !h_w_lend || !d_expo_ns || !d_paths || !d_dpaths || !h_out)
+        MCX_FAIL(h, -1, "%s: a NULL book, buffer, row list, weight table or h_out", who);
+    if (n_paths <= 0 || n_dates_metric <= 1) { memset(h_out, 0, sizeof(double) * KTV_N); return 0; }
+    // every check comes before the first upload: a refused call enqueues nothing and leaves h_out as it was
+    if (ld < n_paths) MCX_FAIL(h, -2, "%s: leading dimension < n_paths", who);
+    const int nd = n_dates_metric - 1;
+    const int32_t* lists[2] = {h_surv_c, h_surv_o};
+    for (int q = 0; q < 2; ++q)
+        for (int m = 0; lists[q] && m < nd; ++m)
+            if (lists[q][m] < 0 || lists[q][m] >= b->n_atoms) MCX_FAIL(h, -2, "%s: atom out of range", who);
+    for (int m = 0; m < n_dates_metric; ++m)          // the rows index the netting set's exposure block of the book
+        if (h_rows[m] < 0 || h_rows[m] >= b->n_expo_rows || (h_delayed && h_delayed[m] >= b->n_expo_rows))
+            MCX_FAIL(h, -2, "%s: exposure row of metric date %d out of range", who, m);
+    hipStream_t s = (hipStream_t)stream;
+    const int grid = mcx_grid_for(n_paths, MCX_BLOCK, KT_FVA_GRID_CAP);
+    KTVArgs a;
+    memset(&a, 0, sizeof(a));
+    const size_t part_bytes = sizeof(double) * (size_t)grid * KTV_N;
+    if (part_bytes > h->ws_bytes || part_bytes > h->pinned_bytes) MCX_FAIL(h, -2, "%s: workspace too small", who);
+    a.partials = h->d_ws;
+    if (int rc = fill_book(h, b, d_datoms, d_paths, d_dpaths, n_paths, ld, n_dates, &a.b)) return rc;
+    if (!kt_upload_rows(h, h_rows, h_delayed, n_dates_metric, &a, s)) return -100;
+    {                                                 // the two weight tables in one staged table, the atom ids in another
+        std::vector<double> wts(h_w_borrow, h_w_borrow + nd);
+        wts.insert(wts.end(), h_w_lend, h_w_lend + nd);
+        const double* d_w = (const double*)mcx_stage_small(h, wts.data(), sizeof(double) * wts.size(), s);
+        if (!d_w) return -100;
+        a.w_borrow = d_w; a.w_lend = d_w + nd;
+    }
+    if (h_surv_c || h_surv_o) {
+        std::vector<int32_t> ids;
+        for (int q = 0; q < 2; ++q)
+            if (lists[q]) ids.insert(ids.end(), lists[q], lists[q] + nd);
+        const int32_t* d_ids = (const int32_t*)mcx_stage_small(h, ids.data(), sizeof(int32_t) * ids.size(), s);
+        if (!d_ids) return -100;
+        if (h_surv_c) { a.surv_c = d_ids; d_ids += nd; }
+        if (h_surv_o) a.surv_o = d_ids;
+    }
+    a.expo = d_expo_ns; a.ex_stride = expo_tangent_stride; a.threshold = threshold;
+    a.n_dates = n_dates_metric; a.collateralized = collateralized;
+    hipLaunchKernelGGL(kt_fva, dim3(grid), dim3(MCX_BLOCK), 0, s, a);
+    MCX_HIP(h, hipGetLastError());
+    // the block partials (at most KT_FVA_GRID_CAP x 15 doubles) through the pinned buffer, added in block order on the host, as
+    // mcx_tangent_xva adds its own
+    MCX_HIP(h, hipMemcpyAsync(h->h_pinned, a.partials, part_bytes, hipMemcpyDeviceToHost, s));
+    MCX_HIP(h, hipStreamSynchronize(s));
+    const double* part = (const double*)h->h_pinned;
+    double sums[KTV_N] = {};
+    for (int q = 0; q < grid; ++q)
+        for (int k = 0; k < KTV_N; ++k) sums[k] += part[(size_t)q * KTV_N + k];
     memcpy(h_out, sums, sizeof(sums));
     return 0;
 }

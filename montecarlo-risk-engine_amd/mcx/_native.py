@@ -23,7 +23,7 @@ _EXPORTS = [
     "mcx_comm_unique_id", "mcx_comm_init", "mcx_comm_destroy", "mcx_allreduce_f64", "mcx_allgather_f64",
     "mcx_book_create", "mcx_book_destroy", "mcx_book_set_coeffs", "mcx_eval_book", "mcx_eval_book_describe", "mcx_resolve_atoms",
     "mcx_lsm_stats", "mcx_lsm_step", "mcx_lsm_run", "mcx_lsm_solve", "mcx_lsm_step_batch", "mcx_lsm_step_batch_dev", "mcx_lsm_solve_batch", "mcx_lsm_run_batch", "mcx_lsm_dates_moments", "mcx_lsm_dates_run", "mcx_book_get_coeffs", "mcx_book_set_coeffs_batch", "mcx_book_set_bridge_rng", "mcx_book_set_exercise_replay", "mcx_book_set_payoff_tangents",
-    "mcx_fused_is_straight_line", "mcx_tangent_paths", "mcx_tangent_paths_chol", "mcx_tangent_lsm", "mcx_tangent_lsm_batch", "mcx_tangent_lsm_step", "mcx_tangent_eval", "mcx_tangent_cva", "mcx_tangent_xva", "mcx_tangent_profiles", "mcx_tangent_pick",
+    "mcx_fused_is_straight_line", "mcx_tangent_paths", "mcx_tangent_paths_chol", "mcx_tangent_lsm", "mcx_tangent_lsm_batch", "mcx_tangent_lsm_step", "mcx_tangent_eval", "mcx_tangent_cva", "mcx_tangent_xva", "mcx_tangent_fva", "mcx_tangent_profiles", "mcx_tangent_pick",
     "mcx_box_muller", "mcx_tangent_european", "mcx_fused_create", "mcx_fused_destroy", "mcx_fused_num_records", "mcx_fused_run", "mcx_fused_eval_paths", "mcx_fused_run_device", "mcx_fused_eval_paths_device", "mcx_fused_set_timing", "mcx_fused_kernel_times", "mcx_fused_describe",
     "mcx_value_poly_fit", "mcx_book_collapse_values", "mcx_book_value_poly_info", "mcx_rows_minmax",
     "mcx_storage_create", "mcx_storage_destroy", "mcx_storage_lsm_step", "mcx_storage_lsm_run", "mcx_storage_eval",
@@ -72,6 +72,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.mcx_lsm_dates_run.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, i64, i64, vp, i64, i64, vp, i32, vp]
     lib.mcx_book_set_payoff_tangents.argtypes = [vp, vp, vp, vp]
     lib.mcx_tangent_xva.argtypes = [vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, f64, vp, vp, f64, vp, i64, vp, vp, i64, i64, i32, vp, vp]
+    lib.mcx_tangent_fva.argtypes = [vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp, vp, vp, i64, vp, vp, i64, i64, i32, vp, vp]
     lib.mcx_reduce_fva.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp]
     lib.mcx_tangent_paths.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
     lib.mcx_tangent_paths_s2f.argtypes = lib.mcx_tangent_paths_chol.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, i64, vp, vp, i64, vp, vp]
@@ -660,6 +661,36 @@ class HipBackend:
             C.c_double(own_recovery), _vp(expo[0, ns_i].data_ptr()), C.c_int64(expo.stride(0)), _vp(paths.data_ptr()),
             _vp(dpaths.data_ptr()), C.c_int64(n), C.c_int64(ld), C.c_int32(paths.shape[0]), _abi.ptr(out), self._stream()),
             "mcx_tangent_xva")
+        return out
+
+    def tangent_fva(self, book, datoms: torch.Tensor, rows, cp_surv, own_surv, w_borrow, w_lend, threshold: float, expo: torch.Tensor,
+                    ns_i: int, paths: torch.Tensor, dpaths: torch.Tensor, delayed=None, collateralized=False,
+                    n_paths: int | None = None, out: np.ndarray | None = None) -> np.ndarray:
+        """mcx_tangent_fva -> [3][1+NP] (written into `out` when given): the sums over the local paths of the value image and the NP
+        tangent images of (fca, fba, fva).  cp_surv / own_surv: the S(0,t_k) atom id list of the counterparty and of the own name, or
+        None for a name that never defaults; w_borrow / w_lend: the n_dates-1 funding weights of each leg (constants: no tangent).
+        expo [1+NP][NS][rows][n], paths [T][D][n], dpaths [NP][T][D][n] share their leading dimension; they may be path slices of
+        padded tensors (n_paths: the paths that count, default all n of them)"""
+        NP = _abi.TANGENT_NP
+        ld = _ld(paths)
+        n = paths.shape[-1] if n_paths is None else int(n_paths)
+        assert n <= paths.shape[-1] and _ld(dpaths) == ld and _ld(expo) == ld and dpaths.shape[0] == NP
+        assert dpaths.stride(0) == paths.shape[0] * paths.stride(0) and expo.shape[0] == 1 + NP
+        dl = None if delayed is None else np.ascontiguousarray(delayed, dtype=np.int32)
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        sc, so = [None if ids is None else np.ascontiguousarray(ids, dtype=np.int32) for ids in (cp_surv, own_surv)]
+        wb, wl = [np.ascontiguousarray(w, dtype=np.float64).reshape(-1) for w in (w_borrow, w_lend)]
+        assert len(wb) == len(wl) == max(len(r) - 1, 0), "one funding weight per interval of the metric timeline"
+        if len(wb) == 0:                            # (an empty numpy array has no address to hand over)
+            wb = wl = np.zeros(1)
+        if out is None:
+            out = np.zeros((3, 1 + NP))
+        assert out.dtype == np.float64 and out.shape == (3, 1 + NP) and out.flags["C_CONTIGUOUS"]
+        self._check(self.lib.mcx_tangent_fva(
+            self.h, book.ptr, _vp(datoms.data_ptr()), _abi.ptr(r), _abi.ptr(dl), C.c_int32(int(collateralized)), C.c_int32(len(r)),
+            C.c_double(threshold), _abi.ptr(sc), _abi.ptr(so), _abi.ptr(wb), _abi.ptr(wl), _vp(expo[0, ns_i].data_ptr()),
+            C.c_int64(expo.stride(0)), _vp(paths.data_ptr()), _vp(dpaths.data_ptr()), C.c_int64(n), C.c_int64(ld),
+            C.c_int32(paths.shape[0]), _abi.ptr(out), self._stream()), "mcx_tangent_fva")
         return out
 
     def tangent_profiles(self, rows, threshold: float, expo: torch.Tensor, ns_i: int, delayed=None, collateralized=False,

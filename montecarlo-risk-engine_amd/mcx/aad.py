@@ -22,6 +22,8 @@ on the dual paths of mcx_tangent_paths_wide_hw (`hull_white_route`), in passes o
 book's horizon reaches no descriptor number, its rows are exact zeros without a pass.
 With `SimulationController.tangent_xva` the five records of DVAMetric / BilateralCVAMetric take their tangents from mcx_tangent_xva
 (csrc/kt_book.hip kt_xva; `xva_route`, `_scatter_xva`) on whichever of these passes serves the book; without it such a metric bumps.
+With `SimulationController.tangent_fva` the three records of FVAMetric take theirs from mcx_tangent_fva (kt_fva, the dual of k4_fva;
+`fva_route`, `_scatter_fva`) in the same way; the two flags are independent, and a book that holds both families needs both.
 
 Every other configuration (`run_with_bumps`): sensitivities through the LSM regression — CVA / EPE / PFE greeks, SURVEY §8f
 rank 1, reference test `tests/pytests/test_cva_large_netting_set_aad_vs_fd.py` — are computed by CENTRAL DIFFERENCES WITH
@@ -51,7 +53,7 @@ import numpy as np
 
 from . import _abi
 from .maths.regression import regression_centering
-from .metrics.metric import MetricType, mean_and_error
+from .metrics.metric import MetricType, XvaMetricType, mean_and_error
 from .models.black_scholes import BlackScholesModel
 from .models.heston import HestonModel
 from .plan import SimPlan, UnsecuredSpec
@@ -431,6 +433,14 @@ def xva_route(sc) -> bool:
         and all(m._native for m in sc.risk_metrics.metrics if m.metric_type in _XVA_TYPES)
 
 
+def fva_route(sc) -> bool:
+    """Host only: does FVAMetric take its tangents from mcx_tangent_fva (csrc/kt_book.hip kt_fva, the dual of k4_fva)?  Only with
+    SimulationController.tangent_fva on a backend with the binding, and only for the native metrics, as xva_route.  Otherwise one
+    FVAMetric sends the whole book to bump-and-revalue.  Independent of tangent_xva and of the path routes"""
+    return bool(getattr(sc, "tangent_fva", False)) and hasattr(sc.backend, "tangent_fva") \
+        and all(m._native for m in sc.risk_metrics.metrics if m.metric_type == XvaMetricType.FVA)
+
+
 def hull_white_route(sc) -> bool:
     """Host only: do the book's dual paths come from mcx_tangent_paths_wide_hw (csrc/kt_wide.hip kt_paths_wide<., true>: the per-slot
     kernel with the two Hull-White dual steps)?  Only with SimulationController.tangent_hull_white on a backend with the binding, for
@@ -505,6 +515,8 @@ def _tangent_book_routes(sc):
     if any(m.metric_type not in _SCATTER or not m._native for m in sc.risk_metrics.metrics):
         raise _NoTangentForm("metric")
     if any(m.metric_type in _XVA_TYPES for m in sc.risk_metrics.metrics) and not xva_route(sc):
+        raise _NoTangentForm("metric")
+    if any(m.metric_type == XvaMetricType.FVA for m in sc.risk_metrics.metrics) and not fva_route(sc):
         raise _NoTangentForm("metric")
     batched = _batch_tangent_lsm(sc)
     if any(p.get_num_states() > 1 for p in sc.products) and not hasattr(sc.backend, "tangent_lsm_step"):
@@ -864,9 +876,25 @@ def _scatter_xva(ctx, chunk, ns, m_i, m, img, out):
             out[e_i][j] = float(mean[r, 1 + q])
 
 
+def _scatter_fva(ctx, chunk, ns, m_i, m, img, out):
+    """FVAMetric: the three records (fca, fba, fva) with their tangents from ONE mcx_tangent_fva launch and ONE collective of its 15
+    sums.  Gated as the primal metric (controller.py): only by a counterparty the metric names (None applies to every set) against a
+    set that has one; a gated set keeps its zero rows, nothing is launched.  The own name never gates.  The funding weights are
+    constants of the model parameters"""
+    if ns.set.counterparty_id is not None and m.counterparty_id is not None and m.counterparty_id != ns.set.counterparty_id:
+        return
+    cp_surv, own_surv = ctx.base._fva_atoms[m_i]
+    sums = ctx.be.tangent_fva(ctx.base.book, chunk.datoms, ctx.rows, cp_surv, own_surv, m.w_borrow, m.w_lend, ns.set.threshold,
+                              img.expo, ns.i, img.paths, img.dpaths, ns.delayed, ns.coll)
+    mean = ctx.shard.all_reduce_np(sums) / float(ctx.sc.num_paths_mainsim)
+    for e_i in range(3):                                                      # FVAMetric.EVALUATIONS order
+        for q, j in enumerate(chunk.sel):
+            out[e_i][j] = float(mean[e_i, 1 + q])
+
+
 _SCATTER = {MetricType.PV: _scatter_pv, MetricType.CVA: _scatter_cva, MetricType.PFE: _scatter_pfe, MetricType.EPE: _scatter_profile,
             MetricType.ENE: _scatter_profile, MetricType.CE: _scatter_profile, MetricType.EEPE: _scatter_profile,
-            MetricType.DVA: _scatter_xva, MetricType.BCVA: _scatter_xva}
+            MetricType.DVA: _scatter_xva, MetricType.BCVA: _scatter_xva, XvaMetricType.FVA: _scatter_fva}
 
 
 def _scatter_metric_tangents(ctx, chunk, img, grads):

@@ -304,6 +304,11 @@ class SimulationController:
         # collective per netting set, metric and pass; False: one such metric sends the whole book to bump-and-revalue.  Independent
         # of the path-route flags above: the scatter reads only the dual images of a pass, so it composes with every route
         self.tangent_xva = False
+        # differentiate=True: True keeps a book whose RiskMetrics holds a native FVAMetric on the forward-mode book pass: its three
+        # records take their tangents from mcx_tangent_fva (mcx/aad.py _scatter_fva), one launch and one collective per netting set,
+        # metric and pass; False: one FVAMetric sends the whole book to bump-and-revalue.  Independent of tangent_xva (a book with
+        # FVA and bilateral CVA needs both) and of the path-route flags
+        self.tangent_fva = False
         self._force_wide_plan = False    # set by aad._clone_controller only: build the SimPlan with force_wide=True
         # The reference compiles nothing: every run_simulation() sees the current state of its products / metrics.  Re-using the
         # compiled descriptors and the uploaded book of the previous run is an opt-in for callers that re-run an UNCHANGED
